@@ -3,6 +3,16 @@
 
     python bench.py --gpus N --steps K --warmup W [--workload qws|normal|synth4|synth5] [--batch B]
                     [--precision f32|split|f16] [--scaling weak|strong] [--global-batch G]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warm-up steps, times EXACTLY K steps once, writes the last timed step's outputs if
+--dump-outputs is given, and prints the line: `value` / `ms_per_step` are that one timed region.  Everything else —
+the CPU baseline, the other precision, the per-kernel table and roofline, the PCIe-inclusive rate, the self-checks
+against single-stream runs, and the repeated / settling rounds of the timed region — runs only with --full.
+  --dump-outputs DIR  writes the arrays the last timed step returned (rank 0's step outputs dict) as DIR/<name>.npy:
+                      float32, or float64 for integer arrays (exact).  Above 60 MiB in all, every array keeps the same
+                      seeded sample of the problems (rows of the batch dimension), whose indices are DIR/sample_rows.npy.
+                      The inputs are seeded: the same arguments give the same inputs in every run.
 
 A "step" = one pass of the whole hot path over one batch of B synthetic problems that is already
 resident in HBM: GNN scores -> per-category top-K feasible candidates -> Low/High pointer-network
@@ -14,11 +24,12 @@ processes BEFORE anything touches a GPU and exits with their status.  Rank 0 pri
   --scaling strong the global batch is fixed (--global-batch, default the workload's: 4096 for synth4 = BASELINE
                    configs[3] "batch=4096 sharded over 8") and sharded contiguously: rank r runs G/N problems per step
 No data-path collective besides the one all-gather of the selected indices.
-The timed region (exactly K steps between barrier + synchronize on both sides, MAX over ranks) is REPEATED until at
-least 1 s has been measured; `value` / `ms_per_step` are the median round, `timing` carries min / median / max.
+The timed region is exactly K steps between barrier + synchronize on both sides, MAX over ranks.  With --full it is
+REPEATED until at least 1 s has been measured (behind untimed settling rounds); `value` / `ms_per_step` are then the
+median round, `timing` carries min / median / max.  Every round runs the same steps W .. W+K-1.
 Steps rotate over --batches (default 4) distinct resident batches per rank.
 
-Extra objects on the line:
+Extra objects on the line (--full only):
   roofline     : the dominant kernel by time, priced against the bound that applies to it
   kernels      : every timed kernel of the step (avg ms, algorithmic bytes/flops, fraction of peak), plus — marked
                  "in_step": false — the GCN aggregate on the reference's batching of the service graph (B copies),
@@ -28,7 +39,7 @@ Extra objects on the line:
   other_precision : a second measurement of the same workload in the OTHER arithmetic of the recurrent W_hh.h products —
                  the fp32 matrix cores when `value` is the exact split (the default), the exact split when `value` is f32 —
                  with its own kernel table and the agreement of the two results; reported beside `value`, never as `value`
-Defaults: --gpus 1 --steps 100 --warmup 10 --workload qws (a few seconds of GPU time + ~10 s of CPU baseline).
+Defaults: --gpus 1 --steps 100 --warmup 10 --workload qws (a few seconds; with --full ~10 s more of CPU baseline).
 """
 import argparse
 import contextlib
@@ -136,6 +147,36 @@ class KernelTimers:
             for k, v in self.events.items():
                 print(k, [round(a.elapsed_time(b), 3) for a, b in v], file=sys.stderr)
         return {k: (sum(a.elapsed_time(b) for a, b in v) / len(v), len(v)) for k, v in self.events.items()}
+
+
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(out, directory, n_problems, seed=0):
+    """--dump-outputs: the tensors of one step's outputs dict as ``directory/<name>.npy`` — float32 (float64 stays float64), integer
+    and boolean arrays as float64, which holds them exactly.  Above DUMP_LIMIT_BYTES in all, every array whose leading dimension
+    is the batch keeps the same seeded sample of the problems, in order, and ``sample_rows.npy`` lists the sampled indices."""
+    import numpy as np
+    arrays = {}
+    for name, v in sorted(out.items()):
+        if not isinstance(v, torch.Tensor):
+            continue
+        v = v.detach().cpu()
+        v = v.double() if not v.is_floating_point() or v.dtype == torch.float64 else v.float()
+        arrays[name] = v.numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        per_problem = sum(a.nbytes for a in arrays.values() if a.ndim and a.shape[0] == n_problems) / n_problems
+        rest = total - per_problem * n_problems
+        n = int((DUMP_LIMIT_BYTES - rest) // (per_problem + 8))          # + its float64 entry in sample_rows
+        if n < 1:
+            raise SystemExit(f"--dump-outputs: {total} bytes of outputs, not even one problem fits in {DUMP_LIMIT_BYTES}")
+        rows = np.sort(np.random.default_rng(seed).choice(n_problems, size=n, replace=False))
+        arrays = {k: (a[rows] if a.ndim and a.shape[0] == n_problems else a) for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name.replace("/", "_") + ".npy"), np.ascontiguousarray(a))
 
 
 def _oracle_pass(ctx, lo, hi):
@@ -512,9 +553,16 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0, help="strong scaling: problems per step over ALL GPUs "
                     "(default: the workload's G, else its per-GPU batch)")
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches the steps rotate over")
-    ap.add_argument("--min-time", type=float, default=1.0, help="repeat the K-step timed region until this many seconds")
-    ap.add_argument("--settle", type=int, default=24, help="at most this many UNTIMED rounds of K steps behind the warm-up, until three in a row "
-                    "agree within 2 %% (0: none — the first timed round follows the W warm-up steps directly); they are listed in timing.settling_round_us")
+    ap.add_argument("--min-time", type=float, default=None, help="repeat the K-step timed region until this many seconds "
+                    "(default: 1.0 with --full, else 0 — one timed region of exactly K steps)")
+    ap.add_argument("--settle", type=int, default=None, help="at most this many UNTIMED rounds of K steps behind the warm-up, until three in a row "
+                    "agree within 2 %% (0: none — the first timed round follows the W warm-up steps directly); they are listed in timing.settling_round_us "
+                    "(default: 24 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: CPU baseline, other precision, kernel table and roofline, "
+                         "PCIe-inclusive rate, self-checks, repeated timed rounds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 60 MiB in all)")
     ap.add_argument("--write-through", type=int, default=-1, help="hand-off form of the cooperative kernels: 1 = agent-scope write-through "
                     "granule stores (placement independent), 0 = stores that stay in the XCD's L2 (same-XCD groups), -1 = the library's default")
     ap.add_argument("--precision", default="split", choices=["f32", "f16", "split"],
@@ -535,6 +583,10 @@ def main():
     ap.add_argument("--inflight", type=int, default=2,
                     help="independent steps (batches) in flight on separate HIP streams (needs --graph 1)")
     args = ap.parse_args()
+    if args.min_time is None:
+        args.min_time = 1.0 if args.full else 0.0
+    if args.settle is None:
+        args.settle = 24 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                                 # never returns
@@ -573,7 +625,7 @@ def main():
     # P processes x t threads is the honest use of the host's cores), which a GPU-initialised process must not do.
     # Same seeded weights as the GPU run below (build_models seeds torch before constructing them).
     cpu_line = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         net_c, low_c, high_c = build_models(T, S, K, torch.device("cpu"), w["n_gcn"])
         cpu_line = cpu_baseline(w, table, pb, *({k: v.detach().clone() for k, v in m.state_dict().items()} for m in (net_c, low_c, high_c)))
         del net_c, low_c, high_c
@@ -617,7 +669,7 @@ def main():
     del host_batches[1:]
 
     timers = KernelTimers()
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         # the mirrors reach the kernels through the C++ operators: the two recurrent launches and the GCN aggregate through
         # custom_ops' callers, the rest as torch.ops.gnnpn.* (an attribute of the namespace object: wrapped the same way)
         from gnnpn_sc_amd import custom_ops
@@ -750,13 +802,13 @@ def main():
         Between two rounds the runner is waited for through ITS synchronize() (besides the device-wide one), as a caller that
         works in bursts of K steps would: the runner then starts the next burst's two slots together (pipeline.COMMON_START_US;
         the hold is inside the timed region)."""
-        rounds, total, i0, res = [], 0.0, args.warmup, None
+        rounds, total, res = [], 0.0, None
         timed_rounds.local = []
         timed_rounds.bad = 0              # OR of the status every round's poll returned (failure codes | shortfall of finished tiles)
         timed_rounds.polls = 0
 
         def one_round():
-            nonlocal i0, res
+            nonlocal res
             rn = runner if runner is not None else cur["runner"]
             if rn is not None:
                 # between two rounds (outside the timed region): wait for the runner AND check the previous round — failure
@@ -768,11 +820,10 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                res = run_step(i0 + i)
+                res = run_step(args.warmup + i)     # every round the same steps: the last one's batch does not depend on the round count
             finish_gathers()                  # every step's all-gather has landed before the clock stops
             torch.cuda.synchronize()
             gdist.barrier(world)
-            i0 += args.steps
             local = time.perf_counter() - t0
             timed_rounds.local.append(local)
             return gdist.max_over_ranks(local, dev, world)
@@ -871,6 +922,8 @@ def main():
     runner = cur["runner"]
     elapsed, timing = summarise(rounds)
     ops.check_status(dev)
+    if args.dump_outputs and rank == 0:          # before anything else runs: what the last timed step returned
+        dump_outputs(step.last, args.dump_outputs, B)
     # per-rank record (every rank contributes; rank 0 prints): this rank's own step time, whether it degraded, and the placement
     # counters of its slots' last encoder launches (members placed, seats off their canonical CU, declined seats)
     lr = sorted(timed_rounds.local)
@@ -888,29 +941,31 @@ def main():
         import torch.distributed as td
         per_rank = [None] * world
         td.all_gather_object(per_rank, mine)
-    # self-check: every slot's (overlapped) result equals a single-stream run of the same kernels on the same batch
     decode_impl = runner.decode_impl if runner is not None else 0
-    with gpu_turn(share):
-        ref = pipe.run(svc, batch, decode_impl=decode_impl)
-        torch.cuda.synchronize()
     agreement = None
-    if args.precision != "f32":       # agreement of the reduced-precision mode with the f32 path: same batch,
+    if args.full:
+        # self-check: every slot's (overlapped) result equals a single-stream run of the same kernels on the same batch
         with gpu_turn(share):
-            r32 = ML2PNPipeline(net, low, high, K, precision="f32").run(svc, batch)   # compared on the SELECTED rows (dummy /
-            torch.cuda.synchronize()                                  # duplicate candidates are one selection)
-        same = (ref["actions"] == r32["actions"]).all(-1)
-        agreement = {"problems_with_identical_selection": round(float(same.all(1).float().mean()), 4),
-                     "identical_decisions": round(float(same.float().mean()), 5),
-                     "mean_abs_R_diff": round(float((ref["R"] - r32["R"]).abs().mean()), 6)}
-    if runner is not None:
-        for s in range(runner.n_slots):
-            if (id(runner), s) not in last:        # fewer steps than slots
-                continue
-            o = runner.graphs[s].outputs
+            ref = pipe.run(svc, batch, decode_impl=decode_impl)
+            torch.cuda.synchronize()
+        if args.precision != "f32":       # agreement of the reduced-precision mode with the f32 path: same batch,
             with gpu_turn(share):
-                rj = pipe.run(svc, batches[last[(id(runner), s)]], decode_impl=decode_impl)
-            if not (torch.equal(o["idx_high"], rj["idx_high"]) and torch.equal(o["R"], rj["R"])):
-                raise SystemExit(f"slot {s}: overlapped result differs from the single-stream run")
+                r32 = ML2PNPipeline(net, low, high, K, precision="f32").run(svc, batch)   # compared on the SELECTED rows (dummy /
+                torch.cuda.synchronize()                                  # duplicate candidates are one selection)
+            same = (ref["actions"] == r32["actions"]).all(-1)
+            agreement = {"problems_with_identical_selection": round(float(same.all(1).float().mean()), 4),
+                         "identical_decisions": round(float(same.float().mean()), 5),
+                         "mean_abs_R_diff": round(float((ref["R"] - r32["R"]).abs().mean()), 6)}
+        if runner is not None:
+            for s in range(runner.n_slots):
+                if (id(runner), s) not in last:        # fewer steps than slots
+                    continue
+                o = runner.graphs[s].outputs
+                with gpu_turn(share):
+                    rj = pipe.run(svc, batches[last[(id(runner), s)]], decode_impl=decode_impl)
+                if not (torch.equal(o["idx_high"], rj["idx_high"]) and torch.equal(o["R"], rj["R"])):
+                    raise SystemExit(f"slot {s}: overlapped result differs from the single-stream run")
+
     def kernel_pass(rn):
         """Per-kernel durations of one runner's step: an eager single-stream pass with HIP event pairs around the C-ABI calls
         (events cannot be read back from a replayed graph).  -> (events summary, passes)."""
@@ -947,7 +1002,7 @@ def main():
         return out
 
     n_timed, summary = args.steps, timers.summary()
-    if args.graph and not args.no_kernel_timers:
+    if args.full and args.graph and not args.no_kernel_timers:
         with gpu_turn(share):
             summary, n_timed = kernel_pass(runner)
     gc.enable()
@@ -959,7 +1014,7 @@ def main():
     PREC_TEXT = {"f32": "W_hh.h of encoder and decoder on the fp32 matrix cores (v_mfma_f32_16x16x4_f32)",
                  "split": "W_hh.h of encoder and decoder from fp32 operands split EXACTLY into three fp16 pieces, six fp16 "
                           "products per term (every cross term >= 2^-24 kept), fp32 accumulate; rest f32"}
-    if other and args.graph and not args.no_split_line:
+    if args.full and other and args.graph and not args.no_split_line:
         pipe_s = ML2PNPipeline(net, low, high, K, precision=other)
         with gpu_turn(share):
             runner_s = PipelinedRunner(pipe_s, svc, batch, slots=n_slots, halves=False if share else None)
@@ -999,94 +1054,96 @@ def main():
             if st.get("gathered_rows", 0) % (world * B) != 0 or st.get("gathered_rows", 0) == 0:
                 raise SystemExit(f"bucketed all-gather returned {st.get('gathered_rows')} rows, expected a multiple of {world * B}")
     value = world * B * args.steps / elapsed
-    kernels = kernel_table(summary, n_timed, args.precision)
-    # HBM traffic per launch from the committed PMC passes (rocprofv3 cannot run inside this process):
-    # profiles/r05_pmc_traffic.json (tools/r05_profiles.sh + tools/collect_profiles.py; r04's while that one is absent), FETCH_SIZE doubled as the gfx950 guide
-    # prescribes; only quoted when this run is a workload / batch / precision those passes measured.
-    # Both summaries carry the source hash of the tree they were measured on (gnnpn_sc_amd._lib.source_hash); they are quoted only
-    # while it equals the loaded library's — after any kernel change they read null until the passes have been re-run.
-    from gnnpn_sc_amd import _lib as _glib
-    lib_hash = _glib.source_hash()
-    counters_state = {}
+    kernels, roof = [], None
+    if args.full:          # the kernel table, roofline and counter quotes
+        kernels = kernel_table(summary, n_timed, args.precision)
+        # HBM traffic per launch from the committed PMC passes (rocprofv3 cannot run inside this process):
+        # profiles/r05_pmc_traffic.json (tools/r05_profiles.sh + tools/collect_profiles.py; r04's while that one is absent), FETCH_SIZE doubled as the gfx950 guide
+        # prescribes; only quoted when this run is a workload / batch / precision those passes measured.
+        # Both summaries carry the source hash of the tree they were measured on (gnnpn_sc_amd._lib.source_hash); they are quoted only
+        # while it equals the loaded library's — after any kernel change they read null until the passes have been re-run.
+        from gnnpn_sc_amd import _lib as _glib
+        lib_hash = _glib.source_hash()
+        counters_state = {}
 
-    def committed(name):
-        """A committed counter summary, or None when it was not measured on the sources of the kernels it is about (`source_group`:
-        the recurrent kernels' or the aggregate's files, gnnpn_sc_amd._lib.SOURCE_GROUPS; absent: the whole tree)."""
-        with open(os.path.join(ROOT, "profiles", name)) as f:
-            d = json.load(f)
-        now = _glib.source_hash(d.get("source_group"))
-        counters_state[name] = "current" if d.get("source_hash") == now else f"stale (measured on sources {d.get('source_hash')}, the tree's are {now}): not quoted"
-        return d if d.get("source_hash") == now else None
+        def committed(name):
+            """A committed counter summary, or None when it was not measured on the sources of the kernels it is about (`source_group`:
+            the recurrent kernels' or the aggregate's files, gnnpn_sc_amd._lib.SOURCE_GROUPS; absent: the whole tree)."""
+            with open(os.path.join(ROOT, "profiles", name)) as f:
+                d = json.load(f)
+            now = _glib.source_hash(d.get("source_group"))
+            counters_state[name] = "current" if d.get("source_hash") == now else f"stale (measured on sources {d.get('source_hash')}, the tree's are {now}): not quoted"
+            return d if d.get("source_hash") == now else None
 
-    def pmc_traffic(precision):
-        try:
-            name = next(n for n in ("r06_pmc_traffic.json", "r05_pmc_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
-            pmc = committed(name)
-            if pmc is None:
+        def pmc_traffic(precision):
+            try:
+                name = next(n for n in ("r06_pmc_traffic.json", "r05_pmc_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
+                pmc = committed(name)
+                if pmc is None:
+                    return {}
+                # the summary's hash covers the recurrent kernels' sources; the other kernels of the table are quoted only while the WHOLE tree is unchanged
+                rest_ok = pmc.get("source_hash_all") == lib_hash
+                return {k: v["traffic"] for k, v in pmc.get(f"{args.workload}_b{B}_{precision}", {}).get("kernels", {}).items()
+                        if rest_ok or k in ("lstm_encode", "pointer_decode")}
+            except (OSError, ValueError, KeyError, StopIteration):
                 return {}
-            # the summary's hash covers the recurrent kernels' sources; the other kernels of the table are quoted only while the WHOLE tree is unchanged
-            rest_ok = pmc.get("source_hash_all") == lib_hash
-            return {k: v["traffic"] for k, v in pmc.get(f"{args.workload}_b{B}_{precision}", {}).get("kernels", {}).items()
-                    if rest_ok or k in ("lstm_encode", "pointer_decode")}
-        except (OSError, ValueError, KeyError, StopIteration):
-            return {}
-    # Matrix-pipe utilisation of the two recurrent kernels (BASELINE north_star: "MFMA utilisation ... against gfx950 peak") from the
-    # committed SQ-counter passes of the same eager command (tools/r05_recurrent_sq.sh -> profiles/r05_recurrent_sq_summary.json):
-    # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8).  Quoted, like `traffic`: rocprofv3 cannot run inside this process.
-    def sq_mfma_util(precision):
-        try:
-            name = next(n for n in ("r06_recurrent_sq_summary.json", "r05_recurrent_sq_summary.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
-            sq = committed(name)
-            if sq is None:
+        # Matrix-pipe utilisation of the two recurrent kernels (BASELINE north_star: "MFMA utilisation ... against gfx950 peak") from the
+        # committed SQ-counter passes of the same eager command (tools/r05_recurrent_sq.sh -> profiles/r05_recurrent_sq_summary.json):
+        # SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8).  Quoted, like `traffic`: rocprofv3 cannot run inside this process.
+        def sq_mfma_util(precision):
+            try:
+                name = next(n for n in ("r06_recurrent_sq_summary.json", "r05_recurrent_sq_summary.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
+                sq = committed(name)
+                if sq is None:
+                    return {}
+                sq = sq["kernels"]
+                names = {"lstm_encode": "lstm_encode_coop_kernel", "pointer_decode": "pointer_decode_lean_kernel"}
+                return {k: sq[f"{args.workload}/{precision}/{n}"]["derived"]["mfma_busy_frac_of_all_simds"] for k, n in names.items()
+                        if f"{args.workload}/{precision}/{n}" in sq and B == WORKLOADS[args.workload]["B"]}     # the passes ran the default batch
+            except (OSError, ValueError, KeyError, StopIteration):
                 return {}
-            sq = sq["kernels"]
-            names = {"lstm_encode": "lstm_encode_coop_kernel", "pointer_decode": "pointer_decode_lean_kernel"}
-            return {k: sq[f"{args.workload}/{precision}/{n}"]["derived"]["mfma_busy_frac_of_all_simds"] for k, n in names.items()
-                    if f"{args.workload}/{precision}/{n}" in sq and B == WORKLOADS[args.workload]["B"]}     # the passes ran the default batch
-        except (OSError, ValueError, KeyError, StopIteration):
-            return {}
-    traffic = pmc_traffic(args.precision)
-    util = sq_mfma_util(args.precision)
-    for k in kernels:
-        k["traffic"] = traffic.get(k["kernel"])
-        if k["kernel"] in util:
-            k["mfma_util"] = util[k["kernel"]]
-    if other_line is not None and "kernels" in other_line:
-        t2, u2 = pmc_traffic(other), sq_mfma_util(other)
-        for k in other_line["kernels"]:
-            k["traffic"] = t2.get(k["kernel"])
-            if k["kernel"] in u2:
-                k["mfma_util"] = u2[k["kernel"]]
-    if world == 1 and args.graph and not args.no_kernel_timers:
-        agg = batched_aggregate_roofline(table, B, dev)
-        try:     # the committed PMC passes of tools/r04_aggregate_profiles.sh, keyed by shape (rows per copy x copies) and kernel
-            pname = next(n for n in ("r06_csr_aggregate_pmc_traffic.json", "r05_csr_aggregate_pmc_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
-            pm = committed(pname)
-            if pm is None:
-                raise KeyError(pname)
-            kname = {"tiled": "csr_aggregate_tiled_kernel", "l2-gather": "csr_aggregate_kernel"}.get(agg["form"])
-            agg["traffic"] = pm["shapes"][f"{agg['rows'] // agg['copies']}x{agg['copies']}"][kname]["traffic"]
-        except (OSError, ValueError, KeyError, ZeroDivisionError, StopIteration):
-            agg["traffic"] = None
-    roof = None
-    if kernels:
-        k0 = kernels[0]
-        roof = {"kernel": k0["kernel"], "bound": k0["bound"], "achieved": k0["achieved"], "peak": k0["peak"],
-                "unit": k0["unit"], "frac": k0["frac"], "traffic": k0["traffic"],
-                # where `traffic` and `mfma_util` come from: committed rocprofv3 --pmc passes of the same eager command, NOT this run
-                "counters_from": {"what": "committed rocprofv3 --pmc passes of the same eager command: FETCH_SIZE x 2 + WRITE_SIZE per launch; SQ_VALU_MFMA_BUSY_CYCLES / SIMD-cycles",
-                                  "library_source_hash": lib_hash, "files": counters_state}}
-        if "mfma_util" in k0:
-            roof["mfma_util"] = k0["mfma_util"]
-        if "fp32_equivalent" in k0:      # split: `achieved` counts the six EXECUTED f16 products per fp32 term
-            roof["fp32_equivalent"] = k0["fp32_equivalent"]
+        traffic = pmc_traffic(args.precision)
+        util = sq_mfma_util(args.precision)
+        for k in kernels:
+            k["traffic"] = traffic.get(k["kernel"])
+            if k["kernel"] in util:
+                k["mfma_util"] = util[k["kernel"]]
+        if other_line is not None and "kernels" in other_line:
+            t2, u2 = pmc_traffic(other), sq_mfma_util(other)
+            for k in other_line["kernels"]:
+                k["traffic"] = t2.get(k["kernel"])
+                if k["kernel"] in u2:
+                    k["mfma_util"] = u2[k["kernel"]]
+        if world == 1 and args.graph and not args.no_kernel_timers:
+            agg = batched_aggregate_roofline(table, B, dev)
+            try:     # the committed PMC passes of tools/r04_aggregate_profiles.sh, keyed by shape (rows per copy x copies) and kernel
+                pname = next(n for n in ("r06_csr_aggregate_pmc_traffic.json", "r05_csr_aggregate_pmc_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
+                pm = committed(pname)
+                if pm is None:
+                    raise KeyError(pname)
+                kname = {"tiled": "csr_aggregate_tiled_kernel", "l2-gather": "csr_aggregate_kernel"}.get(agg["form"])
+                agg["traffic"] = pm["shapes"][f"{agg['rows'] // agg['copies']}x{agg['copies']}"][kname]["traffic"]
+            except (OSError, ValueError, KeyError, ZeroDivisionError, StopIteration):
+                agg["traffic"] = None
+        roof = None
+        if kernels:
+            k0 = kernels[0]
+            roof = {"kernel": k0["kernel"], "bound": k0["bound"], "achieved": k0["achieved"], "peak": k0["peak"],
+                    "unit": k0["unit"], "frac": k0["frac"], "traffic": k0["traffic"],
+                    # where `traffic` and `mfma_util` come from: committed rocprofv3 --pmc passes of the same eager command, NOT this run
+                    "counters_from": {"what": "committed rocprofv3 --pmc passes of the same eager command: FETCH_SIZE x 2 + WRITE_SIZE per launch; SQ_VALU_MFMA_BUSY_CYCLES / SIMD-cycles",
+                                      "library_source_hash": lib_hash, "files": counters_state}}
+            if "mfma_util" in k0:
+                roof["mfma_util"] = k0["mfma_util"]
+            if "fp32_equivalent" in k0:      # split: `achieved` counts the six EXECUTED f16 products per fp32 term
+                roof["fp32_equivalent"] = k0["fp32_equivalent"]
     line = {
         "metric": "service-composition problems/sec (ML+2PN inference)", "value": round(value, 2),
         "unit": "problems/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
         "vs_baseline": None, "dtype": {"f32": "f32", "f16": "f16 encoder operands / f32 rest",
                                        # its own token, not "f32": a consumer keyed on dtype must not compare this line with an
-                                       # fp32-MFMA line of another round as like with like (ADVICE r3); `agreement_vs_f32` is always in the line
+                                       # fp32-MFMA line of another round as like with like (ADVICE r3); `agreement_vs_f32` is in every --full line
                                        "split": "f32-split3xf16 (f32 operands and results; recurrent W_hh.h products: fp32 operands split exactly into 3 x f16, "
                                                 "six f16-matrix-core products per term, f32 accumulate; everything else f32 arithmetic)"}[args.precision],
         "precision": args.precision,
@@ -1097,9 +1154,9 @@ def main():
                               "hipGraph replay, one step in flight, its recurrent part as two half-batches side by side on two HIP "
                               "streams (cooperative launches paired on every CU)" if runner.halves else
                               f"hipGraph replay, {runner.n_streams} independent step(s) in flight on separate HIP streams"),
-                   "kernel_timing": ("HIP events in a separate single-stream pass" if args.graph else
-                                     "HIP events inside the timed region (durations include overlap with the "
-                                     "other in-flight step)"),
+                   **({"kernel_timing": ("HIP events in a separate single-stream pass" if args.graph else
+                                         "HIP events inside the timed region (durations include overlap with the "
+                                         "other in-flight step)")} if args.full else {}),
                    "service_embedding": "problem-independent GCN branch evaluated once per (weights, service table), "
                                         "outside the step (SURVEY.md section 7)",
                    "weights": "random-init (PyTorch defaults, seed 0)", "parallelism": f"dp{world}",
@@ -1109,9 +1166,10 @@ def main():
                    **({"rank0_cpu_affinity": affinity} if affinity is not None else {}),
                    **({"NOT_A_MEASUREMENT": "GNNPN_BENCH_SHARE_GPU=1: all ranks share one GPU over gloo (launch-path check)"}
                       if share else {})},
-        "roofline": roof, "kernels": kernels + ([agg] if world == 1 and args.graph and not args.no_kernel_timers else []),
+        **({"roofline": roof, "kernels": kernels + ([agg] if world == 1 and args.graph and not args.no_kernel_timers else [])}
+           if args.full else {}),
     }
-    if world == 1 and args.graph and not args.no_kernel_timers and not share and not use_dist:
+    if args.full and world == 1 and args.graph and not args.no_kernel_timers and not share and not use_dist:
         with gpu_turn(share):
             n_pcie = max(100, min(2000, int(0.25 / max(elapsed / args.steps, 1e-6))))      # about a quarter of a second of steps
             pv = pcie_inclusive_rate(runner, batches, B, T, n_pcie, dev)

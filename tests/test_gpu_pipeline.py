@@ -978,9 +978,10 @@ def test_soak_beside_a_collective_shaped_interferer(dev, shape):
 
 
 def test_bench_line_contract(dev):
-    """bench.py as the driver runs it (a child process, `--gpus 1 --steps K --warmup W`): exit 0, exactly ONE JSON line on
+    """bench.py --full as a child process (`--gpus 1 --steps K --warmup W --full`): exit 0, exactly ONE JSON line on
     stdout with the contract's keys, the BASELINE metric / config, a roofline object for the dominant kernel and the CPU
-    baseline; and the self-launching `--gpus 4` entry (four ranks on this one GPU over gloo: launch path only), weak and strong."""
+    baseline; and the self-launching `--gpus 4` entry (four ranks on this one GPU over gloo: launch path only), weak and strong.
+    (The plain line, without --full: test_bench_plain_line_and_dump_outputs.)"""
     import json
     import os
     import subprocess
@@ -990,7 +991,7 @@ def test_bench_line_contract(dev):
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_PORT", "GNNPN_FORCE_DIST")}
     env["PYTHONPATH"] = root
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--min-time", "0",
-                        "--no-split-line"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--no-split-line", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -1027,7 +1028,7 @@ def test_bench_line_contract(dev):
     # phase is repeated and the line says so
     env_d = dict(env, GNNPN_BENCH_FORCE_DEGRADE="timed", GNNPN_FORCE_DIST="1")
     rd = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--min-time", "0.05",
-                         "--no-split-line", "--no-cpu-baseline", "--no-kernel-timers"], capture_output=True, text=True, timeout=600,
+                         "--no-split-line", "--no-cpu-baseline", "--no-kernel-timers", "--full"], capture_output=True, text=True, timeout=600,
                         env=env_d, cwd=root)
     assert rd.returncode == 0, rd.stderr[-2000:]
     dd = json.loads([ln for ln in rd.stdout.splitlines() if ln.strip()][-1])
@@ -1043,7 +1044,7 @@ def test_bench_line_contract(dev):
     env2 = dict(env, GNNPN_BENCH_SHARE_GPU="1")
     for extra, gb in ((["--batch", "32"], 4 * 32), (["--scaling", "strong", "--global-batch", "128"], 128)):
         r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--min-time", "0",
-                             "--no-cpu-baseline", "--no-split-line", "--no-kernel-timers"] + extra, capture_output=True, text=True,
+                             "--no-cpu-baseline", "--no-split-line", "--no-kernel-timers", "--full"] + extra, capture_output=True, text=True,
                             timeout=900, env=env2, cwd=root)
         assert r2.returncode == 0, r2.stderr[-2000:]
         out2 = [ln for ln in r2.stdout.splitlines() if ln.strip()]
@@ -1055,8 +1056,53 @@ def test_bench_line_contract(dev):
     # ... and with ONE of the four ranks reporting a hand-off status after the warm-up: that rank degrades, every rank repeats
     # the phase (the collectives of a phase are counted the same on all ranks), the line names the rank
     r3 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--min-time", "0",
-                         "--no-cpu-baseline", "--no-split-line", "--no-kernel-timers", "--batch", "32"], capture_output=True, text=True,
+                         "--no-cpu-baseline", "--no-split-line", "--no-kernel-timers", "--full", "--batch", "32"], capture_output=True, text=True,
                         timeout=900, env=dict(env2, GNNPN_BENCH_FORCE_DEGRADE="warmup", GNNPN_BENCH_FORCE_DEGRADE_RANK="2"), cwd=root)
     assert r3.returncode == 0, r3.stderr[-2000:]
     d3 = json.loads([ln for ln in r3.stdout.splitlines() if ln.strip()][-1])
     assert [x["rank"] for x in d3["degraded"]] == [2] and [bool(p["degraded"]) for p in d3["per_rank"]] == [False, False, True, False]
+
+
+def test_bench_plain_line_and_dump_outputs(dev, tmp_path):
+    """bench.py as the driver runs it (a child process, `--gpus 1 --steps K --warmup W`, no --full): exit 0, exactly ONE JSON
+    line, ONE timed region of exactly K steps, the headline keys and nothing measured beside them; --dump-outputs writes the
+    last timed step's outputs as float32 / float64 .npy files, and a second run with the same arguments writes the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()                 # an earlier test's process group left RANK / WORLD_SIZE behind
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_PORT", "GNNPN_FORCE_DIST")}
+    env["PYTHONPATH"] = root
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 7 and d["warmup"] == 3 and d["value"] > 0 and d["higher_is_better"] is True
+        assert d["dtype"].split()[0] == "f32-split3xf16" and d["unit"] == "problems/s"
+        t = d["timing"]
+        assert t["rounds"] == 1 and t["steps_per_round"] == 7 and t["untimed_settling_rounds"] == 0
+        assert abs(d["ms_per_step"] - t["round_ms"]["median"] / 7) < 1e-3
+        assert abs(d["value"] - d["config"]["batch_per_gpu"] * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        for k in ("cpu_baseline", "other_precision", "agreement_vs_f32", "kernels", "roofline", "pcie_inclusive"):
+            assert k not in d, k
+        files = sorted(os.listdir(out))
+        arrays = {f: np.load(out / f, allow_pickle=False) for f in files}
+        assert all(f.endswith(".npy") for f in files) and {"idx_high.npy", "R.npy", "scores.npy"} <= set(files), files
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+        B, T = d["config"]["batch_per_gpu"], 47
+        assert arrays["idx_high.npy"].shape == (B, T) and arrays["R.npy"].shape == (B,)
+        assert np.all(arrays["idx_high.npy"] >= 0) and np.all(np.isfinite(arrays["R.npy"]))
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:                                         # same arguments, same inputs: the same outputs
+        assert np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True), f

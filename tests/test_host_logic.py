@@ -394,6 +394,31 @@ def test_bench_strong_scaling_partition_is_the_same_global_set():
     assert b0.batch.max() == 31 and b0.edge_index.max() == b0.x.shape[0] - 1       # offsets of the merged chunks
 
 
+def test_bench_dump_outputs_types_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every tensor of a step's outputs as float32 / float64 (integers exact in float64); above the
+    size limit, every batch-shaped array keeps the same seeded sample of problems, in order, listed in sample_rows.npy."""
+    import bench
+    B, T = 64, 5
+    out = {"idx_high": torch.arange(B * T, dtype=torch.int32).view(B, T), "R": torch.linspace(0, 1, B),
+           "candidate_ids": torch.arange(B * 40, dtype=torch.int64).view(B, 40) + 2 ** 40, "mask": torch.ones(B, T, dtype=torch.bool),
+           "half": torch.ones(B, 3, dtype=torch.float16), "not_a_tensor": 3}
+    bench.dump_outputs(out, str(tmp_path / "whole"), B)
+    got = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert set(got) == {"idx_high", "R", "candidate_ids", "mask", "half"}
+    assert got["idx_high"].dtype == np.float64 and got["R"].dtype == np.float32 and got["half"].dtype == np.float32
+    assert np.array_equal(got["candidate_ids"], out["candidate_ids"].numpy().astype(np.float64))
+    limit = 20 * (T * 8 + 4 + 40 * 8 + T * 8 + 3 * 4 + 8)           # room for 20 of the 64 problems and their sample_rows entries
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(out, str(tmp_path / run), B)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    rows = s1["sample_rows.npy"].astype(np.int64)
+    assert len(rows) == 20 and np.all(np.diff(rows) > 0) and sum(a.nbytes for a in s1.values()) <= limit
+    assert np.array_equal(s1["idx_high.npy"], out["idx_high"].numpy()[rows].astype(np.float64))
+    assert s1.keys() == s2.keys() and all(np.array_equal(s1[f], s2[f]) for f in s1)
+
+
 def test_half_batch_split_keeps_whole_tiles_in_the_first_half():
     """pipeline.half_batch_split: the cut the paired half-batches use (tiles of 16 problems never straddle it; both halves
     non-empty; the halves differ by at most one tile)."""

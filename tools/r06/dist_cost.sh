@@ -10,7 +10,7 @@ for cfg in plain:0 dist:8 dist:32 dist:1; do
   mode=${cfg%%:*}; ge=${cfg#*:}
   extra=""; [ $mode = dist ] && extra="--gather-every $ge"
   fd=0; [ $mode = dist ] && fd=1
-  GNNPN_FORCE_DIST=$fd timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision $extra > $O/${mode}_${ge}_$i.json 2> $O/${mode}_${ge}_$i.err
+  GNNPN_FORCE_DIST=$fd timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision $extra > $O/${mode}_${ge}_$i.json 2> $O/${mode}_${ge}_$i.err
   python3 -c "
 import json
 d=json.loads([l for l in open('$O/${mode}_${ge}_$i.json') if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 mkdir -p gpurun_out
 P='import json,sys; d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); print(d["value"], d["ms_per_step"], d["config"].get("slot_stream_priority"), (d.get("pcie_inclusive") or {}).get("ratio_to_value"), [r.get("collective_ms") for r in d.get("per_rank", [])][:1])'
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision"
 if [ "${1:-grid}" = grid ]; then
 for i in 1 2; do
 for cfg in "4 0" "4 -1" "8 0" "8 -1"; do

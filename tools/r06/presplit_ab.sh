@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 for i in 1 2 3; do
 for ps in 1 0; do
-GNNPN_PRESPLIT=$ps timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision > $O/ab_${ps}_$i.json 2> $O/ab_${ps}_$i.err
+GNNPN_PRESPLIT=$ps timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision > $O/ab_${ps}_$i.json 2> $O/ab_${ps}_$i.err
 python3 -c "
 import json
 d=json.loads([l for l in open('$O/ab_${ps}_$i.json') if l.startswith('{')][-1])

@@ -9,7 +9,7 @@ timeout -k 10 1000 python -m pytest tests/test_gpu_pn.py tests/test_gpu_pipeline
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python tools/time_fixed_part.py > $O/fixed_part.jsonl 2> $O/fixed_part.err; echo "fixed rc=$?"; cat $O/fixed_part.jsonl
 for i in 1 2 3; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision > $O/bench_$i.json 2> $O/bench_$i.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-precision > $O/bench_$i.json 2> $O/bench_$i.err; echo "bench rc=$?"
 python3 -c "
 import json
 d=json.loads([l for l in open('$O/bench_$i.json') if l.startswith('{')][-1])

@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 F="--min-time 0 --warmup 5 --no-cpu-baseline --no-kernel-timers --no-other-precision"
 for st in 20 220; do
-  timeout 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $O/s$st -- python3 $R/bench.py --steps $st $F > $O/s$st.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $O/s$st -- python3 $R/bench.py --full --steps $st $F > $O/s$st.log 2>&1
   echo "steps $st rc=$?"
 done
 python3 - <<PY

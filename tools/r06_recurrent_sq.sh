@@ -14,7 +14,7 @@ for cfg in ${CFGS:-qws:split:3 qws:f32:3 synth4:split:1}; do
   i=0
   for set in "${SETS[@]}"; do
     tag=${wl}_${pr}_$i; i=$((i+1))
-    timeout -k 10 240 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/$tag -- python3 $R/bench.py --workload $wl --precision $pr --steps $st --warmup 1 $SOLO > $O/$tag.log 2>&1 || { echo "pass $tag failed"; tail -3 $O/$tag.log; }
+    timeout -k 10 240 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/$tag -- python3 $R/bench.py --full --workload $wl --precision $pr --steps $st --warmup 1 $SOLO > $O/$tag.log 2>&1 || { echo "pass $tag failed"; tail -3 $O/$tag.log; }
     echo "pass $tag done"
   done
 done
