@@ -53,13 +53,16 @@ def check(dataset, serCategory, epoch):
     return result
 
 
-def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32"):
+def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None):
     """Run ML+2PN inference over ``./data/<dataset>`` on the GPU and write the two artefacts that
     ``check`` reads: the rankings of ALL problems (trainML.py:146-149 format, [P][S] ints) and the
     High-level actions of the test quarter (trainPNHigh.py:133-144 format, [T][nTest][8]).
     ``precision``: arithmetic of the recurrent products and of the large-graph GIN layers — "f32" by default here (the artefact
     files are the reference's hand-off format: the parity path), "split" = what bench.py measures (the exact
-    three-piece products: same selections on every pinned problem)."""
+    three-piece products: same selections on every pinned problem).
+    ``woa``: a dict (popSize, MAX_Iter, reduct, seed) — then the test quarter's actions are also refined on the device
+    (ML2PNPipeline.refine) and ``./solutions/WOA/<dataset>/ML+2PN+WOA.txt`` written as the WOA approach writes it (problem
+    ``idx`` on stream ``seed + idx``; seed None: fresh seeds)."""
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -73,7 +76,7 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     pipe = ML2PNPipeline(net.to(dev).eval(), low.to(dev).eval(), high.to(dev).eval(), n_per, precision=precision)
     table, _ = ld.tables_from_dataset(ds, 0, 0)
     svc = DeviceServices.from_table(table, dev)
-    rankings, actions = [], [[] for _ in range(T)]
+    rankings, actions, test_actions = [], [[] for _ in range(T)], []
     n_train = P // 4 * 3
     from . import ops
     for lo in range(0, P, batch_size):
@@ -88,7 +91,36 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
             if lo + b >= n_train:
                 for t in range(T):
                     actions[t].append(act[b, t].tolist())
-    return write_artifacts(dataset, epoch, rankings, actions)
+        if woa is not None and hi > n_train:
+            test_actions.append(act[max(0, n_train - lo):])
+    paths = write_artifacts(dataset, epoch, rankings, actions)
+    if woa is not None:
+        refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)), **woa)
+    return paths
+
+
+def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None):
+    """ES-WOA refinement of the test quarter's actions [nTest, T, 8] on the device, written as the WOA approach's
+    ``ML+2PN+WOA.txt`` (WOA.py:286-296): quality = minCost / best fitness, problem ``idx`` on stream ``seed + idx``."""
+    import time
+    import torch
+    from . import loadData as ld
+    from .WOA import write_ml2pn_woa
+    from .pipeline import DeviceBatch
+    dev = svc.qos.device
+    P = len(ds["nodefeatures"])
+    first = P // 4 * 3
+    n = actions.shape[0]
+    _, pb = ld.tables_from_dataset(ds, first, first + n)
+    batch = DeviceBatch.from_problems(pb, dev)
+    seeds = None if seed is None else [(seed + first + i) & 0xFFFFFFFFFFFFFFFF for i in range(n)]
+    torch.cuda.synchronize(dev)
+    t0 = time.time()
+    res = pipe.refine(svc, batch, {"actions": torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float64)).to(dev)},
+                      popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=ds["minCostList"][first:first + n])
+    quality = res["quality"].cpu().tolist()
+    per_problem = (time.time() - t0) / max(n, 1)
+    return write_ml2pn_woa(dataset, quality, per_problem, first)
 
 
 def artifact_paths(dataset, epoch):

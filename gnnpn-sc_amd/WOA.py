@@ -157,17 +157,27 @@ class WOA:
         t0 = time.time()
         results = fine_tune(problems, self.popSize, self.MAX_Iter, seeds, self.device)
         per_problem = (time.time() - t0) / max(n, 1)
-        out = {"quality": [], "time": [], "averageQ": 0, "averageT": 0}
         self.bestFitnesses = [[r["bestFitnesses"][i] for r in results] for i in range(self.MAX_Iter)]   # :264, 283-284
-        for i, r in enumerate(results):                                                        # :286-292
-            out["quality"].append(minCostList[first + i] / r["bestFitness"])
-            out["time"].append(per_problem)
-            out["averageQ"] = sum(out["quality"]) / (self.times + 1)
-            out["averageT"] = sum(out["time"]) / (self.times + 1)
-            print(first + i, out["averageQ"], out["averageT"])
-            self.times += 1
-        os.makedirs(f"./solutions/WOA/{self.dataset}", exist_ok=True)
-        with open(f"./solutions/WOA/{self.dataset}/ML+2PN+WOA.txt", "w") as f:                 # :294-296
-            json.dump(out, f)
+        out = write_ml2pn_woa(ds, [minCostList[first + i] / r["bestFitness"] for i, r in enumerate(results)], per_problem, first,
+                              self.times)
+        self.times += len(results)
         self.results = results
         return out
+
+
+def write_ml2pn_woa(dataset, quality, per_problem, first, times=0):
+    """The progress lines and ``./solutions/WOA/<dataset>/ML+2PN+WOA.txt`` of the ML2PNWOATest mode (WOA.py:286-296) for the
+    qualities of test problems ``first``, ``first + 1`` ...; ``per_problem``: the time booked to each."""
+    import json
+    out = {"quality": [], "time": [], "averageQ": 0, "averageT": 0}
+    for i, q in enumerate(quality):                                                            # :286-292
+        out["quality"].append(q)
+        out["time"].append(per_problem)
+        out["averageQ"] = sum(out["quality"]) / (times + 1)
+        out["averageT"] = sum(out["time"]) / (times + 1)
+        print(first + i, out["averageQ"], out["averageT"])
+        times += 1
+    os.makedirs(f"./solutions/WOA/{dataset}/", exist_ok=True)
+    with open(f"./solutions/WOA/{dataset}//ML+2PN+WOA.txt", "w") as f:                        # :294-296
+        json.dump(out, f)
+    return out

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("GNNPN_LIB") or os.path.join(_HERE, "libgnnpn_hip.so")
 ABI_VERSION = 9
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
+E_UNSUP = -2
+WOA_OK, WOA_ROWS_MISMATCH, WOA_INDEX_ERROR, WOA_NO_SLOTS = 0, 1, 2, 3     # per-problem status words of gnnpn_woa_candidates_count
 
 _P = c_void_p
 _SIGNATURES = {
@@ -86,6 +88,15 @@ _SIGNATURES = {
     "gnnpn_eswoa_f64": (c_int, [c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, _P]),
     "gnnpn_eswoa_wide_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "gnnpn_eswoa_wide_f64": (c_int, [c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gnnpn_eswoa_ragged_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "gnnpn_eswoa_ragged_f64": (c_int, [c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, _P, c_int32, _P,
+                                       c_int64, _P, _P, _P, _P, _P, _P]),
+    "gnnpn_woa_candidates_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "gnnpn_woa_candidates_count": (c_int, [c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_double,
+                                           _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "gnnpn_woa_candidates_fill": (c_int, [c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, _P, c_int32, c_int32, _P, _P, _P, _P,
+                                          _P]),
+    "gnnpn_debug_round5_f64": (c_int, [_P, _P, c_int64, _P]),
     "gnnpn_debug_cell_activations": (c_int, [_P, _P, _P, c_int64, _P]),
     "gnnpn_debug_lds_interferer": (c_int, [c_int32, c_int32, c_int32, _P]),
     "gnnpn_gate_wait": (c_int, [_P, c_uint32, c_int32, _P]),

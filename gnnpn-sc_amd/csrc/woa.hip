@@ -94,7 +94,38 @@ __device__ __forceinline__ void gather_row(const double* cand, int base, int len
 }
 }  // namespace
 
-__global__ __launch_bounds__(64) void eswoa_kernel(int32_t T, const int32_t* __restrict__ cand_ptr,
+// Where a problem's categories come from.  FixedT: one T for the whole launch, problem p owns entries p*T .. p*T+T-1 of
+// cand_ptr / len_init / start_pos (gnnpn_eswoa_f64, gnnpn_eswoa_wide_f64).  RaggedT: prob_ptr [B+1], problem p owns entries
+// prob_ptr[p] .. prob_ptr[p+1]-1 and its outputs are rows of `stride` (gnnpn_eswoa_ragged_f64); it also checks that a problem
+// fits what the launch was sized for, and may write the best composition's rows.
+struct FixedT {
+    int32_t T;
+    __device__ __forceinline__ int count(int) const { return T; }
+    __device__ __forceinline__ size_t first(int p) const { return (size_t)p * T; }
+    __device__ __forceinline__ size_t out_row(int p) const { return (size_t)p * T; }
+    __device__ __forceinline__ bool fits(int) const { return true; }
+    __device__ __forceinline__ bool fits_cand(int) const { return true; }
+    __device__ __forceinline__ double* rows_out(int) const { return nullptr; }
+};
+struct RaggedT {
+    const int32_t* prob_ptr;
+    int32_t stride;      // max_slots: row length of best_pos / best_rows, and the largest T the launch is sized for
+    int32_t max_T;       // 64 for the lane-per-category form, stride for the workgroup form
+    int32_t max_cand;    // lane-per-category form: candidates of the largest problem (LDS); workgroup form: unused
+    int32_t n_lists;     // entries of len_init / start_pos (cand_ptr has one more)
+    double* best_rows;   // [B, stride, 4] or NULL
+    __device__ __forceinline__ int count(int p) const { return prob_ptr[p + 1] - prob_ptr[p]; }
+    __device__ __forceinline__ size_t first(int p) const { return (size_t)prob_ptr[p]; }
+    __device__ __forceinline__ size_t out_row(int p) const { return (size_t)p * stride; }
+    __device__ __forceinline__ bool fits(int T) const {
+        return T >= 1 && T <= max_T && T <= stride && prob_ptr[blockIdx.x] >= 0 && prob_ptr[blockIdx.x + 1] <= n_lists;
+    }
+    __device__ __forceinline__ bool fits_cand(int n_cand) const { return max_cand <= 0 || n_cand <= max_cand; }
+    __device__ __forceinline__ double* rows_out(int p) const { return best_rows ? best_rows + (size_t)p * stride * 4 : nullptr; }
+};
+
+template <class Shape>
+__global__ __launch_bounds__(64) void eswoa_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                    const int32_t* __restrict__ len_init, const double* __restrict__ cand_g,
                                                    const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
                                                    int32_t pop, int32_t max_iter, const unsigned long long* __restrict__ seeds,
@@ -102,7 +133,17 @@ __global__ __launch_bounds__(64) void eswoa_kernel(int32_t T, const int32_t* __r
                                                    double* __restrict__ history, long long* __restrict__ draws_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int p = blockIdx.x, lane = threadIdx.x;
-    const int c0 = cand_ptr[(size_t)p * T], n_cand = cand_ptr[(size_t)p * T + T] - c0;
+    const int T = sh.count(p);
+    const size_t s0 = sh.first(p);
+    const bool fits = sh.fits(T);
+    const int c0 = fits ? cand_ptr[s0] : 0, n_cand = fits ? cand_ptr[s0 + T] - c0 : 0;
+    if (!fits || !sh.fits_cand(n_cand)) {                             // not what the launch was sized for: no search
+        if (lane == 0) {
+            best_fitness[p] = NAN;
+            draws_out[p] = -1;
+        }
+        return;
+    }
     double* col = reinterpret_cast<double*>(lds_raw);                 // [4][64]
     double* bounds = col + 256;                                       // [4]
     double* cand = bounds + 4;                                        // [n_cand][4]
@@ -110,9 +151,9 @@ __global__ __launch_bounds__(64) void eswoa_kernel(int32_t T, const int32_t* __r
     for (int i = lane; i < n_cand * 4; i += 64) cand[i] = cand_g[(size_t)c0 * 4 + i];
     if (lane < 4) bounds[lane] = bounds_g[(size_t)p * 4 + lane];
     const bool live = lane < T;
-    const int base = live ? cand_ptr[(size_t)p * T + lane] - c0 : 0;
-    const int len = live ? cand_ptr[(size_t)p * T + lane + 1] - cand_ptr[(size_t)p * T + lane] : 1;
-    const int len0 = live ? len_init[(size_t)p * T + lane] : 1;
+    const int base = live ? cand_ptr[s0 + lane] - c0 : 0;
+    const int len = live ? cand_ptr[s0 + lane + 1] - cand_ptr[s0 + lane] : 1;
+    const int len0 = live ? len_init[s0 + lane] : 1;
     const unsigned long long seed = seeds[p];
     unsigned long long k = 0;                                         // draws consumed so far (wave-uniform)
     __syncthreads();
@@ -127,8 +168,8 @@ __global__ __launch_bounds__(64) void eswoa_kernel(int32_t T, const int32_t* __r
     double best_fit = 3.0;                                            // :71
     int best = 0;                                                     // this lane's category of the recorded best
     int alias = -1;                                                   // individual whose list the record shares
-    if (start_pos[(size_t)p * T] >= 0) {                              // :55-69
-        best = live ? start_pos[(size_t)p * T + lane] : 0;
+    if (start_pos[s0] >= 0) {                                         // :55-69
+        best = live ? start_pos[s0 + lane] : 0;
         if (live) gather_row(cand, base, len, best, q);
         best_fit = figure_of_merit(q, T, lane, col, bounds);
     }
@@ -208,7 +249,14 @@ __global__ __launch_bounds__(64) void eswoa_kernel(int32_t T, const int32_t* __r
         }
         if (lane == 0) history[(size_t)p * max_iter + t] = best_fit;
     }
-    if (live) best_pos_out[(size_t)p * T + lane] = best;
+    if (live) best_pos_out[sh.out_row(p) + lane] = best;
+    if (double* rows = sh.rows_out(p)) {                              // the recorded best's rows (Python indexing)
+        if (live) {
+            gather_row(cand, base, len, best, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) rows[(size_t)lane * 4 + c] = q[c];
+        }
+    }
     if (lane == 0) {
         best_fitness[p] = best_fit;
         draws_out[p] = (long long)k;
@@ -345,7 +393,8 @@ __device__ double wide_merit(const WideLds& L, const int* pos, const double* can
 }
 }  // namespace
 
-__global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_t* __restrict__ cand_ptr,
+template <class Shape>
+__global__ __launch_bounds__(WNT) void eswoa_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                          const int32_t* __restrict__ len_init, const double* __restrict__ cand_g,
                                                          const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
                                                          int32_t pop, int32_t max_iter, const unsigned long long* __restrict__ seeds,
@@ -354,6 +403,15 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_
                                                          long long* __restrict__ draws_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int p = blockIdx.x, tid = threadIdx.x;
+    const int T = sh.count(p);
+    const size_t s0 = sh.first(p);
+    if (!sh.fits(T)) {                                             // not what the launch was sized for: no search
+        if (tid == 0) {
+            best_fitness[p] = NAN;
+            draws_out[p] = -1;
+        }
+        return;
+    }
     WideLds L;
     L.col0 = reinterpret_cast<double*>(lds_raw);
     L.col2 = L.col0 + T;
@@ -363,13 +421,13 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_
     L.cnt = reinterpret_cast<int*>(L.bounds + 4);
     L.base = L.cnt + 4;
     L.len = L.base + T;
-    const int c0 = cand_ptr[(size_t)p * T];
+    const int c0 = cand_ptr[s0];
     const double* cand = cand_g + (size_t)c0 * 4;
-    int* pos = pos_ws + (size_t)p * pop * T;              // [pop][T]
-    int* best = best_pos_out + (size_t)p * T;             // the recorded best composition (a COPY: see `alias`)
+    int* pos = pos_ws + (size_t)pop * s0;                 // [pop][T]
+    int* best = best_pos_out + sh.out_row(p);             // the recorded best composition (a COPY: see `alias`)
     for (int j = tid; j < T; j += WNT) {
-        L.base[j] = cand_ptr[(size_t)p * T + j] - c0;
-        L.len[j] = cand_ptr[(size_t)p * T + j + 1] - cand_ptr[(size_t)p * T + j];
+        L.base[j] = cand_ptr[s0 + j] - c0;
+        L.len[j] = cand_ptr[s0 + j + 1] - cand_ptr[s0 + j];
     }
     if (tid < 4) L.bounds[tid] = bounds_g[(size_t)p * 4 + tid];
     const unsigned long long seed = seeds[p];
@@ -378,7 +436,7 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_
     // initial population (WOA.py:51-52): individual i, category j <- draw k + i*T + j + 1, lengths BEFORE the append
     for (int i = 0; i < pop; ++i)
         for (int j = tid; j < T; j += WNT)
-            pos[(size_t)i * T + j] = draw_below(seed, k + (unsigned long long)i * T + j + 1, len_init[(size_t)p * T + j]);
+            pos[(size_t)i * T + j] = draw_below(seed, k + (unsigned long long)i * T + j + 1, len_init[s0 + j]);
     k += (unsigned long long)pop * T;
     __syncthreads();
 
@@ -388,8 +446,8 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_
         for (int j = tid; j < T; j += WNT) best[j] = pos[(size_t)i * T + j];
         alias = i;
     };
-    if (start_pos[(size_t)p * T] >= 0) {                              // :55-69
-        for (int j = tid; j < T; j += WNT) best[j] = start_pos[(size_t)p * T + j];
+    if (start_pos[s0] >= 0) {                                         // :55-69
+        for (int j = tid; j < T; j += WNT) best[j] = start_pos[s0 + j];
         __syncthreads();
         best_fit = wide_merit(L, best, cand, T, tid);
     } else {
@@ -460,6 +518,14 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(int32_t T, const int32_
         }
         if (tid == 0) history[(size_t)p * max_iter + t] = best_fit;
     }
+    if (double* rows = sh.rows_out(p)) {                              // the recorded best's rows (Python indexing)
+        __syncthreads();
+        for (int j = tid; j < T; j += WNT) {
+            const int x = best[j], ln = L.len[j];
+            const double* q = cand + (size_t)(L.base[j] + (x < 0 ? x + ln : x)) * 4;
+            for (int c = 0; c < 4; ++c) rows[(size_t)j * 4 + c] = q[c];
+        }
+    }
     if (tid == 0) {
         best_fitness[p] = best_fit;
         draws_out[p] = (long long)k;
@@ -484,9 +550,9 @@ extern "C" int gnnpn_eswoa_wide_f64(int32_t P, int32_t T, const int32_t* cand_pt
     const size_t lds = eswoa_wide_lds_bytes(T);
     if (lds > 160 * 1024 - 1024)
         GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_wide: T=%d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", T, lds);
-    if (hipFuncSetAttribute((const void*)eswoa_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)eswoa_wide_kernel<FixedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_wide: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(eswoa_wide_kernel, dim3(P), dim3(WNT), lds, (hipStream_t)stream, T, cand_ptr, len_init, cand, bounds,
+    hipLaunchKernelGGL(eswoa_wide_kernel<FixedT>, dim3(P), dim3(WNT), lds, (hipStream_t)stream, FixedT{T}, cand_ptr, len_init, cand, bounds,
                        start_pos, pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds),
                        reinterpret_cast<int32_t*>(workspace), best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
     GNNPN_CHECK_LAUNCH("eswoa_wide_f64");
@@ -510,11 +576,56 @@ extern "C" int gnnpn_eswoa_f64(int32_t P, int32_t T, const int32_t* cand_ptr, co
     const size_t lds = eswoa_lds_bytes(max_cand, pop, T);
     if (lds > 160 * 1024 - 1024)
         GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", lds, pop, T, max_cand);
-    if (hipFuncSetAttribute((const void*)eswoa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)eswoa_kernel<FixedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(eswoa_kernel, dim3(P), dim3(64), lds, (hipStream_t)stream, T, cand_ptr, len_init, cand, bounds, start_pos,
+    hipLaunchKernelGGL(eswoa_kernel<FixedT>, dim3(P), dim3(64), lds, (hipStream_t)stream, FixedT{T}, cand_ptr, len_init, cand, bounds, start_pos,
                        pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds), best_fitness, best_pos, history,
                        reinterpret_cast<long long*>(draws));
     GNNPN_CHECK_LAUNCH("eswoa_f64");
+    return GNNPN_OK;
+}
+
+// ---- a ragged batch: problem p has prob_ptr[p+1] - prob_ptr[p] categories, all problems in ONE launch ----------------------
+extern "C" int64_t gnnpn_eswoa_ragged_workspace_bytes(int32_t n_lists, int32_t max_slots, int32_t pop, int32_t wide) {
+    if (!(wide || max_slots > 64)) return 0;
+    return gnnpn_eswoa_wide_workspace_bytes(1, n_lists, pop);
+}
+
+extern "C" int gnnpn_eswoa_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                      const int32_t* cand_ptr, const int32_t* len_init, const double* cand, const double* bounds,
+                                      const int32_t* start_pos, int32_t pop, int32_t max_iter, const uint64_t* seeds, int32_t wide,
+                                      void* workspace, int64_t workspace_bytes, double* best_fitness, int32_t* best_pos,
+                                      double* best_rows, double* history, int64_t* draws, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && pop > 0 && max_iter >= 0 && max_slots >= 1, "eswoa_ragged: bad argument");
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(prob_ptr && cand_ptr && len_init && cand && bounds && start_pos && seeds && best_fitness && best_pos && history &&
+                  draws, "eswoa_ragged: null operand");
+    const bool use_wide = wide || max_slots > 64;
+    if (use_wide) {
+        GNNPN_REQUIRE(workspace && workspace_bytes >= gnnpn_eswoa_ragged_workspace_bytes(n_lists, max_slots, pop, wide),
+                      "eswoa_ragged: the workgroup form needs a workspace of gnnpn_eswoa_ragged_workspace_bytes");
+        const size_t lds = eswoa_wide_lds_bytes(max_slots);
+        if (lds > 160 * 1024 - 1024)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_ragged: %d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", max_slots, lds);
+        if (hipFuncSetAttribute((const void*)eswoa_wide_kernel<RaggedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_ragged: cannot reserve %zu B of LDS", lds);
+        hipLaunchKernelGGL(eswoa_wide_kernel<RaggedT>, dim3(B), dim3(WNT), lds, (hipStream_t)stream,
+                           RaggedT{prob_ptr, max_slots, max_slots, 0, n_lists, best_rows}, cand_ptr, len_init, cand, bounds, start_pos, pop,
+                           max_iter, reinterpret_cast<const unsigned long long*>(seeds), reinterpret_cast<int32_t*>(workspace),
+                           best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
+        GNNPN_CHECK_LAUNCH("eswoa_ragged_f64 (workgroup form)");
+        return GNNPN_OK;
+    }
+    GNNPN_REQUIRE(max_cand >= 1, "eswoa_ragged: max_cand must be >= 1 for the lane-per-category form");
+    const size_t lds = eswoa_lds_bytes(max_cand, pop, max_slots);
+    if (lds > 160 * 1024 - 1024)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_ragged: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", lds, pop,
+                   max_slots, max_cand);
+    if (hipFuncSetAttribute((const void*)eswoa_kernel<RaggedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_ragged: cannot reserve %zu B of LDS", lds);
+    hipLaunchKernelGGL(eswoa_kernel<RaggedT>, dim3(B), dim3(64), lds, (hipStream_t)stream, RaggedT{prob_ptr, max_slots, 64, max_cand, n_lists, best_rows},
+                       cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds),
+                       best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
+    GNNPN_CHECK_LAUNCH("eswoa_ragged_f64");
     return GNNPN_OK;
 }

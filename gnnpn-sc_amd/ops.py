@@ -952,6 +952,125 @@ def eswoa(cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, n_c
     return best_fit, best_pos, history[:, :int(max_iter)], draws
 
 
+
+def debug_round5(x):
+    """round(v, 5) of every float64 of ``x`` as the candidate builder computes it (gnnpn_debug_round5_f64; test hook)."""
+    y = torch.empty_like(x)
+    check(_lib.load().gnnpn_debug_round5_f64(dev_ptr(x, F64, "x"), dev_ptr(y, F64, "y"), x.numel(), stream_ptr()),
+          "gnnpn_debug_round5_f64")
+    return y
+
+
+_WOA_STATUS = {_lib.WOA_ROWS_MISMATCH: "as many seed rows as non-empty candidate lists expected (WOA._prepare raises)",
+               _lib.WOA_INDEX_ERROR: "addS replaces past the end of a kept list (the reference raises IndexError)",
+               _lib.WOA_NO_SLOTS: "no candidate list and no seed row: nothing to search",
+               _lib.E_UNSUP: "a task category outside 0..49 or outside the table (GNNPN_E_UNSUP: addS raises IndexError)"}
+
+
+def woa_status_error(status, first):
+    """The error a problem's status word of gnnpn_woa_candidates_count stands for."""
+    return GnnpnError(f"woa_candidates: problem {first}: status {status}: {_WOA_STATUS.get(status, 'unknown status')}")
+
+
+def woa_candidates(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct=0, patches=(), check_status=True):
+    """The ES-WOA operands of a batch, built on the device (gnnpn_woa_candidates_count / _fill; loadDataOther + WOA._prepare).
+    cat_ptr [T+1] i32, qos [S,4] f64 (DeviceServices); x [N,7] f32, seg_ptr [B+1] i32, local_bounds [B,T,4] f64, global_bounds
+    [B,4] f64 (DeviceBatch); actions [B,T',8] f32 or f64 (ML2PNPipeline.run's, or an artefact's rows); patches: WOA._prepare's
+    (want 4-tuple, column, value) triples.  Two small copies to the host: the largest category (sizes the workspace) and the
+    totals.  A problem the host path raises on raises GnnpnError naming it (``check_status=False``: returned in ``status``).
+    Returns a dict: prob_ptr [B+1], n_slots [B], cand_ptr [n+1], len_init [n], cand [m,4] f64, start_pos [n], bounds [B,4],
+    status [B] (device tensors) and max_slots, max_cand (ints)."""
+    lib = _lib.load()
+    dev = x.device
+    B = seg_ptr.numel() - 1
+    if actions.dim() != 3 or actions.shape[0] != B or actions.shape[2] != 8:
+        raise GnnpnError(f"woa_candidates: actions [B={B}, T, 8] expected, got {tuple(actions.shape)}")
+    if actions.dtype not in (F32, F64):
+        raise GnnpnError(f"woa_candidates: actions must be float32 or float64, got {actions.dtype}")
+    if x.dim() != 2 or local_bounds.dim() != 3 or local_bounds.shape[0] != B or local_bounds.shape[1] != cat_ptr.numel() - 1:
+        raise GnnpnError("woa_candidates: inconsistent shapes (x [N,7], local_bounds [B, T, 4] with T = len(cat_ptr) - 1)")
+    for name, t in (("cat_ptr", cat_ptr), ("qos", qos), ("x", x), ("seg_ptr", seg_ptr), ("local_bounds", local_bounds),
+                    ("global_bounds", global_bounds), ("actions", actions)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GnnpnError(f"woa_candidates: {name}: expected a CUDA tensor (the hot path has no CPU implementation)")
+    patches = list(patches)
+    for want, col, _val in patches:
+        if len(want) != 4 or not 0 <= int(col) < 4:
+            raise GnnpnError("woa_candidates: a patch is (4 values, column 0..3, value)")
+    pt = torch.tensor([list(map(float, w)) + [float(c), float(v)] for w, c, v in patches] or [[0.0] * 6], dtype=F64).to(dev)
+    N, n_cat, aT = x.shape[0], cat_ptr.numel() - 1, actions.shape[1]
+    max_cat = int((cat_ptr[1:] - cat_ptr[:-1]).max().item()) if n_cat else 0
+    nbytes = int(lib.gnnpn_woa_candidates_workspace_bytes(B, N, max_cat))
+    ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.int64, device=dev)
+    prob_ptr = torch.empty(B + 1, dtype=I32, device=dev)
+    n_slots = torch.empty(B, dtype=I32, device=dev)
+    bounds = torch.empty(B, 4, dtype=F64, device=dev)
+    status = torch.empty(B, dtype=I32, device=dev)
+    totals = torch.empty(6, dtype=I32, device=dev)
+    check(lib.gnnpn_woa_candidates_count(B, N, dev_ptr(x, F32, "x"), x.shape[1], dev_ptr(seg_ptr, I32, "seg_ptr"),
+                                         dev_ptr(local_bounds, F64, "local_bounds"), dev_ptr(global_bounds, F64, "global_bounds"),
+                                         n_cat, dev_ptr(cat_ptr, I32, "cat_ptr"), dev_ptr(qos, F64, "qos"),
+                                         dev_ptr(actions, actions.dtype, "actions"), int(actions.dtype == F64), aT, float(reduct),
+                                         dev_ptr(pt, F64, "patches"), len(patches), max_cat, dev_ptr(ws, torch.int64, "workspace"),
+                                         ws.numel() * 8, dev_ptr(prob_ptr, I32, "prob_ptr"), dev_ptr(n_slots, I32, "n_slots"),
+                                         dev_ptr(bounds, F64, "bounds"), dev_ptr(status, I32, "status"),
+                                         dev_ptr(totals, I32, "totals"), stream_ptr()), "gnnpn_woa_candidates_count")
+    n_lists, n_cand, max_slots, max_cand, n_bad, first_bad = totals.tolist()        # the one copy of the totals
+    if n_bad and check_status:
+        raise woa_status_error(int(status[first_bad].item()), first_bad)
+    cand_ptr = torch.empty(n_lists + 1, dtype=I32, device=dev)
+    len_init = torch.empty(n_lists, dtype=I32, device=dev)
+    start_pos = torch.empty(n_lists, dtype=I32, device=dev)
+    cand = torch.empty(n_cand, 4, dtype=F64, device=dev)
+    if B == 0:
+        cand_ptr.zero_()
+    check(lib.gnnpn_woa_candidates_fill(B, N, dev_ptr(seg_ptr, I32, "seg_ptr"), dev_ptr(cat_ptr, I32, "cat_ptr"),
+                                        dev_ptr(qos, F64, "qos"), max_cat, dev_ptr(ws, torch.int64, "workspace"), ws.numel() * 8,
+                                        dev_ptr(status, I32, "status"), dev_ptr(prob_ptr, I32, "prob_ptr"), n_lists, n_cand,
+                                        dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
+                                        dev_ptr(cand, F64, "cand"), dev_ptr(start_pos, I32, "start_pos"), stream_ptr()),
+          "gnnpn_woa_candidates_fill")
+    return {"prob_ptr": prob_ptr, "n_slots": n_slots, "cand_ptr": cand_ptr, "len_init": len_init, "cand": cand,
+            "start_pos": start_pos, "bounds": bounds, "status": status, "max_slots": max_slots, "max_cand": max_cand}
+
+
+def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, max_slots=None, max_cand=None,
+                 wide=None):
+    """ES-WOA over a batch whose problems differ in their number of categories, in ONE launch (gnnpn_eswoa_ragged_f64).
+    prob_ptr [B+1] i32 (problem p owns lists prob_ptr[p] .. prob_ptr[p+1]-1), cand_ptr [n+1], len_init [n], cand [m,4] f64,
+    bounds [B,4] f64, start_pos [n] (a problem's first entry < 0: no seed), seeds [B] int64; max_slots / max_cand: the
+    largest list count / candidate count of a problem (None: read back from the device).  ``wide``: the workgroup form for
+    every problem (it is taken anyway when a problem has more than 64 categories).  Returns (best_fitness [B] f64,
+    best_pos [B, max_slots] i32 (0 past a problem's count), history [B, max_iter] f64, draws [B] i64,
+    best_rows [B, max_slots, 4] f64 (0 past a problem's count))."""
+    dev = cand.device
+    B = prob_ptr.numel() - 1
+    n = cand_ptr.numel() - 1
+    I64 = torch.int64
+    if n != len_init.numel() or n != start_pos.numel() or bounds.shape != (B, 4) or seeds.numel() != B:
+        raise GnnpnError("eswoa_ragged: inconsistent operand sizes")
+    if max_slots is None:
+        max_slots = int((prob_ptr[1:] - prob_ptr[:-1]).max().item()) if B else 1
+    if max_cand is None:
+        max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
+    max_slots, max_cand = max(int(max_slots), 1), max(int(max_cand), 1)
+    best_fit = torch.empty(B, dtype=F64, device=dev)
+    best_pos = torch.zeros(B, max_slots, dtype=I32, device=dev)
+    best_rows = torch.zeros(B, max_slots, 4, dtype=F64, device=dev)
+    history = torch.empty(B, max(int(max_iter), 1), dtype=F64, device=dev)
+    draws = torch.empty(B, dtype=I64, device=dev)
+    lib = _lib.load()
+    nbytes = int(lib.gnnpn_eswoa_ragged_workspace_bytes(n, max_slots, int(pop), int(bool(wide))))
+    ws = torch.empty(max(nbytes // 4, 1), dtype=I32, device=dev)
+    check(lib.gnnpn_eswoa_ragged_f64(B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"),
+                                     dev_ptr(len_init, I32, "len_init"), dev_ptr(cand, F64, "cand"), dev_ptr(bounds, F64, "bounds"),
+                                     dev_ptr(start_pos, I32, "start_pos"), int(pop), int(max_iter), dev_ptr(seeds, I64, "seeds"),
+                                     int(bool(wide)), dev_ptr(ws, I32, "workspace"), nbytes, dev_ptr(best_fit, F64, "best_fitness"),
+                                     dev_ptr(best_pos, I32, "best_pos"), dev_ptr(best_rows, F64, "best_rows"),
+                                     dev_ptr(history, F64, "history"), dev_ptr(draws, I64, "draws"), stream_ptr()),
+          "gnnpn_eswoa_ragged_f64")
+    return best_fit, best_pos, history[:, :int(max_iter)], draws, best_rows
+
 # ---- REINFORCE training step of the High-level pointer network (csrc/train.hip; include/gnnpn_hip.h) -----------------
 
 def gemm(a, b, a_kmajor=False, b_kmajor=False):

@@ -131,6 +131,36 @@ def warn_partitioned_device(device, precision):
                       RuntimeWarning, stacklevel=3)
 
 
+@torch.no_grad()
+def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=()):
+    """The third stage: ES-WOA refinement of ``out["actions"]`` (what ``run`` returned, or any mapping with an actions
+    tensor [B,T,8], float32 or float64) on the device — the candidate lists of every problem built from ``services`` /
+    ``batch`` (gnnpn_woa_candidates_count / _fill: loadDataOther + WOA._prepare, bit for bit) and the search of every problem
+    in one launch (gnnpn_eswoa_ragged_f64: WOA.fine_tune).  ``seeds``: [B] stream seeds (None: fresh OS entropy, as
+    fine_tune); ``min_cost`` [B]: adds quality = min_cost / best_fitness (WOA.py:286-287); ``patches``: WOA._prepare's.
+    A problem the host path raises on raises GnnpnError naming it.  ``ML2PNPipeline.refine`` is this, as a method.
+    Returns device tensors: best_fitness [B] f64, best_rows [B, max_slots, 4] f64, n_slots [B] i32, best_pos
+    [B, max_slots] i32 (negative: Python list positions), history [B, MAX_Iter] f64, draws [B] i64 (and quality [B] f64)."""
+    actions = out["actions"]
+    dev = actions.device
+    B = batch.n_problems
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    if seeds is None:
+        seeds = np.frombuffer(os.urandom(8 * B), dtype=np.int64).copy()
+    if not isinstance(seeds, torch.Tensor):
+        seeds = torch.from_numpy(np.asarray(seeds, dtype=np.uint64).reshape(B).view(np.int64).copy())
+    seeds = seeds.to(device=dev, dtype=torch.int64).contiguous()
+    fit, pos, hist, draws, rows = ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"],
+                                                   tabs["bounds"], tabs["start_pos"], popSize, MAX_Iter, seeds,
+                                                   max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+    res = {"best_fitness": fit, "best_rows": rows, "n_slots": tabs["n_slots"], "best_pos": pos, "history": hist, "draws": draws}
+    if min_cost is not None:
+        mc = min_cost if isinstance(min_cost, torch.Tensor) else torch.as_tensor(np.asarray(min_cost, dtype=np.float64))
+        res["quality"] = mc.to(device=dev, dtype=torch.float64) / fit
+    return res
+
+
 class ML2PNPipeline:
     """net: modelML.Net; low/high: modelPN.CombinatorialRL (levels "Low"/"High")."""
 
@@ -214,6 +244,11 @@ class ML2PNPipeline:
                                    lds_kb=lds_kb, ws=ws, paired_start=paired_start, write_through=write_through)
         out.update(scores=scores, pn_inputs=rows, candidate_ids=ids)
         return out
+
+    def refine(self, services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=()):
+        """The third stage, ES-WOA refinement of ``out["actions"]`` on the device: module-level ``refine`` (it needs no
+        network).  An extra call: ``run`` / ``capture`` are unchanged."""
+        return refine(services, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, patches=patches)
 
     def capture(self, services, batch, warmup=2, decode_impl=0, lds_kb=0, ws=None, paired_start=False, pool=None, write_through=False):
         """Record one whole pass over (services, batch) into a HIP graph and return a callable that

@@ -699,6 +699,64 @@ int gnnpn_eswoa_wide_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const in
                          void* workspace, int64_t workspace_bytes, double* best_fitness, int32_t* best_pos, double* history,
                          int64_t* draws, void* stream);
 
+/* The ES-WOA search over a RAGGED batch in one launch: problem p has prob_ptr[p+1] - prob_ptr[p] categories (lists), its
+ * entries of cand_ptr / len_init / start_pos are prob_ptr[p] .. prob_ptr[p+1]-1 (cand_ptr has n_lists + 1 entries), the rest
+ * as gnnpn_eswoa_f64.  Replaces the per-problem loop of src/baselines/WOA.py:271-288 (one ESWOA per test problem) where
+ * problems differ in their number of categories; a problem's run is the one gnnpn_eswoa_f64 / _wide_f64 give it alone.
+ *   max_slots : the largest category count (rows of best_pos / best_rows); max_slots <= 64 and wide == 0: the
+ *               lane-per-category form (max_cand sizes its LDS as in gnnpn_eswoa_f64), else the workgroup form for the whole
+ *               launch (workspace of gnnpn_eswoa_ragged_workspace_bytes = pop * n_lists int32, 0 for the lane form)
+ * Outputs: best_fitness [B], best_pos [B, max_slots] (entries past a problem's count are not written), best_rows
+ * [B, max_slots, 4] or NULL (the recorded best's candidate rows, Python indexing), history [B, max_iter], draws [B].  A
+ * problem with no category, more than the launch was sized for, or entries past n_lists is not searched: best_fitness NaN,
+ * draws -1. */
+int64_t gnnpn_eswoa_ragged_workspace_bytes(int32_t n_lists, int32_t max_slots, int32_t pop, int32_t wide);
+int gnnpn_eswoa_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                           const int32_t* cand_ptr, const int32_t* len_init, const double* cand, const double* bounds,
+                           const int32_t* start_pos, int32_t pop, int32_t max_iter, const uint64_t* seeds, int32_t wide,
+                           void* workspace, int64_t workspace_bytes, double* best_fitness, int32_t* best_pos, double* best_rows,
+                           double* history, int64_t* draws, void* stream);
+
+/* ES-WOA inputs of an ML+2PN batch built on the device (csrc/woa_prep.hip).  Replaces what src/baselines/WOA.py:194-208 and
+ * :13-26, 55-69 (`WOA.start` + `ESWOA.__init__`: action rows, the pick set, rounding, the appended pick) and
+ * src/loadData.py:155-276 (`addS`, `loadDataOther`: the per-task candidate lists) do on the host, with the same results
+ * bit for bit — of the reference's host path, quirks included:
+ *   - slots: the task nodes of a problem, node order (its segment's nodes after the first), category x[n*x_ld] - 1;
+ *   - each slot keeps its category's services (table order) inside the local bounds [B, n_cat, 4] or, reduct != 0, the
+ *     front of `addS` (sentinel (1,0,1,1), replace-or-append, members equal to a pick skipped); empty lists are dropped;
+ *   - rows: actions [B, actions_T, 8] (float32 if actions_f64 == 0, else float64; widened to float64) in category order,
+ *     those whose left-to-right float64 sum of the first four values is 3.0 (dummy rows) dropped; the pick set is the rows
+ *     rounded to 5 decimals (Python's round(v, 5), bit for bit: gnnpn_debug_round5_f64); row l pairs with the l-th kept
+ *     list; with rows, candidates and rows are rounded, `patches` [n_patches][6] (4 values, column, new value; WOA.py:27-41
+ *     as data) applied to the rows, a row absent from its list appended, start = its first position; without rows the
+ *     lists stay unrounded and start = -1;
+ *   - bounds [B,4] = global_bounds (loadData.py:268-273).
+ * gnnpn_woa_candidates_count: launches the scan of every slot and the scans over the problems; writes prob_ptr [B+1],
+ *   n_slots [B], bounds [B,4], status [B] (GNNPN_WOA_* below, or GNNPN_E_UNSUP for a task category outside 0..49 or
+ *   outside the table: addS raises IndexError there) and totals [6] = {lists, candidates, largest list count of a problem,
+ *   largest candidate count of a problem, problems with a non-zero status, the first of them or -1}.  A problem with a
+ *   non-zero status takes no room in the tables.  workspace: gnnpn_woa_candidates_workspace_bytes(B, n_nodes, largest
+ *   category of the table), kept until the fill.
+ * gnnpn_woa_candidates_fill: with n_lists = totals[0] and n_cand = totals[1] read back, writes cand_ptr [n_lists+1],
+ *   len_init [n_lists], cand [n_cand,4] f64, start_pos [n_lists] — the operands of gnnpn_eswoa_ragged_f64.
+ * gnnpn_debug_round5_f64: y[i] = round(x[i], 5) as the builder computes it (test hook). */
+#define GNNPN_WOA_OK 0
+#define GNNPN_WOA_ROWS_MISMATCH 1   /* as many non-dummy rows as kept lists, or none: WOA._prepare raises otherwise */
+#define GNNPN_WOA_INDEX_ERROR 2     /* addS replaces past the end of a kept list (reference: IndexError) */
+#define GNNPN_WOA_NO_SLOTS 3        /* no kept list and no rows: nothing to search */
+int64_t gnnpn_woa_candidates_workspace_bytes(int32_t B, int32_t n_nodes, int32_t max_cat_size);
+int gnnpn_woa_candidates_count(int32_t B, int32_t n_nodes, const float* x, int32_t x_ld, const int32_t* seg_ptr,
+                               const double* local_bounds, const double* global_bounds, int32_t n_cat, const int32_t* cat_ptr,
+                               const double* qos, const void* actions, int32_t actions_f64, int32_t actions_T, double reduct,
+                               const double* patches, int32_t n_patches, int32_t max_cat_size, void* workspace,
+                               int64_t workspace_bytes, int32_t* prob_ptr, int32_t* n_slots, double* bounds, int32_t* status,
+                               int32_t* totals, void* stream);
+int gnnpn_woa_candidates_fill(int32_t B, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr, const double* qos,
+                              int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status,
+                              const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* cand_ptr, int32_t* len_init,
+                              double* cand, int32_t* start_pos, void* stream);
+int gnnpn_debug_round5_f64(const double* x, double* y, int64_t n, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training step of the GNN candidate-ranking model.  Replaces the autograd graph of
  * src/models/trainML.py:39-45 over src/models/modelML.py:131-176 (model.train(): BatchNorm1d on batch statistics).  The

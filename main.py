@@ -9,6 +9,9 @@
                                          # `main.py <ds> ML` / `PNHigh` wrote for that epoch.  A missing file is an error
                                          # unless --random-init asks for seeded random weights
 
+    python main.py QWS ML+2PN -1 --infer --woa [--seed N]   # ... and refine the test quarter's actions with ES-WOA on the
+                                         # device ([<ds>-WOA] popSize / MAX_Iter / reduct): ./solutions/WOA/<ds>/ML+2PN+WOA.txt
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -150,7 +153,7 @@ def main(argv):
         return 0
     sec = cfg[f"{ds}-ML+2PN"]
     flags = [a for a in argv[3:] if a.startswith("--")]
-    pos = [a for a in argv[3:] if not a.startswith("--")]
+    pos = [a for i, a in enumerate(argv[3:]) if not a.startswith("--") and (i == 0 or argv[3 + i - 1] != "--seed")]
     epoch = int(pos[0]) if pos else int(sec["epoch"])
     n_cat = int(sec["serviceCategory"])
     if here not in sys.path:
@@ -162,7 +165,14 @@ def main(argv):
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
         net, low, high, K = _models(cfg, ds, n_services, len(sf), epoch, "--random-init" in flags)
-        ML2PN.infer(ds, net, low, high, K, epoch)
+        woa = None
+        if "--woa" in flags:                                        # + ES-WOA refinement on the device ([<ds>-WOA])
+            w = cfg[f"{ds}-WOA"]
+            args = argv[3:]
+            woa = {"popSize": int(w["popSize"]), "MAX_Iter": int(w["MAX_Iter"]),
+                   "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]),
+                   "seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
+        ML2PN.infer(ds, net, low, high, K, epoch, woa=woa)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
     return 0
