@@ -53,7 +53,8 @@ def check(dataset, serCategory, epoch):
     return result
 
 
-def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None):
+def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
+          sample_seed=None):
     """Run ML+2PN inference over ``./data/<dataset>`` on the GPU and write the two artefacts that
     ``check`` reads: the rankings of ALL problems (trainML.py:146-149 format, [P][S] ints) and the
     High-level actions of the test quarter (trainPNHigh.py:133-144 format, [T][nTest][8]).
@@ -62,7 +63,10 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     three-piece products: same selections on every pinned problem).
     ``woa``: a dict (popSize, MAX_Iter, reduct, seed) — then the test quarter's actions are also refined on the device
     (ML2PNPipeline.refine) and ``./solutions/WOA/<dataset>/ML+2PN+WOA.txt`` written as the WOA approach writes it (problem
-    ``idx`` on stream ``seed + idx``; seed None: fresh seeds)."""
+    ``idx`` on stream ``seed + idx``; seed None: fresh seeds).
+    ``samples`` > 1: best-of-N decoding (ML2PNPipeline.best_of): per problem the greedy answer or one of samples-1 sampled
+    High decodes, whichever has the smallest R; the refinement then starts from it.  ``sample_seed``: the draws' seed
+    (batch i of the run uses replica streams of sample_seed + i); None: fresh OS entropy."""
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -84,8 +88,17 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
         _, pb = ld.tables_from_dataset(ds, lo, hi)
         batch = DeviceBatch.from_problems(pb, dev)
         # a timed-out inter-workgroup hand-off must never reach an artefact file: checked per batch, repeated once if it happens
-        act = ops.run_checked(lambda attempt: pipe.run(svc, batch, write_through=attempt > 0)["actions"].cpu().numpy().astype(np.float64),
-                              dev)                                       # [b,T,8]
+        if samples > 1:
+            seed_b = None if sample_seed is None else (int(sample_seed) + lo // batch_size) & 0x7FFFFFFFFFFFFFFF
+            if seed_b is None:
+                from .modelPN import fresh_seed
+                seed_b = fresh_seed()           # one seed per batch
+            # best_of checks its own launches before it returns: a failed hand-off raises there (no repeat of the batch)
+            act = ops.run_checked(lambda attempt: pipe.best_of(svc, batch, samples, seed=seed_b, write_through=attempt > 0)["actions"]
+                                  .cpu().numpy().astype(np.float64), dev)
+        else:
+            act = ops.run_checked(lambda attempt: pipe.run(svc, batch, write_through=attempt > 0)["actions"].cpu().numpy().astype(np.float64),
+                                  dev)                                       # [b,T,8]
         rankings += pipe.rankings(svc, batch).cpu().tolist()
         for b in range(hi - lo):
             if lo + b >= n_train:

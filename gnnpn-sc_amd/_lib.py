@@ -66,6 +66,10 @@ _SIGNATURES = {
     "gnnpn_pointer_decode_f32": (c_int, [c_int, _P, _P, c_float, c_int, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          _P, _P, c_int64, _P]),
     "gnnpn_pointer_decode_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "gnnpn_pointer_decode_replicas_f32": (c_int, [_P, _P, c_float, c_int, c_int32, c_int32, c_int32, ctypes.c_uint64, c_int32, c_int32,
+                                                  c_int32, _P, _P, c_int64, _P]),
+    "gnnpn_replica_seed": (ctypes.c_uint64, [ctypes.c_uint64, c_int32]),
+    "gnnpn_best_of_select_f32": (c_int, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gnnpn_pointer_decode_attn_f32": (c_int, [_P, _P, _P, c_float, c_int, c_int32, c_int32, c_int32, c_int32, _P]),
     "gnnpn_attention_logits_f32": (c_int, [_P, _P, c_int64, _P, c_float, c_int, _P, c_int32, c_int32, c_int32,
                                            c_int32, c_int32, _P]),

@@ -62,6 +62,16 @@ __device__ __forceinline__ float stream_uniform24(unsigned long long seed, unsig
     return (float)(z >> 40) * 5.9604644775390625e-08f;
 }
 
+// seed of sampled replica `replica` (include/gnnpn_hip.h, gnnpn_pointer_decode_replicas_f32): the splitmix64 finaliser of
+// seed ^ (replica * odd constant), top bit cleared (63 bits: the seeds the sampling wrappers pass) — a hash, so that no two
+// replicas' streams are shifts of each other
+__host__ __device__ __forceinline__ unsigned long long replica_seed(unsigned long long seed, unsigned long long replica) {
+    unsigned long long z = seed ^ (replica * 0xD1B54A32D192ED03ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFFull;
+}
+
 // monotone map fp32 -> u32 (larger float -> larger unsigned; -0 < +0; NaNs sort above +inf)
 __device__ __forceinline__ unsigned float_order_key(float f) {
     unsigned u = __float_as_uint(f);

@@ -17,7 +17,9 @@
 #include "decode_shared.h"
 #include "lstm_shared.h"
 
-template <int H, int BT>
+// REP: sampled replicas (gnnpn_pointer_decode_replicas_f32; decode_shared.h ReplicaMap): B counts rows, row b reads the inputs
+// of problem b / rep_R and draws from replica_seed(sample_seed, rep_first + b % rep_R); the other builds never read the two
+template <int H, int BT, bool REP = false>
 __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
     const float* __restrict__ embedded, const float* __restrict__ enc_out, const float* __restrict__ h0,
     const float* __restrict__ c0, const float* __restrict__ start, const float* __restrict__ wih,
@@ -25,7 +27,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
     const float* __restrict__ latent_win, const float* __restrict__ inputs, float tanh_c, int use_tanh,
     int32_t* __restrict__ idx_out, float* __restrict__ win_logits, float* __restrict__ pick_prob,
     float* __restrict__ actions, float* __restrict__ queries, int32_t B, int32_t T, int32_t n_per, int sample,
-    unsigned long long sample_seed) {
+    unsigned long long sample_seed, int rep_R, int rep_first) {
     constexpr int NT = H < 64 ? 64 : H;
     constexpr int NW = NT / 64;
     __shared__ __attribute__((aligned(16))) float xs[BT][H];
@@ -40,6 +42,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
     const int L = T * n_per;
     const float4* __restrict__ Wi = reinterpret_cast<const float4*>(wih);
     const float4* __restrict__ Wh = reinterpret_cast<const float4*>(whh);
+    auto prob_of = [rep_R](int b) { return REP ? b / rep_R : b; };   // row -> problem whose inputs it reads
 
     float bi[4], bh[4], c[BT], h[BT];
 #pragma unroll
@@ -50,8 +53,8 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
 #pragma unroll
     for (int p = 0; p < BT; ++p) {
         const bool ok = owner && (b0 + p < B);
-        c[p] = ok ? c0[(int64_t)(b0 + p) * H + j] : 0.0f;
-        h[p] = ok ? h0[(int64_t)(b0 + p) * H + j] : 0.0f;
+        c[p] = ok ? c0[(int64_t)prob_of(b0 + p) * H + j] : 0.0f;
+        h[p] = ok ? h0[(int64_t)prob_of(b0 + p) * H + j] : 0.0f;
         if (owner) {
             hs[0][p][j] = h[p];
             xs[p][j] = start[j];
@@ -89,7 +92,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
             const int p = q / n_per, r = q - p * n_per;
             float part = 0.0f;
             if (b0 + p < B) {
-                const float* row = enc_out + ((int64_t)(b0 + p) * L + (int64_t)k * n_per + r) * H;
+                const float* row = enc_out + ((int64_t)prob_of(b0 + p) * L + (int64_t)k * n_per + r) * H;
                 for (int e = lane * 4; e < H; e += 256) {
                     const float4 ev = *reinterpret_cast<const float4*>(row + e);
                     const float4 hv = *reinterpret_cast<const float4*>(&hs[cur][p][e]);
@@ -108,13 +111,14 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
         if (j < BT && b0 + j < B) {
             const int p = j;
             const int64_t wbase = ((int64_t)(b0 + p) * T + k) * n_per;
+            const int64_t lbase = ((int64_t)prob_of(b0 + p) * T + k) * n_per;
             float best = 0.0f;
             int best_r = -1;
             for (int r = 0; r < n_per; ++r) {
                 float v = lg[p][r];
                 if (use_tanh) v = __fmul_rn(tanh_c, tanhf(v));
                 win_logits[wbase + r] = v;
-                if (latent_win) v = __fadd_rn(v, latent_win[wbase + r]);
+                if (latent_win) v = __fadd_rn(v, latent_win[lbase + r]);
                 lg[p][r] = v;
                 if (best_r < 0 || v > best) {   // strict '>' keeps the first maximum
                     best = v;
@@ -125,7 +129,9 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
             for (int r = 0; r < n_per; ++r) denom = __fadd_rn(denom, expf(__fsub_rn(lg[p][r], best)));
             float prob = 1.0f / denom;                              // exp(best-best)/sum
             if (sample) {   // multinomial(1) from the window softmax (modelPN.py:227-228): first r with u < cdf_r
-                const float u = stream_uniform24(sample_seed, (unsigned long long)(b0 + p) * T + k);
+                const unsigned long long seed =
+                    REP ? replica_seed(sample_seed, (unsigned long long)(rep_first + (b0 + p) % rep_R)) : sample_seed;
+                const float u = stream_uniform24(seed, (unsigned long long)prob_of(b0 + p) * T + k);
                 float cdf = 0.0f;
                 int pick = -1, last_pos = 0;
                 for (int r = 0; r < n_per; ++r) {
@@ -148,7 +154,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
 #pragma unroll
         for (int p = 0; p < BT; ++p) {
             if (b0 + p < B) {
-                const int64_t row = (int64_t)(b0 + p) * L + sel[p];
+                const int64_t row = (int64_t)prob_of(b0 + p) * L + sel[p];
                 if (owner) xs[p][j] = embedded[row * H + j];
                 if (j < 8) actions[((int64_t)(b0 + p) * T + k) * 8 + j] = inputs[row * 8 + j];
             }
@@ -157,21 +163,21 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
     }
 }
 
-template <int H>
+template <int H, bool REP = false>
 static void launch_decode(const float* embedded, const float* enc_out, const float* h0, const float* c0,
                           const float* start, const float* wih, const float* whh, const float* bih,
                           const float* bhh, const float* latent_win, const float* inputs, float tanh_c,
                           int use_tanh, int32_t* idx, float* win_logits, float* pick_prob, float* actions,
                           float* queries, int32_t B, int32_t T, int32_t n_per, int sample, unsigned long long sample_seed,
-                          hipStream_t s) {
+                          hipStream_t s, int rep_R = 0, int rep_first = 0) {
     constexpr int NT = H < 64 ? 64 : H;
     int bt = 1;
     while (bt < 4 && B / (bt * 2) >= 256) bt *= 2;
     dim3 grid((B + bt - 1) / bt), block(NT);
 #define GNNPN_LAUNCH_DEC(BT_)                                                                                  \
-    hipLaunchKernelGGL((pointer_decode_kernel<H, BT_>), grid, block, 0, s, embedded, enc_out, h0, c0, start, wih, \
+    hipLaunchKernelGGL((pointer_decode_kernel<H, BT_, REP>), grid, block, 0, s, embedded, enc_out, h0, c0, start, wih, \
                        whh, bih, bhh, latent_win, inputs, tanh_c, use_tanh, idx, win_logits, pick_prob, actions,  \
-                       queries, B, T, n_per, sample, sample_seed)
+                       queries, B, T, n_per, sample, sample_seed, rep_R, rep_first)
     switch (bt) {
         case 1: GNNPN_LAUNCH_DEC(1); break;
         case 2: GNNPN_LAUNCH_DEC(2); break;
@@ -266,6 +272,79 @@ extern "C" int gnnpn_pointer_decode_f32(int n_nets, const gnnpn_decode_net_t* ne
                               d.sample, d.sample_seed, s);
     }
     GNNPN_CHECK_LAUNCH("pointer_decode_f32");
+    return GNNPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sampled replicas of one net (best-of-N decoding): B x R rows over the inputs of B problems, by indirection (include/gnnpn_hip.h)
+extern "C" uint64_t gnnpn_replica_seed(uint64_t seed, int32_t replica) {
+    return replica_seed(seed, (unsigned long long)(long long)replica);
+}
+
+extern "C" int gnnpn_pointer_decode_replicas_f32(const gnnpn_decode_net_t* net, const float* inputs, float tanh_c, int use_tanh,
+                                                 int32_t B, int32_t R, int32_t first, uint64_t seed, int32_t T, int32_t n_per,
+                                                 int32_t H, const gnnpn_launch_opts_t* opts_in, void* workspace,
+                                                 int64_t workspace_bytes, void* stream) {
+    g_gnnpn_last_units = 0;
+    GNNPN_REQUIRE(R >= 1, "pointer_decode_replicas: R must be >= 1, got %d", R);
+    GNNPN_REQUIRE(first >= 0, "pointer_decode_replicas: first replica must be >= 0, got %d", first);
+    GNNPN_REQUIRE(B >= 0 && T > 0 && n_per >= 1 && n_per <= 64, "pointer_decode_replicas: bad shape (B %d, T %d, n_per %d)", B, T, n_per);
+    const int64_t rows = (int64_t)B * R;
+    GNNPN_REQUIRE(rows <= (1 << 30), "pointer_decode_replicas: B*R = %lld rows exceed 2^30", (long long)rows);
+    if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_replicas: hidden size %d not built (256, 32)", H);
+    if (B == 0) return GNNPN_OK;                    // empty batch: its buffers may be NULL
+    GNNPN_REQUIRE(net && inputs, "pointer_decode_replicas: null input");
+    const CoopOpts opts = coop_opts(opts_in);
+    GNNPN_REQUIRE(opts.impl >= 0 && opts.impl <= 2, "pointer_decode_replicas: opts.impl must be 0 (auto), 1 (streaming) or 2 (cooperative)");
+    GNNPN_REQUIRE(opts.lds_kb >= 0 && opts.lds_kb <= 160, "pointer_decode_replicas: opts.lds_kb must be 0..160");
+    const gnnpn_decode_net_t& d = *net;
+    GNNPN_REQUIRE(d.enc_out && d.h0 && d.c0 && d.start && d.wih_packed && d.whh_packed && d.bih && d.bhh,
+                  "pointer_decode_replicas: null input of the net");
+    GNNPN_REQUIRE(d.embedded || d.xw_fold, "pointer_decode_replicas: the net needs embedded or the folded input side");
+    GNNPN_REQUIRE((d.xw_fold != nullptr) == (d.xb_fold != nullptr) && (d.xw_fold != nullptr) == (d.start_fold != nullptr),
+                  "pointer_decode_replicas: xw_fold, xb_fold and start_fold go together");
+    GNNPN_REQUIRE(d.idx && d.win_logits && d.pick_prob && d.actions, "pointer_decode_replicas: null output");
+    GNNPN_REQUIRE(!d.queries, "pointer_decode_replicas: queries are not written (must be NULL)");
+    GNNPN_REQUIRE(d.latent_from == -1, "pointer_decode_replicas: latent_from must be -1 (Low's window logits come from latent_win)");
+    GNNPN_REQUIRE(gnnpn_aligned(d.wih_packed, 16) && gnnpn_aligned(d.whh_packed, 16) && gnnpn_aligned(d.enc_out, 16) &&
+                      (!d.embedded || gnnpn_aligned(d.embedded, 16)),
+                  "pointer_decode_replicas: weights / enc_out / embedded must be 16-byte aligned");
+    DecodeArgs args{};
+    memcpy(&args.net[0], &d, sizeof(DecodeNet));
+    args.net[0].sample = 1;
+    args.net[0].sample_seed = seed;
+    args.net[0].whh_split = nullptr;               // fp32 decoder arithmetic
+    args.inputs = inputs;
+    args.tanh_c = tanh_c;
+    args.use_tanh = use_tanh;
+    args.B = (int32_t)rows;
+    args.T = T;
+    args.K = n_per;
+    hipStream_t s = (hipStream_t)stream;
+    const bool coop = opts.impl != 1 && gnnpn_decode_coop_supported(H, n_per) && d.xw_fold && (workspace != nullptr || opts.impl == 2);
+    if (coop) {
+        const int64_t need = gnnpn_decode_coop_workspace_need(rows, T, n_per);
+        GNNPN_REQUIRE(workspace && workspace_bytes >= need && gnnpn_aligned(workspace, 256),
+                      "pointer_decode_replicas: B*R = %lld rows need a workspace of %lld B (256-B aligned), got %lld B",
+                      (long long)rows, (long long)need, (long long)workspace_bytes);
+        const int rc = gnnpn_launch_decode_coop(args, 1, GNNPN_PREC_F32, false, opts, workspace, workspace_bytes, s,
+                                                ReplicaMap{R, first});
+        if (rc != GNNPN_OK) return rc;
+        GNNPN_CHECK_LAUNCH("pointer_decode_replicas_f32(coop)");
+        return GNNPN_OK;
+    }
+    if (opts.impl == 2) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_replicas: the cooperative form needs H = 256, n_per <= 16 and the folded input side");
+    if (!d.embedded) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_replicas: the streaming form needs the embedded tensor");
+    const DecodeNet& n0 = args.net[0];
+    if (H == 256)
+        launch_decode<256, true>(n0.embedded, n0.enc_out, n0.h0, n0.c0, n0.start, n0.wih, n0.whh, n0.bih, n0.bhh, n0.latent_win,
+                                 inputs, tanh_c, use_tanh, n0.idx, n0.win_logits, n0.pick_prob, n0.actions, nullptr, (int32_t)rows,
+                                 T, n_per, 1, seed, s, R, first);
+    else
+        launch_decode<32, true>(n0.embedded, n0.enc_out, n0.h0, n0.c0, n0.start, n0.wih, n0.whh, n0.bih, n0.bhh, n0.latent_win,
+                                inputs, tanh_c, use_tanh, n0.idx, n0.win_logits, n0.pick_prob, n0.actions, nullptr, (int32_t)rows,
+                                T, n_per, 1, seed, s, R, first);
+    GNNPN_CHECK_LAUNCH("pointer_decode_replicas_f32");
     return GNNPN_OK;
 }
 
@@ -437,5 +516,66 @@ extern "C" int gnnpn_qos_reward_f32(const float* actions, float* R, int32_t B, i
     hipLaunchKernelGGL(qos_reward_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, actions, R, B, T,
                        level);
     GNNPN_CHECK_LAUNCH("qos_reward_f32");
+    return GNNPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Best-of-N selection: one WAVE per problem.  The lanes take the replicas' R in turn and reduce (order key of R, replica index)
+// to its minimum — smallest R, lowest index among equals (so replica 0, the greedy answer, wins every tie); then the wave
+// copies the winner's rows.  NaN sorts above everything (only an all-NaN problem picks it: replica 0); -0 counts as +0.
+__global__ __launch_bounds__(256) void best_of_select_kernel(int32_t B, int32_t N, int32_t T, const float* __restrict__ R0,
+                                                             const int32_t* __restrict__ idx0, const float* __restrict__ act0,
+                                                             const float* __restrict__ prob0, const float* __restrict__ Rs,
+                                                             const int32_t* __restrict__ idxs, const float* __restrict__ acts,
+                                                             const float* __restrict__ probs, float* __restrict__ R_out,
+                                                             int32_t* __restrict__ idx_out, float* __restrict__ act_out,
+                                                             float* __restrict__ prob_out, int32_t* __restrict__ winner) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                            // the whole wave
+    const int S = N - 1;
+    unsigned long long best = ~0ull;
+    for (int j = lane; j < N; j += 64) {
+        float r = j == 0 ? R0[b] : Rs[(int64_t)b * S + (j - 1)];
+        if (r == 0.0f) r = 0.0f;
+        const unsigned hi = r != r ? 0xFFFFFFFFu : float_order_key(r);
+        const unsigned long long key = ((unsigned long long)hi << 32) | (unsigned)j;
+        best = key < best ? key : best;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)(best & 0xffffffffu), off, 64);
+        const unsigned hi = __shfl_xor((unsigned)(best >> 32), off, 64);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        best = o < best ? o : best;
+    }
+    const int w = (int)(best & 0xffffffffu);
+    const int64_t src = w == 0 ? (int64_t)b : (int64_t)b * S + (w - 1);
+    const int32_t* si = (w == 0 ? idx0 : idxs) + src * T;
+    const float* sp = (w == 0 ? prob0 : probs) + src * T;
+    const float* sa = (w == 0 ? act0 : acts) + src * T * 8;
+    for (int t = lane; t < T; t += 64) {
+        idx_out[(int64_t)b * T + t] = si[t];
+        prob_out[(int64_t)b * T + t] = sp[t];
+    }
+    for (int i = lane; i < T * 8; i += 64) act_out[(int64_t)b * T * 8 + i] = sa[i];
+    if (lane == 0) {
+        winner[b] = w;
+        R_out[b] = w == 0 ? R0[b] : Rs[src];
+    }
+}
+
+extern "C" int gnnpn_best_of_select_f32(int32_t B, int32_t N, int32_t T, const float* R0, const int32_t* idx0, const float* actions0,
+                                        const float* probs0, const float* Rs, const int32_t* idxs, const float* actionss,
+                                        const float* probss, float* R_out, int32_t* idx_out, float* actions_out, float* probs_out,
+                                        int32_t* winner, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && N >= 1 && T > 0 && (int64_t)T * 8 < (1ll << 31), "best_of_select: bad argument (B %d, N %d, T %d)", B, N, T);
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(R0 && idx0 && actions0 && probs0, "best_of_select: null input (replica 0)");
+    GNNPN_REQUIRE(N == 1 || (Rs && idxs && actionss && probss), "best_of_select: null input (replicas 1..N-1)");
+    GNNPN_REQUIRE(R_out && idx_out && actions_out && probs_out && winner, "best_of_select: null output");
+    hipLaunchKernelGGL(best_of_select_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, N, T, R0, idx0, actions0,
+                       probs0, Rs, idxs, actionss, probss, R_out, idx_out, actions_out, probs_out, winner);
+    GNNPN_CHECK_LAUNCH("best_of_select_f32");
     return GNNPN_OK;
 }

@@ -76,12 +76,13 @@ __device__ __forceinline__ int ror16(int v, int n) {
 // OCC: workgroups per CU the build is sized for — 1 (512 registers: fastest alone) or 2 (256 registers: shares the
 // CU with a workgroup of another launch, pipeline.PipelinedRunner)
 // SAMPLE: the build that can draw the pick from the window softmax (gnnpn_decode_net_t.sample); the greedy builds carry
-// none of that code
+// none of that code.  Only this build reads `rep` (sampled replicas, decode_shared.h: row -> problem indirection)
 template <bool FOLDX, bool DIAG, bool SPLIT, int OCC, int EVH_ = (OCC == 2 ? 2 : 1), bool SAMPLE = false>
 __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArgs a, u64* __restrict__ xh,
                                                                      u64* __restrict__ xp, u64* __restrict__ xl,
                                                                      unsigned* __restrict__ err, unsigned* __restrict__ sticky,
-                                                                     int n_nets, int groups_per_net, int gpx, int ablate_arg, unsigned* __restrict__ seats) {
+                                                                     int n_nets, int groups_per_net, int gpx, int ablate_arg, unsigned* __restrict__ seats,
+                                                                     ReplicaMap rep) {
     const int ablate = DIAG ? ablate_arg : (ablate_arg & 128);
     __shared__ __attribute__((aligned(16))) float hs[SPLIT ? 3 * SPLIT_TILE / 2 : ROWS * LDH16];   // fp32 tile (k-quarter-major, stride LDT) | three fp16 piece tiles (stride LDH16 halfs)
     __shared__ float xs[FOLDX ? 1 : ROWS * LDH];
@@ -106,6 +107,10 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
     if (tid == 0 && same_xcd) atomicAdd(err + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics: workgroups on the same-XCD fast path (per XCD: its own line)
 
     const int B = a.B, T = a.T, K = a.K, L = T * K;
+    // row -> problem whose inputs the row reads: b / R for sampled replicas, the identity everywhere else (constant-folded
+    // in the builds that do not sample); outputs stay indexed by row
+    const int rep_R = SAMPLE ? rep.R : 0;
+    auto prob_of = [rep_R](int b) { return rep_R > 1 ? b / rep_R : b; };
     const bool latent_in_launch = net.latent_from >= 0;
     const bool has_lat = latent_in_launch || net.latent_win;
     bool publishes_latent = false;
@@ -166,11 +171,11 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
         // cell state / output of the two rows this lane finishes: rows kq*4 + {0,1} (c < 8) or kq*4 + {2,3} (c >= 8)
         const int own0 = kq * 4 + (c < 8 ? 0 : 2);
         f32x2 cst, hl = {0.f, 0.f};
-        cst.x = b0 + own0 < B ? net.c0[(int64_t)(b0 + own0) * H + unit] : 0.0f;
-        cst.y = b0 + own0 + 1 < B ? net.c0[(int64_t)(b0 + own0 + 1) * H + unit] : 0.0f;
+        cst.x = b0 + own0 < B ? net.c0[(int64_t)prob_of(b0 + own0) * H + unit] : 0.0f;
+        cst.y = b0 + own0 + 1 < B ? net.c0[(int64_t)prob_of(b0 + own0 + 1) * H + unit] : 0.0f;
         __syncthreads();   // previous tile is completely done with the LDS arrays
         for (int j = 0; j < ROWS; ++j) {
-            const float h0v = (b0 + j < B) ? net.h0[(int64_t)(b0 + j) * H + tid] : 0.0f;
+            const float h0v = (b0 + j < B) ? net.h0[(int64_t)prob_of(b0 + j) * H + tid] : 0.0f;
             if constexpr (SPLIT) split_store(reinterpret_cast<_Float16*>(hs) + j * LDH16 + tid, h0v);
             else hs[ht_index(j, tid)] = h0v;
             if (!FOLDX) xs[j * LDH + tid] = net.start[tid];
@@ -251,7 +256,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                             lv = __uint_as_float(vl);
                         } else if (net.latent_win) {
                             const int b = b0 + wave * 4 + lane / K;
-                            lv = b < B ? net.latent_win[((int64_t)b * T + (k - 1)) * K + lane % K] : 0.0f;
+                            lv = b < B ? net.latent_win[((int64_t)prob_of(b) * T + (k - 1)) * K + lane % K] : 0.0f;
                         }
                         lat[wave * 4 + lane / K][lane % K] = lv;
                     }
@@ -313,7 +318,11 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                                 const float pj = __shfl(pr, (lane & ~15) + j, 64);
                                 if (j <= r) cdf = __fadd_rn(cdf, pj);
                             }
-                            const float u = stream_uniform24(net.sample_seed, (unsigned long long)min(b, B - 1) * T + (k - 1));
+                            // replica rows: stream replica_seed(S, first + b % R) at the key of their problem (decode_shared.h)
+                            const int bs = min(b, B - 1);
+                            const unsigned long long seed = rep_R ? replica_seed(net.sample_seed, (unsigned long long)(rep.first + bs % rep_R))
+                                                                  : net.sample_seed;
+                            const float u = stream_uniform24(seed, (unsigned long long)prob_of(bs) * T + (k - 1));
                             const unsigned below = (unsigned)(__ballot(live && !(u < cdf)) >> (16 * kq)) & 0xffffu;
                             const unsigned pos = (unsigned)(__ballot(live && pr > 0.0f) >> (16 * kq)) & 0xffffu;
                             int cand = min((int)__popc(below), K - 1);           // cdf is non-decreasing: count = first r with u < cdf_r
@@ -340,14 +349,14 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                     // (lane (c, kq) holds features kq and 4+kq of row c): wave 0 of member 0 stores them below,
                     // once they have arrived, instead of a load -> wait -> store on the group's critical path.
                     const int bc = min(b0 + c, B - 1);
-                    const float* rowp = a.inputs + ((int64_t)bc * L + sel[c]) * 8;
+                    const float* rowp = a.inputs + ((int64_t)prob_of(bc) * L + sel[c]) * 8;
                     axf[0] = rowp[kq];
                     axf[1] = rowp[4 + kq];
                 } else if (member == 0 && tid < ROWS * 8) {
                     const int row = tid >> 3, b = b0 + row;
                     if (b < B)
                         net.actions[((int64_t)b * T + (k - 1)) * 8 + (tid & 7)] =
-                            a.inputs[((int64_t)b * L + sel[row]) * 8 + (tid & 7)];
+                            a.inputs[((int64_t)prob_of(b) * L + sel[row]) * 8 + (tid & 7)];
                 }
                 if (k == T) {
                     if (FOLDX && member == 0 && wave == 0 && b0 + c < B) {   // last pick: nothing left to hide the load behind
@@ -364,12 +373,12 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int f = tid + 256 * j, row = f >> 6, q4 = f & 63, b = b0 + row;
-                        xg[j] = b < B ? *reinterpret_cast<const float4*>(net.embedded + ((int64_t)b * L + sel[row]) * H + q4 * 4)
+                        xg[j] = b < B ? *reinterpret_cast<const float4*>(net.embedded + ((int64_t)prob_of(b) * L + sel[row]) * H + q4 * 4)
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
                     }
                 } else if (tid < ROWS * 8) {   // only the raw 8-feature row of the pick is fetched
                     const int row = tid >> 3, b = b0 + row;
-                    xraw = b < B ? a.inputs[((int64_t)b * L + sel[row]) * 8 + (tid & 7)] : 0.0f;
+                    xraw = b < B ? a.inputs[((int64_t)prob_of(b) * L + sel[row]) * 8 + (tid & 7)] : 0.0f;
                 }
             }
 
@@ -382,7 +391,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
             const bool pdot = ppair < ROWS * K;
             if (pdot) {
                 const int b = b0 + prow;
-                const float* src = net.enc_out + ((int64_t)b * L + (int64_t)k * K + pcand) * H + member * UNITS + phalf * (4 * EVN);
+                const float* src = net.enc_out + ((int64_t)prob_of(b) * L + (int64_t)k * K + pcand) * H + member * UNITS + phalf * (4 * EVN);
 #pragma unroll
                 for (int j = 0; j < EVN; ++j)
                     ev[j] = b < B ? *reinterpret_cast<const float4*>(src + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -537,11 +546,16 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
     }
 }
 
+// what this file's launches need at most for `rows` rows (no device call: argument checks use it before any launch)
+int64_t gnnpn_decode_coop_workspace_need(int64_t rows, int32_t T, int32_t n_per) {
+    const int64_t groups = 64, tiles = (rows + ROWS - 1) / ROWS;
+    return COOP_STATUS_BYTES + groups * 2 * ROWS * H * 8 + groups * 2 * G * ROWS * (int64_t)n_per * 8 +
+           tiles * T * ROWS * (int64_t)n_per * 8 + COOP_OVERREAD_BYTES;
+}
+
 extern "C" int64_t gnnpn_pointer_decode_workspace_bytes(int32_t B, int32_t T, int32_t n_per) {
     (void)gnnpn_cu_seat_table();   // callers size their workspace before the first launch and outside any capture: create the seat table here
-    const int64_t groups = 64, tiles = (B + ROWS - 1) / ROWS;
-    const int64_t a8 = COOP_STATUS_BYTES + groups * 2 * ROWS * H * 8 + groups * 2 * G * ROWS * (int64_t)n_per * 8 +
-                       tiles * T * ROWS * (int64_t)n_per * 8 + COOP_OVERREAD_BYTES;
+    const int64_t a8 = gnnpn_decode_coop_workspace_need(B, T, n_per);
     const int64_t lean = gnnpn_decode_lean_workspace_bytes(B, T, n_per);
     return a8 > lean ? a8 : lean;
 }
@@ -568,7 +582,7 @@ extern "C" int gnnpn_decode_diag(uint32_t* out, int32_t n_words, int32_t clear) 
 bool gnnpn_decode_coop_supported(int32_t H_, int32_t n_per) { return H_ == H && n_per <= KMAX; }
 
 int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
-                             void* workspace, int64_t workspace_bytes, hipStream_t s) {
+                             void* workspace, int64_t workspace_bytes, hipStream_t s, ReplicaMap rep) {
     int dev = 0, n_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -581,6 +595,8 @@ int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, 
         // keeps the two builds that one does not cover: the literal two-stage input side and the sampling decoder
         bool any_sample0 = false;
         for (int n = 0; n < n_nets; ++n) any_sample0 |= args.net[n].sample != 0;
+        if (rep.R > 0 && (n_nets != 1 || !any_sample0))
+            GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: sampled replicas are one sampling net per call");
         if (fold && !any_sample0 && args.K <= 16)
             return gnnpn_launch_decode_lean(args, n_nets, precision, shared_cu, opts, workspace, workspace_bytes, s);
     }
@@ -625,7 +641,7 @@ int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, 
 #define GNNPN_DEC8(FOLD_, SAMPLE_)                                                                                                       \
     hipLaunchKernelGGL((pointer_decode_coop_kernel<FOLD_, false, false, 1, 1, SAMPLE_>), dim3(COOP_OVERSUB * groups * G), dim3(256),          \
                        coop_lds_padding((const void*)pointer_decode_coop_kernel<FOLD_, false, false, 1, 1, SAMPLE_>, lds_kb), s, args, p_h, \
-                       p_p, p_l, p_err, p_s, n_nets, groups_per_net, gpx, abl, p_seats)
+                       p_p, p_l, p_err, p_s, n_nets, groups_per_net, gpx, abl, p_seats, rep)
     if (any_sample) GNNPN_DEC8(true, true);       // folded input side, every pick drawn from the window softmax
     else GNNPN_DEC8(false, false);                // the literal two-stage input side (embedding2, then W_ih), greedy
 #undef GNNPN_DEC8

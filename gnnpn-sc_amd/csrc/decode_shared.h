@@ -42,9 +42,18 @@ struct DecodeArgs {
     int32_t B, T, K;
 };
 
+// Sampled replicas (gnnpn_pointer_decode_replicas_f32): R = 0 — rows are problems, draws from net.sample_seed (every other
+// call); R >= 1 — args.B counts rows, row b is replica first + b % R of problem b / R, whose inputs it reads, drawing from
+// replica_seed(net.sample_seed, first + b % R) at key (b / R) * T + k.  Read only by the sampling builds.
+struct ReplicaMap {
+    int32_t R;
+    int32_t first;
+};
+
 bool gnnpn_decode_coop_supported(int32_t H, int32_t n_per);
+int64_t gnnpn_decode_coop_workspace_need(int64_t rows, int32_t T, int32_t n_per);   // decode_coop.hip, no device call
 int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
-                             void* workspace, int64_t workspace_bytes, hipStream_t s);
+                             void* workspace, int64_t workspace_bytes, hipStream_t s, ReplicaMap rep = ReplicaMap{0, 0});
 // decode_lean.hip: the production build of the cooperative form (folded input side, greedy picks; fp32 and exact split)
 int gnnpn_launch_decode_lean(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
                              void* workspace, int64_t workspace_bytes, hipStream_t s);

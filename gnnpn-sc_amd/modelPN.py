@@ -423,6 +423,14 @@ def two_level_greedy(low, high, inputs, fold=None, precision=None, decode_impl=0
         if getattr(la, name) != getattr(ha, name):
             raise ops.GnnpnError(f"two_level_greedy: Low and High nets differ in {name} ({getattr(la, name)!r} vs "
                                  f"{getattr(ha, name)!r}); decode them with separate CombinatorialRL.forward calls")
+    return _two_level_fused(low, high, inputs, fold, precision, decode_impl, lds_kb, write_through, ws, sample_high_seed,
+                            paired_start)[0]
+
+
+def _two_level_fused(low, high, inputs, fold, precision, decode_impl, lds_kb, write_through, ws, sample_high_seed, paired_start):
+    """The fused form of two_level_greedy (both encoders in one launch, both decoders in one launch).  -> (its dict, the High
+    net's encoder state (enc_out, h_n, c_n, embedded)) — two_level_best_of decodes more High replicas from that state."""
+    la, ha = low.actor, high.actor
     la.check_precision(precision)
     ha.check_precision(precision)
     enc_l, emb_l = la.encode_args(inputs, fold)
@@ -437,5 +445,93 @@ def two_level_greedy(low, high, inputs, fold=None, precision=None, decode_impl=0
                                 precision="split" if precision == "split" else "f32", impl=decode_impl, lds_kb=lds_kb,
                                 write_through=write_through, ws=ws, paired_start=paired_start)
     R = torch.ops.gnnpn.qos_reward(dh["actions"], 0 if high.level == "Low" else 1)
-    return {"idx_low": dl["idx"], "idx_high": dh["idx"], "R": R, "actions": dh["actions"],
-            "action_probs": dh["pick_prob"], "win_low": dl["win_logits"], "win_high_raw": dh["win_logits"]}
+    return ({"idx_low": dl["idx"], "idx_high": dh["idx"], "R": R, "actions": dh["actions"],
+             "action_probs": dh["pick_prob"], "win_low": dl["win_logits"], "win_high_raw": dh["win_logits"]},
+            (enc[1], h_n[1], c_n[1], emb_h))
+
+
+def fresh_seed():
+    """A seed from the OS's entropy (as WOA.fine_tune draws its streams when no seed is given)."""
+    return int.from_bytes(os.urandom(8), "little") & 0x7FFFFFFFFFFFFFFF
+
+
+def two_level_best_of(low, high, inputs, samples, seed=None, precision=None, fold=None, decode_impl=0, lds_kb=0, write_through=False,
+                      ws=None):
+    """Best-of-N decoding of the two-level scheme: replica 0 is two_level_greedy's answer, replicas 1..N-1 draw the High
+    level's picks from its window softmax (the sampling policy REINFORCE trains, trainPNHigh.py:83-84) against the same greedy
+    Low level; per problem the replica with the smallest R (round(violate + objFunc, 5), modelPN.py:61) is returned, the
+    lowest replica on ties — never worse than greedy.
+      1. both encoders once (one launch), 2. the fused greedy decode (replica 0 and Low's window logits), 3. ONE launch of
+      samples-1 sampled High replicas that read each problem's encoder state by indirection (ops.pointer_decode_replicas;
+      fp32 decoder arithmetic whatever the encoder's precision), 4. the replicas' R, 5. the selection (ops.best_of_select).
+    Replica j >= 1 draws from stream replica_seed(seed, j) (ops.replica_seed) at key b*T + k — draw for draw what the one-net
+    sampled decode of these problems with that sample_seed does.  seed None: fresh OS entropy.
+    Returns two_level_greedy's keys (the winners' idx_high, R, actions, action_probs; idx_low / win_low / win_high_raw of the
+    greedy pass) plus sample_index [B] i32 (the winning replica), R_all [B,N] and idx_all [B,N,T] (every replica's High picks).
+    The encoder state is never replicated.  The cooperative launches are checked (status words, proof of work) before
+    anything is returned: a failed hand-off raises GnnpnError."""
+    samples = int(samples)
+    if samples < 1:
+        raise ops.GnnpnError(f"two_level_best_of: samples must be >= 1, got {samples}")
+    seed = fresh_seed() if seed is None else int(seed)
+    inputs = inputs.contiguous()
+    la, ha = low.actor, high.actor
+    B = inputs.shape[0]
+    T, K = ha.serCategory, ha.serNumber
+    level = 0 if high.level == "Low" else 1
+    general = la.general or ha.general or la.embedding_size != 0 or ha.embedding_size != 0
+    if general:
+        # one net per call (two_level_greedy's general branch); the replicas loop the one-net sampled call
+        g = two_level_greedy(low, high, inputs, fold=fold, precision=precision, decode_impl=decode_impl, lds_kb=lds_kb,
+                             write_through=write_through, ws=ws)
+        if precision is None:
+            precision = default_precision(low, high, fold, False, decode_impl)
+        rep = None
+        if samples > 1:
+            lat = LatentWindows(g["win_low"], g["idx_low"], None, None, la.C, la.use_tanh)
+            outs = [ha.run(inputs, lat, fold=fold, sample_seed=ops.replica_seed(seed, j), encoder_precision=precision)
+                    for j in range(1, samples)]
+            rep = {"idx": torch.stack([o["idx"] for o in outs], 1).contiguous(),
+                   "actions": torch.stack([o["actions"] for o in outs], 1).contiguous(),
+                   "pick_prob": torch.stack([o["pick_prob"] for o in outs], 1).contiguous()}
+    else:
+        if precision is None:
+            precision = default_precision(low, high, fold, False, decode_impl)
+        g, (enc_h, h_h, c_h, emb_h) = _two_level_fused(low, high, inputs, fold, precision, decode_impl, lds_kb, write_through, ws,
+                                                        None, False)
+        rep = None
+        if samples > 1:
+            net = ha.decode_args(emb_h, enc_h, h_h, c_h, latent_win=g["win_low"], fold=fold)
+            rep = ops.pointer_decode_replicas(net, inputs, T, K, samples - 1, seed, first=1, tanh_c=ha.C, use_tanh=ha.use_tanh,
+                                              impl=decode_impl, lds_kb=lds_kb, write_through=write_through, ws=ws)
+    sam = None
+    if rep is not None:
+        act = rep["actions"]
+        R_s = torch.ops.gnnpn.qos_reward(act[..., -qosandcons:].reshape(B * (samples - 1), T, qosandcons).contiguous(), level)
+        sam = {"R": R_s.view(B, samples - 1), "idx": rep["idx"], "actions": act, "probs": rep["pick_prob"]}
+    sel = _select(g, sam, g["actions"].shape[-1])
+    if ops.coop_supported(ha.hidden_size, K, decode_impl):
+        ops.workspaces(inputs.device, ws).check()       # a failed hand-off of any launch above raises here, before rows are returned
+    out = dict(g)
+    out.update(idx_high=sel["idx"], R=sel["R"], actions=sel["actions"], action_probs=sel["probs"], sample_index=sel["winner"])
+    if sam is None:
+        out["R_all"] = g["R"].unsqueeze(1).clone()
+        out["idx_all"] = g["idx_high"].unsqueeze(1).clone()
+    else:
+        out["R_all"] = torch.cat([g["R"].unsqueeze(1), sam["R"]], 1)
+        out["idx_all"] = torch.cat([g["idx_high"].unsqueeze(1), sam["idx"]], 1)
+    return out
+
+
+def _select(g, sam, width):
+    """ops.best_of_select over action rows of ``width`` columns (8, or 9 with the category column: selected as 8 + 1)."""
+    greedy = {"R": g["R"], "idx": g["idx_high"], "actions": g["actions"][..., -qosandcons:].contiguous(), "probs": g["action_probs"]}
+    s = None if sam is None else dict(sam, actions=sam["actions"][..., -qosandcons:].contiguous())
+    sel = ops.best_of_select(greedy, s)
+    if width != qosandcons:
+        cat0 = g["actions"][..., :1]
+        cats = cat0.unsqueeze(1) if sam is None else torch.cat([cat0.unsqueeze(1), sam["actions"][..., :1]], 1)
+        w = sel["winner"].long()
+        pick = torch.gather(cats, 1, w.view(-1, 1, 1, 1).expand(-1, 1, cats.shape[2], 1)).squeeze(1)
+        sel["actions"] = torch.cat([pick, sel["actions"]], 2)
+    return sel

@@ -905,6 +905,100 @@ def qos_reward(actions, level):
     return R
 
 
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def replica_seed(seed, replica):
+    """Stream of sampled replica ``replica`` of a best-of call with ``seed`` (include/gnnpn_hip.h,
+    gnnpn_pointer_decode_replicas_f32): the splitmix64 finaliser of seed ^ (replica * 0xD1B54A32D192ED03) (mod 2^64), top bit
+    cleared — 63 bits, the range every sample_seed of the sampling wrappers has (custom_ops.pointer_decode).  A hash,
+    not an offset: stream s at draw k is splitmix64(s + (k+1) * golden), so seeds one golden step apart would repeat each
+    other's draws shifted by one step."""
+    z = (int(seed) ^ (int(replica) * 0xD1B54A32D192ED03)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFF
+
+
+def pointer_decode_replicas(net, inputs, n_cat, n_per, replicas, seed, first=1, tanh_c=10.0, use_tanh=True, impl=0, lds_kb=0,
+                            write_through=False, ws=None):
+    """``replicas`` sampled decodes of ONE net over the B problems of ``net`` / ``inputs`` in one launch
+    (gnnpn_pointer_decode_replicas_f32): row (b, j) is replica ``first + j`` of problem b and reads problem b's inputs by
+    indirection (nothing is replicated).  Its draws are those of pointer_decode with sample_seed = replica_seed(seed, first + j).
+    net: as one entry of pointer_decode's ``nets`` with ``latent_win`` (no latent_from, no queries).  fp32 decoder arithmetic.
+    Returns idx [B,R,T] i32, win_logits [B,R,T,K], pick_prob [B,R,T], actions [B,R,T,8]."""
+    B, L, H = net["enc_out"].shape
+    R = int(replicas)
+    if L != n_cat * n_per:
+        raise GnnpnError(f"pointer_decode_replicas: seq_len {L} != {n_cat}*{n_per}")
+    dev = net["enc_out"].device
+    out = {"idx": torch.empty((B, R, n_cat), dtype=I32, device=dev),
+           "win_logits": torch.empty((B, R, n_cat, n_per), dtype=F32, device=dev),
+           "pick_prob": torch.empty((B, R, n_cat), dtype=F32, device=dev),
+           "actions": torch.empty((B, R, n_cat, 8), dtype=F32, device=dev)}
+
+    def launch(impl_):
+        coop = coop_supported(H, n_per, impl_) and net.get("xw_fold") is not None
+        a = _lib.DecodeNet()
+        for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"), ("wih_packed", "wih"),
+                          ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
+            setattr(a, name, dev_ptr(net[key], F32, f"net.{key}").value)
+        emb = net.get("embedded")
+        if coop:
+            a.xw_fold = dev_ptr(net["xw_fold"], F32, "net.xw_fold").value
+            a.xb_fold = dev_ptr(net["xb_fold"], F32, "net.xb_fold").value
+            a.start_fold = dev_ptr(net["start_fold"], F32, "net.start_fold").value
+        elif emb is None:                          # the streaming form gathers embedded rows: formed once per problem, not per row
+            emb = linear(inputs.reshape(B * L, inputs.shape[2]), net["emb_w"], net["emb_b"]).view(B, L, H)
+        a.embedded = None if emb is None else dev_ptr(emb, F32, "net.embedded").value
+        lw = net.get("latent_win")
+        a.latent_win = None if lw is None else dev_ptr(lw, F32, "net.latent_win").value
+        a.latent_from = -1
+        a.idx = dev_ptr(out["idx"], I32, "idx").value
+        a.win_logits = dev_ptr(out["win_logits"], F32, "win").value
+        a.pick_prob = dev_ptr(out["pick_prob"], F32, "prob").value
+        a.actions = dev_ptr(out["actions"], F32, "actions").value
+        wsp = workspaces(dev, ws) if coop else None
+        buf = wsp.decode(B * R, n_cat, n_per) if coop else None
+        opts = _launch_opts(wsp, impl_, lds_kb, write_through)
+        rc = _lib.load().gnnpn_pointer_decode_replicas_f32(
+            _lib.ctypes.byref(a), dev_ptr(inputs, F32, "inputs"), float(tanh_c), int(bool(use_tanh)), B, R, int(first),
+            int(seed) & _M64, n_cat, n_per, H, _lib.ctypes.byref(opts), dev_ptr(buf, torch.uint8, "workspace", True),
+            0 if buf is None else buf.numel(), stream_ptr())
+        if rc == 0 and coop:
+            wsp.note_launch(1, _lib.load().gnnpn_last_launch_units())
+        return rc, emb
+
+    rc, emb = launch(impl)
+    if rc == _lib.E_UNSUP and impl == 0:        # a device the cooperative form is not built for (partitioned): the streaming form
+        rc, emb = launch(1)
+    check(rc, "gnnpn_pointer_decode_replicas_f32")
+    if emb is not None and net.get("embedded") is None:
+        out["_embedded"] = emb
+    return out
+
+
+def best_of_select(greedy, samples=None):
+    """Per problem, the replica with the smallest R — replica 0 = ``greedy`` (R [B], idx [B,T], actions [B,T,8], probs [B,T]),
+    replicas 1..N-1 = ``samples`` (R [B,N-1], idx [B,N-1,T], actions [B,N-1,T,8], probs [B,N-1,T]) or None; ties go to the
+    lowest index (gnnpn_best_of_select_f32).  -> dict(R [B], idx [B,T], actions [B,T,8], probs [B,T], winner [B] i32)."""
+    R0 = greedy["R"]
+    B, T = greedy["idx"].shape
+    N = 1 if samples is None else 1 + samples["R"].shape[1]
+    dev = R0.device
+    out = {"R": torch.empty(B, dtype=F32, device=dev), "idx": torch.empty((B, T), dtype=I32, device=dev),
+           "actions": torch.empty((B, T, 8), dtype=F32, device=dev), "probs": torch.empty((B, T), dtype=F32, device=dev),
+           "winner": torch.empty(B, dtype=I32, device=dev)}
+    sp = (lambda k, dt: None) if samples is None else (lambda k, dt: dev_ptr(samples[k], dt, f"samples.{k}"))
+    check(_lib.load().gnnpn_best_of_select_f32(
+        B, N, T, dev_ptr(R0, F32, "greedy.R"), dev_ptr(greedy["idx"], I32, "greedy.idx"),
+        dev_ptr(greedy["actions"], F32, "greedy.actions"), dev_ptr(greedy["probs"], F32, "greedy.probs"),
+        sp("R", F32), sp("idx", I32), sp("actions", F32), sp("probs", F32),
+        dev_ptr(out["R"], F32, "R"), dev_ptr(out["idx"], I32, "idx"), dev_ptr(out["actions"], F32, "actions"),
+        dev_ptr(out["probs"], F32, "probs"), dev_ptr(out["winner"], I32, "winner"), stream_ptr()), "gnnpn_best_of_select_f32")
+    return out
+
+
 def debug_cell_activations(x):
     """(sigmoid, tanh) as the LSTM-cell kernels evaluate them (test hook)."""
     sig, th = torch.empty_like(x), torch.empty_like(x)

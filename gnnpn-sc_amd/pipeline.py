@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, custom_ops, graph, ops   # noqa: F401  (custom_ops registers torch.ops.gnnpn.*)
-from .modelPN import two_level_greedy
+from .modelPN import two_level_best_of, two_level_greedy
 
 
 @dataclass
@@ -242,6 +242,19 @@ class ML2PNPipeline:
         else:
             out = two_level_greedy(self.low, self.high, rows, precision=self.precision, decode_impl=decode_impl,
                                    lds_kb=lds_kb, ws=ws, paired_start=paired_start, write_through=write_through)
+        out.update(scores=scores, pn_inputs=rows, candidate_ids=ids)
+        return out
+
+    @torch.no_grad()
+    def best_of(self, services, batch, samples, seed=None, decode_impl=0, lds_kb=0, ws=None, write_through=False):
+        """One pass with best-of-``samples`` decoding of the High level (modelPN.two_level_best_of): scores -> candidates ->
+        the greedy pass plus samples-1 sampled High replicas, the one with the smallest R per problem.  Returns run's keys (the
+        winners) plus sample_index, R_all and idx_all.  seed None: fresh OS entropy.  A separate call: run / capture are
+        unchanged; not capturable (it checks the cooperative launches' status before it returns)."""
+        scores = self.scores(services, batch)
+        rows, ids = self.candidates(services, batch, scores)
+        out = two_level_best_of(self.low, self.high, rows, samples, seed=seed, precision=self.precision, decode_impl=decode_impl,
+                                lds_kb=lds_kb, write_through=write_through, ws=ws)
         out.update(scores=scores, pn_inputs=rows, candidate_ids=ids)
         return out
 

@@ -516,6 +516,35 @@ int gnnpn_pointer_decode_attn_f32(const gnnpn_decode_net_t* net, const gnnpn_att
  * Low->High latent granules).  Word 0 after synchronisation: as for the encoder. */
 int64_t gnnpn_pointer_decode_workspace_bytes(int32_t B, int32_t T, int32_t n_per);
 
+/* Sampled replicas of ONE net over B problems (best-of-N decoding of the High level, modelPN.two_level_best_of):
+ * B x R rows, row b*R + j is replica `first + j` of problem b.  Every input of gnnpn_decode_net_t — enc_out, h0, c0,
+ * xw_fold / xb_fold / start_fold or embedded, latent_win [B,T,n_per] — and `inputs` [B,L,8] are read PER PROBLEM: the
+ * kernels map a row to its problem (row / R); nothing is replicated in memory.  Outputs are per row: idx [B,R,T],
+ * win_logits [B,R,T,n_per], pick_prob [B,R,T], actions [B,R,T,8]; queries must be NULL; latent_from must be -1; the
+ * net's sample / sample_seed fields are not read.  Every pick is drawn as gnnpn_pointer_decode_f32 draws with sample = 1:
+ * replica i of problem b takes draw (b*T + k) of the stream of
+ *     replica_seed(seed, i) = fmix(seed ^ (i * 0xD1B54A32D192ED03)) & 0x7FFFFFFFFFFFFFFF   (63 bits, as every sample_seed),
+ *     fmix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ * (all arithmetic mod 2^64) — so a replica is, draw for draw, the one-net sampled decode of the B problems with
+ * sample_seed = replica_seed(seed, i).  A hash, not an offset: the stream of seed s at draw k is fmix(s + (k+1)*golden),
+ * so seeds one golden step apart would repeat each other's draws shifted by one.  gnnpn_replica_seed computes it on the host.
+ * fp32 decoder arithmetic.  Cooperative form (H = 256, n_per <= 16, folded input side, workspace of
+ * gnnpn_pointer_decode_workspace_bytes(B*R, T, n_per)) or the streaming form (embedded given), chosen by opts->impl as for
+ * gnnpn_pointer_decode_f32 (0: cooperative where it is built and a workspace is given, else streaming).
+ * Errors before any launch: GNNPN_E_ARG for R < 1, B < 0, null pointers, a bad shape, B*R beyond the workspace. */
+int gnnpn_pointer_decode_replicas_f32(const gnnpn_decode_net_t* net, const float* inputs, float tanh_c, int use_tanh, int32_t B,
+                                      int32_t R, int32_t first, uint64_t seed, int32_t T, int32_t n_per, int32_t H,
+                                      const gnnpn_launch_opts_t* opts, void* workspace, int64_t workspace_bytes, void* stream);
+uint64_t gnnpn_replica_seed(uint64_t seed, int32_t replica);
+
+/* Best-of-N selection: replica 0 (the greedy answer: R0 [B], idx0 [B,T], actions0 [B,T,8], probs0 [B,T]) and replicas
+ * 1..N-1 (Rs [B,N-1], idxs [B,N-1,T], actionss [B,N-1,T,8], probss [B,N-1,T]; may be NULL when N = 1).  Per problem the
+ * replica with the SMALLEST R wins (the reward the REINFORCE step minimises, modelPN.py:61); ties go to the lowest replica
+ * index, so the greedy answer wins every tie.  Writes the winner's R, idx, actions and probs, and its index in winner [B]. */
+int gnnpn_best_of_select_f32(int32_t B, int32_t N, int32_t T, const float* R0, const int32_t* idx0, const float* actions0,
+                             const float* probs0, const float* Rs, const int32_t* idxs, const float* actionss, const float* probss,
+                             float* R_out, int32_t* idx_out, float* actions_out, float* probs_out, int32_t* winner, void* stream);
+
 /* Full-length attention logits of ONE decode step, for callers that need the reference's
  * return values verbatim (the reference returns every step's whole [B,L] logits tensor,
  * src/models/modelPN.py:239,291; only the window part feeds the decision):

@@ -11,6 +11,8 @@
 
     python main.py QWS ML+2PN -1 --infer --woa [--seed N]   # ... and refine the test quarter's actions with ES-WOA on the
                                          # device ([<ds>-WOA] popSize / MAX_Iter / reduct): ./solutions/WOA/<ds>/ML+2PN+WOA.txt
+    python main.py QWS ML+2PN -1 --infer --samples=N [--seed S] [--woa]   # best-of-N decoding of the High level: per problem
+                                         # the greedy answer or one of N-1 sampled decodes, the smallest R (--woa refines it)
 
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
@@ -172,7 +174,12 @@ def main(argv):
             woa = {"popSize": int(w["popSize"]), "MAX_Iter": int(w["MAX_Iter"]),
                    "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]),
                    "seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
-        ML2PN.infer(ds, net, low, high, K, epoch, woa=woa)
+        best = {}
+        samples = next((a.split("=", 1)[1] for a in flags if a.startswith("--samples=")), None)
+        if samples is not None:                                     # best-of-N decoding of the High level
+            args = argv[3:]
+            best = {"samples": int(samples), "sample_seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
+        ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
     return 0
