@@ -3,6 +3,8 @@
 // (problem, category) segment, each lane scanning a strided share of the segment; the K picks are
 // K wave-wide max-reductions over 64-bit keys (score order bits : inverted id), so ties resolve to
 // the lowest service id and the result does not depend on lane count or launch geometry.
+#include <vector>
+
 #include "common.h"
 
 __device__ __forceinline__ unsigned long long rank_key(float score, uint32_t id) {
@@ -305,9 +307,24 @@ __global__ void precision_at_k_kernel(const int32_t* __restrict__ ranking, int64
 extern "C" int gnnpn_precision_at_k(const int32_t* ranking, int64_t ld_rank, const float* labels, int64_t ld_lab,
                                     int32_t B, int32_t S, const int32_t* ks, int32_t n_k, float* out, void* stream) {
     GNNPN_REQUIRE(B >= 0 && S > 0 && n_k > 0 && ld_rank >= 1 && ld_lab >= S, "precision_at_k: bad shape");
+    GNNPN_REQUIRE(ks, "precision_at_k: null ks");
+    // the kernel reads min(k, S) ranking entries per row and divides by k: every k is checked before the launch (a stream-ordered
+    // copy of the n_k values, then a wait for it; this evaluation path is never captured into a graph)
+    std::vector<int32_t> kh((size_t)n_k);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(kh.data(), ks, sizeof(int32_t) * (size_t)n_k, hipMemcpyDefault, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "precision_at_k: reading ks failed");
+    int32_t kmax = 0;
+    for (int32_t k : kh) {
+        GNNPN_REQUIRE(k >= 1, "precision_at_k: k = %d (every k must be >= 1)", k);
+        kmax = k > kmax ? k : kmax;
+    }
+    GNNPN_REQUIRE(ld_rank >= (kmax < S ? kmax : S), "precision_at_k: ld_rank %lld < min(max k, S) = %d", (long long)ld_rank,
+                  kmax < S ? kmax : S);
     if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(ranking && labels && ks && out, "precision_at_k: null operand");
-    hipLaunchKernelGGL(precision_at_k_kernel, dim3((B * n_k + 127) / 128), dim3(128), 0, (hipStream_t)stream, ranking,
+    GNNPN_REQUIRE(ranking && labels && out, "precision_at_k: null operand");
+    hipLaunchKernelGGL(precision_at_k_kernel, dim3((B * n_k + 127) / 128), dim3(128), 0, s, ranking,
                        ld_rank, labels, ld_lab, B, S, ks, n_k, out);
     GNNPN_CHECK_LAUNCH("precision_at_k");
     return GNNPN_OK;

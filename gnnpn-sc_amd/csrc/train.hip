@@ -323,7 +323,7 @@ __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict_
 
 extern "C" int gnnpn_lstm_train_forward_f32(const float* pregates, const float* whh, const float* bhh, float* enc_out,
                                             float* gates_pre, float* c_all, int32_t B, int32_t L, int32_t H, void* stream) {
-    GNNPN_REQUIRE(pregates && whh && bhh && enc_out && gates_pre && c_all, "lstm_train_forward: null operand");
+    GNNPN_REQUIRE(B == 0 || (pregates && whh && bhh && enc_out && gates_pre && c_all), "lstm_train_forward: null operand");
     GNNPN_REQUIRE(B >= 0 && L > 0, "lstm_train_forward: bad shape");
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_train_forward: hidden size %d not built (256, 32)", H);
     GNNPN_REQUIRE(gnnpn_aligned(whh, 16), "lstm_train_forward: weights must be 16-byte aligned");
@@ -336,8 +336,8 @@ extern "C" int gnnpn_lstm_train_forward_f32(const float* pregates, const float* 
 
 extern "C" int gnnpn_decode_train_forward_f32(const gnnpn_decode_train_t* t, int32_t B, int32_t T, int32_t n_per, int32_t H,
                                               float tanh_c, int use_tanh, void* stream) {
-    GNNPN_REQUIRE(t && t->embedded && t->enc_out && t->h0 && t->c0 && t->start && t->wih && t->whh && t->bih && t->bhh && t->idx &&
-                      t->x_all && t->gates_pre && t->c_all && t->h_all && t->z0 && t->probs && t->logp,
+    GNNPN_REQUIRE(t && (B == 0 || (t->embedded && t->enc_out && t->h0 && t->c0 && t->start && t->wih && t->whh && t->bih && t->bhh &&
+                                   t->idx && t->x_all && t->gates_pre && t->c_all && t->h_all && t->z0 && t->probs && t->logp)),
                   "decode_train_forward: null operand");
     GNNPN_REQUIRE(B >= 0 && T > 0 && n_per >= 1 && n_per <= 64, "decode_train_forward: bad shape");
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "decode_train_forward: hidden size %d not built (256, 32)", H);
@@ -354,8 +354,8 @@ extern "C" int gnnpn_decode_train_forward_f32(const gnnpn_decode_train_t* t, int
 extern "C" int gnnpn_decode_train_backward_f32(const gnnpn_decode_train_t* t, const float* gscale, float* d_enc_out, float* dgates,
                                                float* dx, float* dh0, float* dc0, int32_t B, int32_t T, int32_t n_per, int32_t H,
                                                float tanh_c, int use_tanh, void* stream) {
-    GNNPN_REQUIRE(t && t->enc_out && t->c0 && t->wih && t->whh && t->idx && t->gates_pre && t->c_all && t->h_all && t->z0 &&
-                      t->probs && gscale && d_enc_out && dgates && dx && dh0 && dc0, "decode_train_backward: null operand");
+    GNNPN_REQUIRE(t && (B == 0 || (t->enc_out && t->c0 && t->wih && t->whh && t->idx && t->gates_pre && t->c_all && t->h_all && t->z0 &&
+                                   t->probs && gscale && d_enc_out && dgates && dx && dh0 && dc0)), "decode_train_backward: null operand");
     GNNPN_REQUIRE(B >= 0 && T > 0 && n_per >= 1 && n_per <= 64, "decode_train_backward: bad shape");
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "decode_train_backward: hidden size %d not built (256, 32)", H);
     if (B == 0) return GNNPN_OK;
@@ -370,7 +370,7 @@ extern "C" int gnnpn_decode_train_backward_f32(const gnnpn_decode_train_t* t, co
 extern "C" int gnnpn_lstm_train_backward_f32(const float* whh, const float* gates_pre, const float* c_all, const float* d_enc_out,
                                              const float* dh0, const float* dc0, float* dgates, int32_t B, int32_t L, int32_t H,
                                              void* stream) {
-    GNNPN_REQUIRE(whh && gates_pre && c_all && d_enc_out && dh0 && dc0 && dgates, "lstm_train_backward: null operand");
+    GNNPN_REQUIRE(B == 0 || (whh && gates_pre && c_all && d_enc_out && dh0 && dc0 && dgates), "lstm_train_backward: null operand");
     GNNPN_REQUIRE(B >= 0 && L > 0, "lstm_train_backward: bad shape");
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_train_backward: hidden size %d not built (256, 32)", H);
     if (B == 0) return GNNPN_OK;
@@ -411,7 +411,7 @@ extern "C" int gnnpn_scatter_dx_f32(const float* dx, const int32_t* idx, float* 
 }
 
 extern "C" int gnnpn_sumsq_f32(const float* x, int64_t n, double* accum, void* stream) {
-    GNNPN_REQUIRE(x && accum && n >= 0, "sumsq: bad argument");
+    GNNPN_REQUIRE((x || n == 0) && accum && n >= 0, "sumsq: bad argument");
     if (n == 0) return GNNPN_OK;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 1024) blocks = 1024;

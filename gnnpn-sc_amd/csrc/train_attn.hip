@@ -358,9 +358,9 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_attn_train_backward_
 }
 
 int check(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_per, int32_t H, const char* who) {
-    GNNPN_REQUIRE(t && t->base.embedded && t->base.enc_out && t->base.h0 && t->base.c0 && t->base.start && t->base.wih && t->base.whh &&
-                      t->base.bih && t->base.bhh && t->base.idx && t->base.x_all && t->base.gates_pre && t->base.c_all && t->base.h_all &&
-                      t->base.z0 && t->base.probs && t->base.logp && t->q_all,
+    GNNPN_REQUIRE(t && (B == 0 || (t->base.embedded && t->base.enc_out && t->base.h0 && t->base.c0 && t->base.start && t->base.wih &&
+                                   t->base.whh && t->base.bih && t->base.bhh && t->base.idx && t->base.x_all && t->base.gates_pre &&
+                                   t->base.c_all && t->base.h_all && t->base.z0 && t->base.probs && t->base.logp && t->q_all)),
                   "decode_attn_train: null operand");
     GNNPN_REQUIRE(B >= 0 && T > 0 && n_per >= 1 && n_per <= 64 && t->n_glimpses >= 0 && t->n_glimpses <= 8, "decode_attn_train: bad shape");
     GNNPN_REQUIRE(t->n_glimpses == 0 || t->a_all, "decode_attn_train: glimpse rounds need a_all");
@@ -375,15 +375,15 @@ int check(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_pe
 }
 }  // namespace
 
+// above 64 KB the dynamic LDS must be allowed first: a refusal is reported, nothing is launched
 #define GNNPN_ATTN_DISPATCH(H_, KERNEL, GRID, LDS_, ARG)                                                                      \
     do {                                                                                                                     \
-        if ((H_) == 256) {                                                                                                   \
-            (void)hipFuncSetAttribute((const void*)KERNEL<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_));    \
-            hipLaunchKernelGGL((KERNEL<256>), GRID, dim3(256), LDS_, s, ARG);                                                \
-        } else {                                                                                                             \
-            (void)hipFuncSetAttribute((const void*)KERNEL<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_));     \
-            hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(64), LDS_, s, ARG);                                                  \
-        }                                                                                                                    \
+        const void* f_ = (H_) == 256 ? (const void*)KERNEL<256> : (const void*)KERNEL<32>;                                  \
+        const hipError_t e_ = hipFuncSetAttribute(f_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_));           \
+        if (e_ != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: %u bytes of LDS refused: %s", #KERNEL, (unsigned)(LDS_),      \
+                                         hipGetErrorString(e_));                                                             \
+        if ((H_) == 256) hipLaunchKernelGGL((KERNEL<256>), GRID, dim3(256), LDS_, s, ARG);                                   \
+        else hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(64), LDS_, s, ARG);                                                 \
     } while (0)
 
 extern "C" int gnnpn_decode_attn_train_forward_f32(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_per, int32_t H,

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void bn_train_forward_kernel(const float* __re
         if (rg == 0) {
             invstd_out[c] = invstd;
             if (run_mean) {
-                const float unbiased = rows > 1 ? var * ((float)rows / (float)(rows - 1)) : var;
+                const float unbiased = var * ((float)rows / (float)(rows - 1));
                 run_mean[c] = fmaf(momentum, __fsub_rn(mean, run_mean[c]), run_mean[c]);
                 run_var[c] = fmaf(momentum, __fsub_rn(unbiased, run_var[c]), run_var[c]);
             }
@@ -162,7 +162,8 @@ extern "C" int gnnpn_bn_train_forward_f32(const float* x, int64_t rows, int32_t 
                                           float eps, float momentum, int relu, float* y, float* xhat, float* invstd,
                                           float* running_mean, float* running_var, void* stream) {
     GNNPN_REQUIRE(x && gamma && beta && y && xhat && invstd, "bn_train_forward: null argument");
-    GNNPN_REQUIRE(rows >= 1 && cols >= 1, "bn_train_forward: rows >= 1, cols >= 1");
+    // torch's training-mode BatchNorm raises on one row: the batch variance is 0 and the unbiased one undefined
+    GNNPN_REQUIRE(rows >= 2 && cols >= 1, "bn_train_forward: rows >= 2 (batch statistics), cols >= 1");
     GNNPN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_train_forward: both running buffers or neither");
     hipLaunchKernelGGL(bn_train_forward_kernel, dim3((cols + BN_COLS - 1) / BN_COLS), dim3(256), 0, (hipStream_t)stream, x, rows,
                        cols, gamma, beta, eps, momentum, relu, y, xhat, invstd, running_mean, running_var);

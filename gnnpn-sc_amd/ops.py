@@ -375,6 +375,11 @@ def rank_rows(scores):
 def precision_at_k(ranking, labels, ks=(1, 5)):
     """[B, n_k] fraction of the top-k ranked services with label 1 (trainML.py:63-70)."""
     B, S = labels.shape
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 1:
+        raise GnnpnError(f"precision_at_k: every k must be >= 1, got {ks}")
+    if ranking.dim() != 2 or ranking.shape[0] != B or ranking.shape[1] < min(max(ks), S):
+        raise GnnpnError(f"precision_at_k: ranking [B={B}, >= {min(max(ks), S)}] expected, got {tuple(ranking.shape)}")
     kt = torch.tensor(list(ks), dtype=I32, device=labels.device)
     out = torch.empty((B, len(ks)), dtype=F32, device=labels.device)
     check(_lib.load().gnnpn_precision_at_k(dev_ptr(ranking, I32, "ranking"), ranking.shape[1],
@@ -874,11 +879,17 @@ def attention_logits(enc_out, queries, step, idx, tanh_c=10.0, use_tanh=True):
     """Full [B,L] logits of decode step ``step`` with -inf at the ``step`` previously chosen
     positions (API-compat path, see gnnpn_attention_logits_f32)."""
     B, L, H = enc_out.shape
+    if queries.dim() != 3 or queries.shape[0] != B or queries.shape[2] != H:
+        raise GnnpnError(f"attention_logits: queries [B={B}, T, H={H}] expected, got {tuple(queries.shape)}")
     T = queries.shape[1]
+    if not 0 <= step < T:
+        raise GnnpnError(f"attention_logits: step {step} outside 0..{T - 1}")
+    if tuple(idx.shape) != (B, T):
+        raise GnnpnError(f"attention_logits: idx [B={B}, T={T}] expected, got {tuple(idx.shape)}")
+    qbase = dev_ptr(queries, F32, "queries").value
     out = torch.empty((B, L), dtype=F32, device=enc_out.device)
-    q = queries[:, step, :]
     check(_lib.load().gnnpn_attention_logits_f32(
-        dev_ptr(enc_out, F32, "enc_out"), _lib.ctypes.c_void_p(q.data_ptr()), T * H, dev_ptr(idx, I32, "idx"),
+        dev_ptr(enc_out, F32, "enc_out"), _lib.ctypes.c_void_p(qbase + 4 * step * H), T * H, dev_ptr(idx, I32, "idx"),
         float(tanh_c), int(bool(use_tanh)), dev_ptr(out, F32, "logits"), B, L, H, step, T, stream_ptr()),
         "gnnpn_attention_logits_f32")
     return out
@@ -1167,6 +1178,20 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
 
 # ---- REINFORCE training step of the High-level pointer network (csrc/train.hip; include/gnnpn_hip.h) -----------------
 
+def gemm_split(M, N, K):
+    """The number of k slices gemm gives gnnpn_gemm_f32 for a non-empty (M, N, K)."""
+    tiles = -(-M // 64) * -(-N // 64)
+    return 1 if tiles >= 256 or K < 2048 else max(1, min(64, 512 // tiles, K // 512))   # fill the chip when K >> M, N
+
+
+def colsum_chunking(rows):
+    """(rows_per_chunk, chunks) of colsum's first pass over ``rows`` rows, or None where one pass sums them."""
+    if rows < 4096:
+        return None
+    per = -(-rows // min(128, rows // 256))
+    return per, -(-rows // per)
+
+
 def gemm(a, b, a_kmajor=False, b_kmajor=False):
     """C[m,n] = sum_k Aop[m,k] * Bop[n,k]; an operand given k-major is [K, M] (resp. [K, N])   (gnnpn_gemm_f32)."""
     a, b = _rows2d(a, "gemm.a"), _rows2d(b, "gemm.b")
@@ -1174,8 +1199,11 @@ def gemm(a, b, a_kmajor=False, b_kmajor=False):
     N, Kb = (b.shape[1], b.shape[0]) if b_kmajor else b.shape
     if K != Kb:
         raise GnnpnError(f"gemm: K mismatch {tuple(a.shape)} x {tuple(b.shape)}")
-    tiles = -(-M // 64) * -(-N // 64)
-    split = 1 if tiles >= 256 or K < 2048 else max(1, min(64, 512 // tiles, K // 512))   # fill the chip when K >> M, N
+    if M == 0 or N == 0 or K == 0:                        # as torch.mm: an empty (M, N) result, or zeros for K = 0; no launch
+        if a.dtype != F32 or b.dtype != F32 or a.device != b.device:
+            raise GnnpnError(f"gemm: float32 operands on one device expected, got {a.dtype} on {a.device}, {b.dtype} on {b.device}")
+        return torch.zeros((M, N), dtype=F32, device=a.device)
+    split = gemm_split(M, N, K)
     c = torch.empty((split, M, N) if split > 1 else (M, N), dtype=F32, device=a.device)
     check(_lib.load().gnnpn_gemm_f32(dev_ptr(a, F32, "a"), a.shape[1], int(a_kmajor), dev_ptr(b, F32, "b"), b.shape[1],
                                      int(b_kmajor), dev_ptr(c, F32, "c"), N, M, N, K, split, stream_ptr()), "gnnpn_gemm_f32")
@@ -1186,16 +1214,23 @@ def gemm(a, b, a_kmajor=False, b_kmajor=False):
 
 def colsum(x, rows=None, cols=None, ld=None):
     """out[c] = sum_r x[r, c] (bias gradients; with rows/cols/ld a strided view of a larger buffer)   (gnnpn_colsum_f32)."""
-    rows = x.shape[0] if rows is None else rows
-    cols = x.shape[-1] if cols is None else cols
-    ld = x.shape[-1] if ld is None else ld
-    if rows >= 4096:                                      # two passes: the first fills the chip
-        per = -(-rows // min(128, rows // 256))
-        chunks = -(-rows // per)
+    rows = x.shape[0] if rows is None else int(rows)
+    cols = x.shape[-1] if cols is None else int(cols)
+    ld = x.shape[-1] if ld is None else int(ld)
+    if rows < 0 or cols < 1 or ld < cols:
+        raise GnnpnError(f"colsum: rows {rows} >= 0, 1 <= cols {cols} <= ld {ld} required")
+    if rows and (rows - 1) * ld + cols > x.numel():
+        raise GnnpnError(f"colsum: {rows} rows of {cols} at stride {ld} need {(rows - 1) * ld + cols} elements, x has {x.numel()}")
+    plan = colsum_chunking(rows)
+    if plan:                                              # two passes: the first fills the chip
+        per, chunks = plan
         partial = torch.empty((chunks, cols), dtype=F32, device=x.device)
         check(_lib.load().gnnpn_colsum_chunks_f32(dev_ptr(x, F32, "x"), ld, rows, cols, per, dev_ptr(partial, F32, "partial"),
                                                   stream_ptr()), "gnnpn_colsum_chunks_f32")
         x, rows, ld = partial, chunks, cols
+    if rows == 0:                                         # as x.sum(0) of no rows (nothing to launch; an empty x has no pointer)
+        dev_ptr(x, F32, "x")
+        return torch.zeros(cols, dtype=F32, device=x.device)
     out = torch.empty(cols, dtype=F32, device=x.device)
     check(_lib.load().gnnpn_colsum_f32(dev_ptr(x, F32, "x"), ld, rows, cols, dev_ptr(out, F32, "out"), stream_ptr()),
           "gnnpn_colsum_f32")
@@ -1389,6 +1424,9 @@ def dot(a, b):
     a, b = a.contiguous(), b.contiguous()
     if a.numel() != b.numel():
         raise GnnpnError("dot: sizes differ")
+    if a.numel() == 0:                                    # torch.dot of empty vectors (an empty tensor has no pointer to pass)
+        dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b")
+        return torch.zeros(1, dtype=F32, device=a.device)
     out = torch.empty(1, dtype=F32, device=a.device)
     check(_lib.load().gnnpn_dot_f32(dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b"), a.numel(), dev_ptr(out, F32, "out"), stream_ptr()),
           "gnnpn_dot_f32")
@@ -1398,6 +1436,11 @@ def dot(a, b):
 def embed_grad(dh, x, c, vocab):
     """Gradient of the embedding table of embed_concat: dh [N, >= c] (its first c columns), ids in x[:, 0] -> [vocab, c]."""
     dh, x = _rows2d(dh, "embed_grad.dh"), _rows2d(x, "embed_grad.x")
+    if dh.shape[0] != x.shape[0]:
+        raise GnnpnError(f"embed_grad: dh has {dh.shape[0]} rows, x {x.shape[0]}")
+    if dh.shape[0] == 0:                                  # no rows: every table row's gradient is 0 (an empty tensor has no pointer)
+        dev_ptr(dh, F32, "dh"), dev_ptr(x, F32, "x")
+        return torch.zeros((vocab, c), dtype=F32, device=dh.device)
     out = torch.empty((vocab, c), dtype=F32, device=dh.device)
     check(_lib.load().gnnpn_embed_grad_f32(dev_ptr(dh, F32, "dh"), dh.shape[1], dev_ptr(x, F32, "x"), x.shape[1], dh.shape[0], c,
                                            vocab, dev_ptr(out, F32, "dtable"), stream_ptr()), "gnnpn_embed_grad_f32")

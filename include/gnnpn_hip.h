@@ -252,8 +252,9 @@ int gnnpn_select_candidates(const float* scores, int64_t ld_scores, const int32_
 int gnnpn_rank_rows(const float* scores, int64_t ld_scores, int32_t* ranking, int32_t B, int32_t S,
                     void* stream);
 
-/* P@k: out[b, i] = #(labels[b, ranking[b, j]] == 1 for j < ks[i]) / ks[i].  ranking [B, >=max k]
- * int32, labels [B,S] fp32 (0/1), ks [n_k] int32 (device), out [B, n_k] fp32.
+/* P@k: out[b, i] = #(labels[b, ranking[b, j]] == 1 for j < min(ks[i], S)) / ks[i].  ranking [B, >= min(max k, S)]
+ * int32 (ld_rank >= min(max k, S)), labels [B,S] fp32 (only 1 counts), ks [n_k] int32 (device), every k >= 1, out [B, n_k] fp32.
+ * The ks are read back (stream-ordered) and checked before the launch: the call waits for the stream; GNNPN_E_ARG for k < 1.
  * Replaces the P@1 / P@5 loop of TrainML.test (src/models/trainML.py:63-70). */
 int gnnpn_precision_at_k(const int32_t* ranking, int64_t ld_rank, const float* labels, int64_t ld_lab,
                          int32_t B, int32_t S, const int32_t* ks, int32_t n_k, float* out, void* stream);
@@ -633,7 +634,9 @@ int gnnpn_lstm_train_backward_f32(const float* whh, const float* gates_pre, cons
  * `ref` = W_ref(enc_out) + b_ref per attention module ([B,L,H], gnnpn_linear_f32 by the caller).  The forward saves the queries
  * q_0 = h_k ... q_G of every step and the glimpse softmaxes; the backward (d_enc_out is ADDED to: the caller zeroes it, as d_p_ref /
  * d_g_ref) leaves d ref, the gradients wrt the projected queries (W_query's gradient = their GEMM with the saved queries, its
- * bias' their column sum) and per-problem sums for V.  W_ref's gradient and d enc_out's share through ref are GEMMs over d ref. */
+ * bias' their column sum) and per-problem sums for V.  W_ref's gradient and d enc_out's share through ref are GEMMs over d ref.
+ * n_glimpses 0..8, n_per 1..64, L = T * n_per <= 12800 positions (the backward keeps 8 L bytes, the forward 5 L, in dynamic LDS):
+ * GNNPN_E_UNSUP above; GNNPN_E_LAUNCH when the runtime refuses that much dynamic LDS (nothing enqueued). */
 typedef struct {
     gnnpn_decode_train_t base;
     int32_t bahdanau;        /* 0 'Dot', 1 'Bahdanau' */
@@ -794,7 +797,8 @@ int gnnpn_debug_round5_f64(const double* x, double* y, int64_t n, void* stream);
  * (gnnpn_gemm_f32, gnnpn_colsum_f32, gnnpn_adam_step_f32) and:
  * gnnpn_bn_train_forward_f32: y = [relu](gamma * xhat + beta), xhat = (x - mean) / sqrt(var_biased + eps) over the rows
  *   (BatchNorm1d at modelML.py:79,87,141,154 in training mode); saves xhat [rows,cols] and invstd [cols]; running_mean /
- *   running_var (optional) move by `momentum` towards the batch mean / unbiased variance.
+ *   running_var (optional) move by `momentum` towards the batch mean / unbiased variance.  rows >= 2 (GNNPN_E_ARG otherwise,
+ *   as torch's training-mode BatchNorm raises on one row).
  * gnnpn_bn_train_backward_f32: dy wrt the (post-ReLU) output -> dx, dgamma, dbeta.
  * gnnpn_bce_sigmoid_f32: loss = BCELoss(mean)(p, y) (trainML.py:28,42; log terms clamped at -100) for p = sigmoid(z), and
  *   dz = dLoss/dz as autograd forms it (BCELoss backward with its 1e-12 clamp, then sigmoid backward).
