@@ -21,16 +21,7 @@ extern "C" int gnnpn_lds_footprint_kb(int kb) {
     return prev;
 }
 // dynamic LDS bytes that bring `func`'s footprint to the calling thread's setting (0: none asked for, or the kernel is larger)
-unsigned gnnpn_front_lds_pad(const void* func) {
-    const int kb = g_gnnpn_lds_footprint_kb;
-    if (kb <= 0) return 0;
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, func) != hipSuccess) return 0;
-    const long dyn = (long)kb * 1024 - (long)a.sharedSizeBytes;
-    if (dyn <= 0) return 0;
-    if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return 0;
-    return (unsigned)dyn;
-}
+unsigned gnnpn_front_lds_pad(const void* func) { return gnnpn_lds_padding(func, g_gnnpn_lds_footprint_kb); }
 
 extern "C" int gnnpn_abi_version(void) { return GNNPN_ABI_VERSION; }
 extern "C" const char* gnnpn_last_error(void) { return g_gnnpn_err; }

@@ -29,7 +29,19 @@ extern thread_local char g_gnnpn_err[256];
     } while (0)
 
 static inline bool gnnpn_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-unsigned gnnpn_front_lds_pad(const void* func);   // api.hip: dynamic LDS bytes up to the thread's gnnpn_lds_footprint_kb (0: none)
+
+// dynamic LDS bytes that bring `func`'s footprint to `target_kb` KB (0: none asked for, or the kernel is larger) — a placement
+// constraint callers may ask for (gnnpn_launch_opts_t.lds_kb, gnnpn_lds_footprint_kb); not needed for correctness
+inline unsigned gnnpn_lds_padding(const void* func, int target_kb) {
+    if (target_kb <= 0) return 0;
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, func) != hipSuccess) return 0;
+    const long dyn = (long)target_kb * 1024 - (long)a.sharedSizeBytes;
+    if (dyn <= 0) return 0;
+    if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return 0;
+    return (unsigned)dyn;
+}
+unsigned gnnpn_front_lds_pad(const void* func);   // api.hip: gnnpn_lds_padding up to the thread's gnnpn_lds_footprint_kb
 
 // ---- device helpers -------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

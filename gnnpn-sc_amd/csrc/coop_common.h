@@ -1,14 +1,13 @@
-// Helpers shared by the cooperative recurrent kernels (lstm_coop.hip, decode_coop.hip).
+// Helpers shared by the cooperative recurrent kernels (lstm_coop.hip, decode_coop.hip, decode_lean.hip), and the host side of
+// their launch protocol (coop_begin).
 #pragma once
 #include "common.h"
+#include "lstm_shared.h"   // CoopOpts, the seat table, g_gnnpn_last_units
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 // ---- granule hand-off (CDNA4 guide, Guideline 16 / R2): 8-byte {tag, value}, ONE sc1 store / load
-__device__ __forceinline__ u64 granule_load(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // global_load_dwordx2 sc1
-}
 __device__ __forceinline__ void granule_store(u64* p, unsigned tag, float v) {
     __hip_atomic_store(p, ((u64)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);                                // global_store_dwordx2 sc1
@@ -30,31 +29,12 @@ __device__ __forceinline__ const u64* uniform_ptr(const u64* p) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return reinterpret_cast<const u64*>(((unsigned long long)hi << 32) | lo);
 }
-// pair j of lane l: base + 16 l + 1024 j bytes (`voff` = 16 l)
-__device__ __forceinline__ void granule_load2_x8(u32x4 (&v)[8], const u64* base, unsigned voff) {
-    const u64* q = base + 512;                               // + 4 KB: the 13-bit immediate reaches 4095
-    asm volatile(GNNPN_LD2("%0", "%8", "%9", "0") GNNPN_LD2("%1", "%8", "%9", "1024") GNNPN_LD2("%2", "%8", "%9", "2048")
-                 GNNPN_LD2("%3", "%8", "%9", "3072") GNNPN_LD2("%4", "%8", "%10", "0") GNNPN_LD2("%5", "%8", "%10", "1024")
-                 GNNPN_LD2("%6", "%8", "%10", "2048") GNNPN_LD2("%7", "%8", "%10", "3072")
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-                 : "v"(voff), "s"(base), "s"(q)
-                 : "memory");
-}
-// the same for the lanes that still miss something (call under `if (lane_is_missing)`): the others keep what they have
-__device__ __forceinline__ void granule_reload2_x8(u32x4 (&v)[8], const u64* base, unsigned voff) {
-    const u64* q = base + 512;
-    asm volatile(GNNPN_LD2("%0", "%8", "%9", "0") GNNPN_LD2("%1", "%8", "%9", "1024") GNNPN_LD2("%2", "%8", "%9", "2048")
-                 GNNPN_LD2("%3", "%8", "%9", "3072") GNNPN_LD2("%4", "%8", "%10", "0") GNNPN_LD2("%5", "%8", "%10", "1024")
-                 GNNPN_LD2("%6", "%8", "%10", "2048") GNNPN_LD2("%7", "%8", "%10", "3072")
-                 "s_waitcnt vmcnt(0)"
-                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])
-                 : "v"(voff), "s"(base), "s"(q)
-                 : "memory");
-}
-// the same with the lane mask applied INSIDE the statement (s_and_saveexec ... restore): unconditional at the source level,
-// operands tied in place — a sweep loop built on this one statement keeps its 32 registers where they are (a separate
-// first-pass load, or this load under an `if`, made the register allocator copy all of them every step)
+// Pair j of lane l: base + 16 l + 1024 j bytes (`voff` = 16 l); the second four pairs from base + 4 KB (the 13-bit immediate
+// reaches 4095).
+// Eight pairs for the lanes in `lanes` (the others keep what they have), the lane mask applied INSIDE the statement
+// (s_and_saveexec ... restore): unconditional at the source level, operands tied in place — a sweep loop built on this one
+// statement keeps its 32 registers where they are (a separate first-pass load, or the load under an `if`, made the register
+// allocator copy all of them every step)
 __device__ __forceinline__ void granule_reload2_x8_masked(u32x4 (&v)[8], const u64* base, unsigned voff, unsigned long long lanes) {
     const u64* q = base + 512;
     unsigned long long saved;
@@ -68,19 +48,7 @@ __device__ __forceinline__ void granule_reload2_x8_masked(u32x4 (&v)[8], const u
                  : "v"(voff), "s"(base), "s"(q), "s"(lanes)
                  : "memory", "scc");
 }
-// 8 pairs at `base` (h quarter) and NP pairs at `pbase` (partial dots), one wait
-__device__ __forceinline__ void granule_load2_x8_x2(u32x4 (&v)[8], u32x4 (&w)[2], const u64* base, const u64* pbase, unsigned voff) {
-    const u64* q = base + 512;
-    asm volatile(GNNPN_LD2("%0", "%10", "%11", "0") GNNPN_LD2("%1", "%10", "%11", "1024") GNNPN_LD2("%2", "%10", "%11", "2048")
-                 GNNPN_LD2("%3", "%10", "%11", "3072") GNNPN_LD2("%4", "%10", "%12", "0") GNNPN_LD2("%5", "%10", "%12", "1024")
-                 GNNPN_LD2("%6", "%10", "%12", "2048") GNNPN_LD2("%7", "%10", "%12", "3072")
-                 GNNPN_LD2("%8", "%10", "%13", "0") GNNPN_LD2("%9", "%10", "%13", "1024")
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]),
-                   "=&v"(w[0]), "=&v"(w[1])
-                 : "v"(voff), "s"(base), "s"(q), "s"(pbase)
-                 : "memory");
-}
+// 8 pairs at `base` (h quarter) and 4 pairs at `pbase` (partial dots), one wait
 __device__ __forceinline__ void granule_load2_x8_x4(u32x4 (&v)[8], u32x4 (&w)[4], const u64* base, const u64* pbase, unsigned voff) {
     const u64* q = base + 512;
     asm volatile(GNNPN_LD2("%0", "%12", "%13", "0") GNNPN_LD2("%1", "%12", "%13", "1024") GNNPN_LD2("%2", "%12", "%13", "2048")
@@ -98,20 +66,6 @@ __device__ __forceinline__ void granule_load2_x8_x4(u32x4 (&v)[8], u32x4 (&w)[4]
 // ... and ONE more granule per lane at `lbase` + 8 * lane (the Low net's window logits, read by the High net): in the same
 // statement, so that it shares the sweep's round trip — as a separate load behind the statement's wait it cost the High net
 // a second, dependent L2 round trip every step.  Lanes beyond the window read on (inside the workspace: COOP_OVERREAD_BYTES).
-__device__ __forceinline__ void granule_load2_x8_x2_lat(u32x4 (&v)[8], u32x4 (&w)[2], u64& lat, const u64* base, const u64* pbase,
-                                                        const u64* lbase, unsigned voff) {
-    const u64* q = base + 512;
-    asm volatile(GNNPN_LD2("%0", "%11", "%13", "0") GNNPN_LD2("%1", "%11", "%13", "1024") GNNPN_LD2("%2", "%11", "%13", "2048")
-                 GNNPN_LD2("%3", "%11", "%13", "3072") GNNPN_LD2("%4", "%11", "%14", "0") GNNPN_LD2("%5", "%11", "%14", "1024")
-                 GNNPN_LD2("%6", "%11", "%14", "2048") GNNPN_LD2("%7", "%11", "%14", "3072")
-                 GNNPN_LD2("%8", "%11", "%15", "0") GNNPN_LD2("%9", "%11", "%15", "1024")
-                 "global_load_dwordx2 %10, %12, %16 sc1\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]),
-                   "=&v"(w[0]), "=&v"(w[1]), "=&v"(lat)
-                 : "v"(voff), "v"(voff >> 1), "s"(base), "s"(q), "s"(pbase), "s"(lbase)
-                 : "memory");
-}
 __device__ __forceinline__ void granule_load2_x8_x4_lat(u32x4 (&v)[8], u32x4 (&w)[4], u64& lat, const u64* base, const u64* pbase,
                                                         const u64* lbase, unsigned voff) {
     const u64* q = base + 512;
@@ -195,18 +149,6 @@ __device__ __forceinline__ void granule_publish(u64* p, unsigned tag, float v, b
     else granule_store(p, tag, v);
 }
 
-// Host side: bytes of (unused) dynamic LDS that bring `func`'s footprint to gnnpn_launch_opts_t.lds_kb (an extra placement
-// constraint callers may still ask for; not needed for correctness any more).
-inline unsigned coop_lds_padding(const void* func, int target_kb) {
-    if (target_kb <= 0) return 0;
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, func) != hipSuccess) return 0;
-    const long dyn = (long)target_kb * 1024 - (long)a.sharedSizeBytes;
-    if (dyn <= 0) return 0;
-    if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return 0;
-    return (unsigned)dyn;
-}
-
 // Zeroing of the hand-off workspace before every launch (status words, claim table, every granule tag).  A kernel of our
 // own rather than hipMemsetAsync: with two captured graphs replaying on two streams, the memset NODES of one graph were
 // observed to fill with a 16-byte pattern made of another launch's kernel arguments (tools/soak_pipeline.py: persistent
@@ -239,6 +181,71 @@ inline hipError_t coop_zero_workspace(void* workspace, size_t bytes, hipStream_t
     hipLaunchKernelGGL(coop_zero_kernel, dim3(blocks), dim3(256), 0, s, static_cast<unsigned long long*>(workspace), n8, sticky, word,
                        expected, skip_zeroing ? 1 : 0);
     return hipGetLastError();
+}
+
+// ---- host side: the launch protocol of the three cooperative launchers -------------------------------------------------------
+// Every cooperative kernel is built for groups of COOP_G workgroups (one per CU, all on one XCD), tiles of COOP_ROWS problems
+// and hidden size COOP_H.
+constexpr int COOP_G = 8, COOP_ROWS = 16, COOP_H = 256;
+
+struct CoopLaunch {
+    int n_tiles, gpx, groups, groups_per_net;
+    unsigned* status;   // the launch's status area: the first COOP_STATUS_BYTES of the workspace
+    char* buffers;      // the exchange buffers behind it
+    unsigned* seats;    // the device's canonical seat table (api.hip)
+};
+
+// What every launcher does before its kernel, in this order: the device query; groups per XCD, the refusal of a partitioned
+// device, groups and groups per net; the workspace check against the kernel family's size function `need(groups)`; the seat
+// table; and LAST the zeroing launch, which also books the launch's workgroup-tiles as expected in the caller's status block
+// (the proof of work, coop_zero_kernel).  A launch that has booked must run: every refusal of a call comes before this
+// function, or the next Workspaces.check() reports a shortfall that blames launches that did nothing wrong.
+template <typename Need>
+inline int coop_begin(const char* who, int n_nets, int32_t rows, Need need, int expected_word, const CoopOpts& opts,
+                      void* workspace, int64_t workspace_bytes, hipStream_t s, CoopLaunch& L) {
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot query the device", who);
+    L.n_tiles = (rows + COOP_ROWS - 1) / COOP_ROWS;
+    // groups per XCD: every workgroup must be resident at once (one per CU), grid = 8 * G * gpx
+    L.gpx = n_cu / (8 * COOP_G);
+    if (L.gpx > 8) L.gpx = 8;
+    while (L.gpx > 1 && (L.gpx - 1) * 8 >= n_nets * L.n_tiles) --L.gpx;
+    // coop_place assumes 8 XCDs with workgroup ids dealt round-robin over them (MI355X in SPX mode: 256 CUs); a partitioned
+    // device (CPX / DPX / QPX: fewer XCDs) would never finish staffing
+    if (L.gpx < 1 || n_cu < 256)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: device has %d CUs, the cooperative form is built for 8 XCDs x 32 CUs", who, n_cu);
+    L.groups = L.gpx * 8;
+    if (L.groups < n_nets) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d groups for %d nets", who, L.groups, n_nets);
+    L.groups_per_net = L.groups / n_nets;
+    const int64_t bytes = need(L.groups);
+    if (!workspace || workspace_bytes < bytes || !gnnpn_aligned(workspace, 256))
+        GNNPN_FAIL(GNNPN_E_ARG, "%s: workspace of %lld B (256-B aligned) required", who, (long long)bytes);
+    L.seats = gnnpn_cu_seat_table();
+    if (!L.seats) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot allocate the seat table", who);
+    // zero the status area and every tag before each launch (tags start at 1).  Test hook (lstm_ablate bit 13, tests only): leave
+    // the workspace as the previous launch left it — every workgroup must then notice (status code 8) instead of running on it
+    const unsigned units = (unsigned)(COOP_G * n_nets * L.n_tiles);
+    if (coop_zero_workspace(workspace, (size_t)bytes, s, opts.sticky, expected_word, units, (gnnpn_option_lstm_ablate() & 0x2000) != 0) !=
+        hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: workspace memset failed", who);
+    g_gnnpn_last_units = opts.sticky ? (int64_t)units : 0;
+    L.status = static_cast<unsigned*>(workspace);
+    L.buffers = static_cast<char*>(workspace) + COOP_STATUS_BYTES;
+    return GNNPN_OK;
+}
+
+// Workspace of a cooperative decoder launch (decode_coop.hip, decode_lean.hip): the status area, the h granules (2 parities x
+// 16 rows x 256 units per group), the partial-dot granules (2 parities x `xp_granules` per group), the Low net's window logits
+// (16 rows x K per tile and step), and COOP_OVERREAD_BYTES of slack for the fixed-shape sweeps.
+struct DecodeWorkspace {
+    int64_t h_bytes, p_bytes, l_bytes;
+    int64_t total() const { return COOP_STATUS_BYTES + h_bytes + p_bytes + l_bytes + COOP_OVERREAD_BYTES; }
+};
+inline DecodeWorkspace decode_workspace(int64_t groups, int64_t rows, int32_t T, int32_t K, int64_t xp_granules) {
+    const int64_t tiles = (rows + COOP_ROWS - 1) / COOP_ROWS;
+    return {groups * 2 * COOP_ROWS * COOP_H * 8, groups * 2 * xp_granules * 8, tiles * T * COOP_ROWS * (int64_t)K * 8};
 }
 // one thread of a seated workgroup, when it leaves the kernel: the tiles it took to the end (an aborted tile is not one)
 __device__ __forceinline__ void coop_note_finished(unsigned* sticky, int word, unsigned tiles_done) {
@@ -748,25 +755,12 @@ __device__ __forceinline__ void split_chain(const _Float16* base, const f16x8 (&
             acc[n][r] = __fmul_rn(fmaf(fmaf(a2[n][r], SPLIT_INV, a1[n][r]), SPLIT_INV, __fadd_rn(a0[n][r], a0b[n][r])), inv[n]);
 }
 
-// LSTM cell update for the [i | f] / [g | o] tile pair: lanes c < 8 hold (i, g), lanes c >= 8 hold
-// (f, o) of the same hidden unit; one DPP swap per value, then both halves update (c, h) alike.
-// Same arithmetic as lstm_cell_update (recurrent.h): cy = f*c + i*g ; hy = o*tanh(cy), products and
-// sum rounded separately.
-// two problem rows at once (packed arithmetic, see cell_act2)
-__device__ __forceinline__ void cell_update_pair2(f32x2 g0, f32x2 g1, bool lo_half, f32x2& cst, f32x2& h) {
-    const f32x2 a0 = cell_act2(g0, false);
-    const f32x2 a1 = cell_act2(g1, lo_half);
-    const f32x2 p0 = {swap8(a0.x), swap8(a0.y)}, p1 = {swap8(a1.x), swap8(a1.y)};
-    const f32x2 ig = lo_half ? a0 : p0, gg = lo_half ? a1 : p1;
-    const f32x2 fg = lo_half ? p0 : a0, og = lo_half ? p1 : a1;
-    cst = fg * cst + ig * gg;          // -ffp-contract=off: two rounded products, one rounded sum
-    h = og * cell_act2(cst, true);
-}
-// The same cell update without the duplicated half: of a lane's four rows the lower half-row (lanes c < 8, holding i and g)
-// finishes rows 0,1 and the upper one (c >= 8, holding f and o) rows 2,3.  g0 / g1: the lane's gate pre-activations of
-// rows 0..3 as two packed pairs each.  One DPP exchange per value: a lane sends the gate pair of the rows its PARTNER
-// finishes and receives the partner's gates of its own rows.  Element for element the arithmetic of cell_update_pair2 —
-// five packed activations per step instead of six, two state registers per lane instead of four.
+// LSTM cell update for the [i | f] / [g | o] tile pair: lanes c < 8 hold (i, g), lanes c >= 8 hold (f, o) of the same hidden
+// unit.  Of a lane's four rows the lower half-row (c < 8) finishes rows 0,1 and the upper one (c >= 8) rows 2,3.  g0 / g1: the
+// lane's gate pre-activations of rows 0..3 as two packed pairs each (packed arithmetic, see cell_act2).  One DPP exchange per
+// value: a lane sends the gate pair of the rows its PARTNER finishes and receives the partner's gates of its own rows.  Same
+// arithmetic as lstm_cell_update (recurrent.h): cy = f*c + i*g ; hy = o*tanh(cy), products and sum rounded separately
+// (-ffp-contract=off).
 __device__ __forceinline__ void cell_update_split(const f32x2 (&g0)[2], const f32x2 (&g1)[2], bool lo_half, f32x2& cst, f32x2& h) {
     f32x2 a0[2], a1[2];
 #pragma unroll
@@ -780,13 +774,4 @@ __device__ __forceinline__ void cell_update_split(const f32x2 (&g0)[2], const f3
     const f32x2 fg = lo_half ? t0 : a0[1], og = lo_half ? t1 : a1[1];
     cst = fg * cst + ig * gg;
     h = og * cell_act2(cst, true);
-}
-__device__ __forceinline__ void cell_update_pair(float g0, float g1, bool lo_half, float& cst, float& h) {
-    const float a0 = cell_act(g0, false);            // sigmoid(i) | sigmoid(f)
-    const float a1 = cell_act(g1, lo_half);          // tanh(g)    | sigmoid(o)
-    const float p0 = swap8(a0), p1 = swap8(a1);
-    const float ig = lo_half ? a0 : p0, gg = lo_half ? a1 : p1;
-    const float fg = lo_half ? p0 : a0, og = lo_half ? p1 : a1;
-    cst = __fadd_rn(__fmul_rn(fg, cst), __fmul_rn(ig, gg));
-    h = __fmul_rn(og, cell_act(cst, true));
 }

@@ -30,9 +30,9 @@
 #include "lstm_shared.h"
 
 namespace {
-constexpr int H = 256;
-constexpr int G = 8;
-constexpr int ROWS = 16;
+constexpr int H = COOP_H;
+constexpr int G = COOP_G;
+constexpr int ROWS = COOP_ROWS;
 constexpr int UNITS = H / G;      // 32
 constexpr int LDH = 258;
 constexpr int KMAX = 16;          // candidates per category the cooperative form is built for
@@ -71,20 +71,20 @@ __device__ __forceinline__ int ror16(int v, int n) {
     }
 }
 
-// DIAG: diagnostic build with phase stamps (tools/stamp_decode.py); production carries none of it.
-// SPLIT: W_hh.h from exact three-piece fp16 operands (coop_common.h); everything else as in the fp32 form
-// OCC: workgroups per CU the build is sized for — 1 (512 registers: fastest alone) or 2 (256 registers: shares the
-// CU with a workgroup of another launch, pipeline.PipelinedRunner)
-// SAMPLE: the build that can draw the pick from the window softmax (gnnpn_decode_net_t.sample); the greedy builds carry
+// The fp32 arithmetic, one workgroup per CU (512 registers); the exact-split product and the 2-per-CU builds are those of
+// decode_lean.hip.
+// FOLDX: the folded input side (net.xw_fold); otherwise the literal two-stage one (embedding2, then W_ih).
+// SAMPLE: the build that can draw the pick from the window softmax (gnnpn_decode_net_t.sample); the greedy build carries
 // none of that code.  Only this build reads `rep` (sampled replicas, decode_shared.h: row -> problem indirection)
-template <bool FOLDX, bool DIAG, bool SPLIT, int OCC, int EVH_ = (OCC == 2 ? 2 : 1), bool SAMPLE = false>
-__global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArgs a, u64* __restrict__ xh,
-                                                                     u64* __restrict__ xp, u64* __restrict__ xl,
-                                                                     unsigned* __restrict__ err, unsigned* __restrict__ sticky,
-                                                                     int n_nets, int groups_per_net, int gpx, int ablate_arg, unsigned* __restrict__ seats,
-                                                                     ReplicaMap rep) {
-    const int ablate = DIAG ? ablate_arg : (ablate_arg & 128);
-    __shared__ __attribute__((aligned(16))) float hs[SPLIT ? 3 * SPLIT_TILE / 2 : ROWS * LDH16];   // fp32 tile (k-quarter-major, stride LDT) | three fp16 piece tiles (stride LDH16 halfs)
+// write_through: 128 — the hand-off granules are written through to the device's coherence point instead of staying in the
+// group's L2 (gnnpn_launch_opts_t.write_through).
+template <bool FOLDX, bool SAMPLE>
+__global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs a, u64* __restrict__ xh,
+                                                                   u64* __restrict__ xp, u64* __restrict__ xl,
+                                                                   unsigned* __restrict__ err, unsigned* __restrict__ sticky,
+                                                                   int n_nets, int groups_per_net, int gpx, int write_through, unsigned* __restrict__ seats,
+                                                                   ReplicaMap rep) {
+    __shared__ __attribute__((aligned(16))) float hs[ROWS * LDH16];   // fp32 tile, k-quarter-major with stride LDT (ROWS * LDT floats used)
     __shared__ float xs[FOLDX ? 1 : ROWS * LDH];
     __shared__ __attribute__((aligned(16))) float hsl[ROWS][UNITS + 4];
     __shared__ __attribute__((aligned(16))) float part_lin[4][G * 4 * KMAX];   // per wave: the partial dots of its 4 rows, [row%4][cand][member]
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
     const DecodeNet& net = a.net[net_id];
     if (tid == 0) abort_flag = 0;
     __syncthreads();
-    const bool same_xcd = !(ablate & 128);   // h and partial-dot granules stay inside the group's XCD
+    const bool same_xcd = !(write_through & 128);   // h and partial-dot granules stay inside the group's XCD
     if (tid == 0 && same_xcd) atomicAdd(err + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics: workgroups on the same-XCD fast path (per XCD: its own line)
 
     const int B = a.B, T = a.T, K = a.K, L = T * K;
@@ -123,25 +123,13 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
     int wrow[2];
     wrow[0] = (0 + (c >> 3)) * H + unit;
     wrow[1] = (2 + (c >> 3)) * H + unit;
-    float wBh[SPLIT ? 1 : 2][SPLIT ? 1 : 64], wBx[FOLDX ? 1 : 2][FOLDX ? 1 : 64], bh[2], bi[2], wXf[2][2], sg[2];
-    f16x8 wH16[SPLIT ? 2 : 1][8], wL16[SPLIT ? 2 : 1][8];   // exact split: pieces 0 and 1 (piece 2: LDS bytes, coop_common.h)
-    float winv[2] = {1.0f, 1.0f};
-    __shared__ __attribute__((aligned(16))) unsigned wts[SPLIT ? SPLIT_WT_DWORDS : 4];
-    unsigned* wt_lane = wts + (SPLIT ? (wave * 8 * 64 + lane) * 4 : 0);
-    const uint4* __restrict__ Wsplit = SPLIT ? static_cast<const uint4*>(net.whh_split) : nullptr;   // uniform: packed once per model, or split here
-    if constexpr (SPLIT) {
-        if (Wsplit) load_split_weights(Wsplit + (size_t)member * SPLIT_PACK_U4_PER_MEMBER, tid, wH16, wL16, wt_lane, winv);
-    }
+    float wBh[2][64], wBx[FOLDX ? 1 : 2][FOLDX ? 1 : 64], bh[2], bi[2], wXf[2][2], sg[2];
 #pragma unroll
     for (int tl = 0; tl < 2; ++tl) {
         const int gate = wrow[tl] / H, u = wrow[tl] % H;
         bh[tl] = net.bhh[wrow[tl]];
-        if constexpr (SPLIT) {
-            if (!Wsplit) winv[tl] = split_weights<H>(net.whh, gate, u, kq, wH16[tl], wL16[tl], wt_lane + 2 * tl);
-        } else {
 #pragma unroll
-            for (int kk = 0; kk < 64; ++kk) wBh[tl][kk] = net.whh[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
-        }
+        for (int kk = 0; kk < 64; ++kk) wBh[tl][kk] = net.whh[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
         if constexpr (FOLDX) {   // B-fragments of (W_ih W_e) [4H,8], its bias, and the step-0 gates W_ih.start + b_ih
             wXf[tl][0] = net.xw_fold[wrow[tl] * 8 + kq];
             wXf[tl][1] = net.xw_fold[wrow[tl] * 8 + 4 + kq];
@@ -176,8 +164,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
         __syncthreads();   // previous tile is completely done with the LDS arrays
         for (int j = 0; j < ROWS; ++j) {
             const float h0v = (b0 + j < B) ? net.h0[(int64_t)prob_of(b0 + j) * H + tid] : 0.0f;
-            if constexpr (SPLIT) split_store(reinterpret_cast<_Float16*>(hs) + j * LDH16 + tid, h0v);
-            else hs[ht_index(j, tid)] = h0v;
+            hs[ht_index(j, tid)] = h0v;
             if (!FOLDX) xs[j * LDH + tid] = net.start[tid];
         }
         __syncthreads();
@@ -185,9 +172,6 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
         for (int k = 0; k <= T; ++k) {
             float4 xg[4];
             float xraw = 0.0f, axf[2] = {0.f, 0.f};
-            const bool stamps = DIAG && (ablate & 32);
-            u64 st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (stamps) st[0] = phase_stamp();
             if (k > 0) {
                 // ---- hand-off of publish #(step-1): h_{k-1}, partial dots, Low's window logits — ONE
                 // combined sweep (all loads issued, then all tags checked): one round trip, not three
@@ -199,30 +183,24 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                     const u64* src_l = xl + ((size_t)tile * T + (k - 1)) * ROWS * K + wave * 4 * K;
                     const int n_p = G * 4 * K;            // this wave's rows 4w..4w+3 from all members
                     const int n_l = 4 * K;
-                    constexpr int NPJ = EVH_ == 2 ? 4 : 8;   // partial-dot granules per lane: G*4*K / 64, K <= 8 in the EVH_ = 2 builds
-                    constexpr int NPJ2 = NPJ / 2;            // 16-byte loads: two adjacent granules each (coop_common.h)
+                    constexpr int NPJ2 = 4;                  // 16-byte loads of two partial-dot granules per lane: G*4*K / 64 <= 8 granules (coop_common.h)
                     u32x4 vh[8], vp[NPJ2];
                     unsigned vl = 0;
                     bool ok = false;
                     for (unsigned spins = 0; spins <= SPIN_LIMIT; ++spins) {
                         bool good = true;
-                        // pairs of this lane beyond n_p (K < 8 / K < 16) are loaded and never looked at: they lie at most
+                        // pairs of this lane beyond n_p (K < 16) are loaded and never looked at: they lie at most
                         // 4 KB past this wave's segment, inside the workspace (COOP_OVERREAD_BYTES of slack at its end)
                         if (latent_in_launch) {   // Low's window logits ride the same statement (one round trip, not two)
                             u64 x;
-                            if constexpr (NPJ2 == 2) granule_load2_x8_x2_lat(vh, vp, x, uniform_ptr(src_h), uniform_ptr(src_p), uniform_ptr(src_l), 16u * lane);
-                            else granule_load2_x8_x4_lat(vh, vp, x, uniform_ptr(src_h), uniform_ptr(src_p), uniform_ptr(src_l), 16u * lane);
+                            granule_load2_x8_x4_lat(vh, vp, x, uniform_ptr(src_h), uniform_ptr(src_p), uniform_ptr(src_l), 16u * lane);
                             vl = (unsigned)x;
                             good &= (lane >= n_l) | ((unsigned)(x >> 32) == 1u);
                         } else {
-                            if constexpr (NPJ2 == 2) granule_load2_x8_x2(vh, vp, uniform_ptr(src_h), uniform_ptr(src_p), 16u * lane);
-                            else granule_load2_x8_x4(vh, vp, uniform_ptr(src_h), uniform_ptr(src_p), 16u * lane);
+                            granule_load2_x8_x4(vh, vp, uniform_ptr(src_h), uniform_ptr(src_p), 16u * lane);
                         }
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            if constexpr (SPLIT) good &= split_pair_tagged(vh[j], tag);
-                            else good &= (vh[j].y == tag) & (vh[j].w == tag);
-                        }
+                        for (int j = 0; j < 8; ++j) good &= (vh[j].y == tag) & (vh[j].w == tag);
 #pragma unroll
                         for (int j = 0; j < NPJ2; ++j)
                             if (2 * (lane + 64 * j) < n_p) good &= (vp[j].y == tag) & (vp[j].w == tag);
@@ -236,13 +214,9 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const int i = 2 * (j * 64 + lane);          // even: i and i + 1 share a row
-                        if constexpr (SPLIT) {
-                            split_pair_to_lds(reinterpret_cast<_Float16*>(hs) + (wave * 4 + (i >> 8)) * LDH16 + (i & 255), vh[j]);
-                        } else {
-                            float* d = &hs[ht_index(wave * 4 + (i >> 8), i & 255)];   // units i, i+1: 64 floats apart
-                            d[0] = __uint_as_float(vh[j].x);
-                            d[64] = __uint_as_float(vh[j].z);
-                        }
+                        float* d = &hs[ht_index(wave * 4 + (i >> 8), i & 255)];   // units i, i+1: 64 floats apart
+                        d[0] = __uint_as_float(vh[j].x);
+                        d[64] = __uint_as_float(vh[j].z);
                     }
 #pragma unroll
                     for (int j = 0; j < NPJ2; ++j) {
@@ -261,7 +235,6 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                         lat[wave * 4 + lane / K][lane % K] = lv;
                     }
                 }
-                if (stamps) st[1] = phase_stamp();
 
                 // ---- logits, softmax and first-max argmax inside the wave: wave w owns rows 4w..4w+3,
                 // 16 lanes per row, lane = candidate (K <= 16).  Row-wide max / sum by DPP rotations.
@@ -366,7 +339,6 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                     }
                     break;
                 }
-                if (stamps) st[2] = phase_stamp();
                 // decoder input of step k, in flight under the W_hh.h MFMAs
                 if constexpr (FOLDX) {
                 } else if (net.embedded) {
@@ -383,15 +355,13 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
             }
 
             // this step's window rows, own 32-unit slice: thread (row, cand) holds 32 floats
-            // (OCC == 2: two threads per (row, cand), 16 floats each — half the registers; K <= 8 there)
-            constexpr int EVH = EVH_, EVN = 8 / EVH;   // EVH = 2 needs 2*16*K <= 256 threads, i.e. K <= 8
+            constexpr int EVN = 8;
             float4 ev[EVN];
-            const int ppair = tid / EVH, phalf = tid - ppair * EVH;
-            const int prow = ppair / K, pcand = ppair - prow * K;
-            const bool pdot = ppair < ROWS * K;
+            const int prow = tid / K, pcand = tid - prow * K;
+            const bool pdot = tid < ROWS * K;
             if (pdot) {
                 const int b = b0 + prow;
-                const float* src = net.enc_out + ((int64_t)prob_of(b) * L + (int64_t)k * K + pcand) * H + member * UNITS + phalf * (4 * EVN);
+                const float* src = net.enc_out + ((int64_t)prob_of(b) * L + (int64_t)k * K + pcand) * H + member * UNITS;
 #pragma unroll
                 for (int j = 0; j < EVN; ++j)
                     ev[j] = b < B ? *reinterpret_cast<const float4*>(src + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -399,18 +369,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
 
             // ---- decoder LSTM cell: W_hh.h and the input side as independent fma chains per gate column
             f32x4 ah0 = {0.f, 0.f, 0.f, 0.f}, ah1 = ah0, ax0 = ah0, ax1 = ah0;
-            if constexpr (SPLIT) {
-                f32x4 acc[2] = {ah0, ah1};
-                split_chain(reinterpret_cast<const _Float16*>(hs) + c * LDH16 + 8 * kq, wH16, wL16, wt_lane, winv, acc);
-                ah0 = acc[0];
-                ah1 = acc[1];
-            } else {
-                mfma_chain_pair<LDT, OCC == 2 ? 8 : 16, true>(hs, c, kq, wBh[0], wBh[SPLIT ? 0 : 1], ah0, ah1);
-            }
-            if (stamps) {
-                asm volatile("" ::"v"(ah0[0]), "v"(ah1[0]));
-                st[3] = phase_stamp();
-            }
+            mfma_chain_pair<LDT, 16, true>(hs, c, kq, wBh[0], wBh[1], ah0, ah1);
             float gx[2][4];
             if constexpr (FOLDX) {
                 if (k > 0) {
@@ -424,7 +383,6 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                         act[4 + kq] = axf[1];
                     }
                 }
-                if (stamps) st[4] = st[5] = phase_stamp();
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     gx[0][r] = k > 0 ? __fadd_rn(ax0[r], bi[0]) : sg[0];
@@ -454,12 +412,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                     }
                     __syncthreads();
                 }
-                if (stamps) st[4] = phase_stamp();
                 mfma_chain_pair<LDH>(xs, c, kq, wBx[0], wBx[1], ax0, ax1);
-                if (stamps) {
-                    asm volatile("" ::"v"(ax0[0]), "v"(ax1[0]));
-                    st[5] = phase_stamp();
-                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     gx[0][r] = __fadd_rn(ax0[r], bi[0]);
@@ -478,10 +431,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
             }
             {
                 u64* dst = out_h + own0 * H + unit;
-                if constexpr (SPLIT) {
-                    split_granule_store(dst, step + 1, hl.x, same_xcd);
-                    split_granule_store(dst + H, step + 1, hl.y, same_xcd);
-                } else if (same_xcd) {
+                if (same_xcd) {
                     granule_store_l2(dst, step + 1, hl.x);
                     granule_store_l2(dst + H, step + 1, hl.y);
                 } else {
@@ -495,10 +445,6 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                     if (b0 + own0 + 1 < B) net.queries[((int64_t)(b0 + own0 + 1) * T + k) * H + unit] = hl.y;
                 }
             }
-            if (stamps) {
-                asm volatile("" ::"v"(hl.y));
-                st[6] = phase_stamp();
-            }
             __syncthreads();
             // ---- partial attention dots of the step-k window against the own h_k slice
             {
@@ -506,31 +452,15 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
                 if (pdot) {
 #pragma unroll
                     for (int j = 0; j < EVN; ++j) {
-                        const float4 hv = *reinterpret_cast<const float4*>(&hsl[prow][phalf * (4 * EVN) + 4 * j]);
+                        const float4 hv = *reinterpret_cast<const float4*>(&hsl[prow][4 * j]);
                         p = fmaf(ev[j].x, hv.x, p);
                         p = fmaf(ev[j].y, hv.y, p);
                         p = fmaf(ev[j].z, hv.z, p);
                         p = fmaf(ev[j].w, hv.w, p);
                     }
                 }
-                if constexpr (EVH == 2)   // lanes 2p, 2p+1 hold the two halves of the slice: low half + high half
-                    p = __fadd_rn(p, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, false)));
-                if (pdot && phalf == 0)
+                if (pdot)
                     granule_publish(xp_g + (step & 1) * (G * ROWS * K) + ((size_t)prow * K + pcand) * G + member, step + 1, p, same_xcd);
-            }
-            if (stamps) {
-                st[7] = phase_stamp();
-                if (blockIdx.x == 0 && tid == 0 && k > 0) {
-                    u64* prof = reinterpret_cast<u64*>(err) + 4;
-                    prof[0] += st[1] - st[0];   // combined sweep + LDS fill
-                    prof[1] += st[2] - st[1];   // barrier, logits+argmax, barrier, actions
-                    prof[2] += st[3] - st[2];   // gathers issue + W_hh.h MFMAs
-                    prof[3] += st[4] - st[3];   // input side: folded MFMAs | x embedding into LDS
-                    prof[4] += st[5] - st[4];   // W_ih.x MFMAs (unfolded only)
-                    prof[5] += st[6] - st[5];   // cell + publish h
-                    prof[6] += st[7] - st[6];   // barrier + partial dots + publish
-                    prof[7] += 1;
-                }
             }
             ++step;
         }
@@ -546,12 +476,13 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_coop_kernel(DecodeArg
     }
 }
 
-// what this file's launches need at most for `rows` rows (no device call: argument checks use it before any launch)
-int64_t gnnpn_decode_coop_workspace_need(int64_t rows, int32_t T, int32_t n_per) {
-    const int64_t groups = 64, tiles = (rows + ROWS - 1) / ROWS;
-    return COOP_STATUS_BYTES + groups * 2 * ROWS * H * 8 + groups * 2 * G * ROWS * (int64_t)n_per * 8 +
-           tiles * T * ROWS * (int64_t)n_per * 8 + COOP_OVERREAD_BYTES;
+// this file's workspace (coop_common.h: decode_workspace): the partial dots of the K candidates of every row from every member
+static DecodeWorkspace coop_workspace(int64_t groups, int64_t rows, int32_t T, int32_t K) {
+    return decode_workspace(groups, rows, T, K, (int64_t)G * ROWS * K);
 }
+
+// what this file's launches need at most for `rows` rows (no device call: argument checks use it before any launch)
+int64_t gnnpn_decode_coop_workspace_need(int64_t rows, int32_t T, int32_t n_per) { return coop_workspace(64, rows, T, n_per).total(); }
 
 extern "C" int64_t gnnpn_pointer_decode_workspace_bytes(int32_t B, int32_t T, int32_t n_per) {
     (void)gnnpn_cu_seat_table();   // callers size their workspace before the first launch and outside any capture: create the seat table here
@@ -583,65 +514,37 @@ bool gnnpn_decode_coop_supported(int32_t H_, int32_t n_per) { return H_ == H && 
 
 int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
                              void* workspace, int64_t workspace_bytes, hipStream_t s, ReplicaMap rep) {
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode: cannot query the device");
     bool fold = args.net[0].xw_fold != nullptr;
     for (int n = 0; n < n_nets; ++n)
         if ((args.net[n].xw_fold != nullptr) != fold)
             GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: all nets of a call must use the same input-side form");
-    {   // the shipped configuration (folded input side, greedy picks) runs on the production build, decode_lean.hip; this file
-        // keeps the two builds that one does not cover: the literal two-stage input side and the sampling decoder
-        bool any_sample0 = false;
-        for (int n = 0; n < n_nets; ++n) any_sample0 |= args.net[n].sample != 0;
-        if (rep.R > 0 && (n_nets != 1 || !any_sample0))
-            GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: sampled replicas are one sampling net per call");
-        if (fold && !any_sample0 && args.K <= 16)
-            return gnnpn_launch_decode_lean(args, n_nets, precision, shared_cu, opts, workspace, workspace_bytes, s);
-    }
-    const int n_tiles = (args.B + ROWS - 1) / ROWS;
-    int gpx = n_cu / (8 * G);
-    if (gpx > 8) gpx = 8;
-    while (gpx > 1 && (gpx - 1) * 8 >= n_nets * n_tiles) --gpx;
-    // coop_place assumes 8 XCDs with workgroup ids dealt round-robin over them (MI355X in SPX mode: 256 CUs); a partitioned
-    // device (CPX / DPX / QPX: fewer XCDs) would never finish staffing
-    if (gpx < 1 || n_cu < 256) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: device has %d CUs, the cooperative form is built for 8 XCDs x 32 CUs", n_cu);
-    const int groups = gpx * 8;
-    if (groups < n_nets) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: %d groups for %d nets", groups, n_nets);
-    const int groups_per_net = groups / n_nets;
-    const int64_t h_bytes = (int64_t)groups * 2 * ROWS * H * 8;
-    const int64_t p_bytes = (int64_t)groups * 2 * G * ROWS * args.K * 8;
-    const int64_t l_bytes = (int64_t)n_tiles * args.T * ROWS * args.K * 8;
-    const int64_t need = COOP_STATUS_BYTES + h_bytes + p_bytes + l_bytes + COOP_OVERREAD_BYTES;
-    if (!workspace || workspace_bytes < need || !gnnpn_aligned(workspace, 256))
-        GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: workspace of %lld B (256-B aligned) required", (long long)need);
-    if (coop_zero_workspace(workspace, (size_t)need, s, opts.sticky, GNNPN_STATUS_DEC_EXPECTED, (unsigned)(G * n_nets * n_tiles),
-                            (gnnpn_option_lstm_ablate() & 0x2000) != 0) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode: workspace memset failed");
-    g_gnnpn_last_units = opts.sticky ? (int64_t)G * n_nets * n_tiles : 0;
-    unsigned* p_seats = gnnpn_cu_seat_table();
-    if (!p_seats) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot allocate the seat table", "pointer_decode");
-    char* base = static_cast<char*>(workspace);
-    u64* p_h = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES);
-    u64* p_p = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES + h_bytes);
-    u64* p_l = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES + h_bytes + p_bytes);
-    unsigned* p_err = reinterpret_cast<unsigned*>(base);
-    const int abl = opts.write_through ? 128 : 0;
-    unsigned* p_s = opts.sticky;
+    bool any_sample = false;
+    for (int n = 0; n < n_nets; ++n) any_sample |= args.net[n].sample != 0;
+    if (rep.R > 0 && (n_nets != 1 || !any_sample))
+        GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: sampled replicas are one sampling net per call");
+    // the shipped configuration (folded input side, greedy picks) runs on the production build, decode_lean.hip; this file
+    // keeps the two builds that one does not cover: the literal two-stage input side and the sampling decoder
+    if (fold && !any_sample && args.K <= 16)
+        return gnnpn_launch_decode_lean(args, n_nets, precision, shared_cu, opts, workspace, workspace_bytes, s);
     if (precision == GNNPN_PREC_SPLIT)
         GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the exact-split arithmetic is built for the folded input side with greedy picks (decode_lean.hip)");
     if (shared_cu)
         GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the 2-per-CU build exists for the folded input side with greedy picks only");
-    const int lds_kb = opts.lds_kb;
-    bool any_sample = false;
-    for (int n = 0; n < n_nets; ++n) any_sample |= args.net[n].sample != 0;
     if (any_sample && !fold)
         GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the sampling build exists for the folded fp32 input side only");
-#define GNNPN_DEC8(FOLD_, SAMPLE_)                                                                                                       \
-    hipLaunchKernelGGL((pointer_decode_coop_kernel<FOLD_, false, false, 1, 1, SAMPLE_>), dim3(COOP_OVERSUB * groups * G), dim3(256),          \
-                       coop_lds_padding((const void*)pointer_decode_coop_kernel<FOLD_, false, false, 1, 1, SAMPLE_>, lds_kb), s, args, p_h, \
-                       p_p, p_l, p_err, p_s, n_nets, groups_per_net, gpx, abl, p_seats, rep)
+    CoopLaunch c;
+    const auto need = [&](int groups) { return coop_workspace(groups, args.B, args.T, args.K).total(); };
+    if (const int rc = coop_begin("pointer_decode", n_nets, args.B, need, GNNPN_STATUS_DEC_EXPECTED, opts, workspace, workspace_bytes, s, c))
+        return rc;
+    const DecodeWorkspace w = coop_workspace(c.groups, args.B, args.T, args.K);
+    u64* p_h = reinterpret_cast<u64*>(c.buffers);
+    u64* p_p = reinterpret_cast<u64*>(c.buffers + w.h_bytes);
+    u64* p_l = reinterpret_cast<u64*>(c.buffers + w.h_bytes + w.p_bytes);
+    const int wt = opts.write_through ? 128 : 0;
+#define GNNPN_DEC8(FOLD_, SAMPLE_)                                                                                                  \
+    hipLaunchKernelGGL((pointer_decode_coop_kernel<FOLD_, SAMPLE_>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),                      \
+                       gnnpn_lds_padding((const void*)pointer_decode_coop_kernel<FOLD_, SAMPLE_>, opts.lds_kb), s, args, p_h, p_p, p_l, \
+                       c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, wt, c.seats, rep)
     if (any_sample) GNNPN_DEC8(true, true);       // folded input side, every pick drawn from the window softmax
     else GNNPN_DEC8(false, false);                // the literal two-stage input side (embedding2, then W_ih), greedy
 #undef GNNPN_DEC8

@@ -1,6 +1,6 @@
 // Greedy pointer decode, cooperative form — the production build (round 3): folded input side, greedy picks, both pointer
 // networks in ONE launch.  Replaces /root/reference/src/models/modelPN.py:204-239 (the decode loop) for the shipped
-// configuration; decode_coop.hip keeps the general builds (literal two-stage input side, sampling, diagnostics).
+// configuration; decode_coop.hip keeps the general builds (literal two-stage input side, sampling, best-of-N replicas).
 //
 // Same ownership, hand-off protocol and ARITHMETIC as decode_coop.hip (read its header): a group of 8 workgroups owns a
 // tile of 16 problems, member m keeps W_hh of hidden units [32m, 32m+32) in registers, one exchange per step carries
@@ -9,7 +9,7 @@
 //
 //  * every global access is a buffer instruction: a 128-bit resource in SGPRs + ONE 32-bit lane offset per stream (constant
 //    for the whole launch) + a scalar step offset — no 64-bit vector address arithmetic, no spilled row pointers (the
-//    2-per-CU build of decode_coop.hip carried 96-180 B of scratch and 33 64-bit adds per step).  The hand-off sweeps are
+//    2-per-CU build of decode_coop.hip, since removed, carried 96-180 B of scratch and 33 64-bit adds per step).  The hand-off sweeps are
 //    ordinary (compiler-visible) `buffer_load_dwordx4 ... sc1`: the compiler tracks their completion itself.  Rows past the
 //    end of the batch are "out of range" of the resource and read as zero: no clamping code.
 //  * the partial dots land in the lane that owns (row, candidate): the exchange buffer is [row][16 candidates][8 members],
@@ -28,11 +28,11 @@
 #include "lstm_shared.h"
 
 namespace {
-constexpr int H = 256;
-constexpr int G = 8;
-constexpr int ROWS = 16;
+constexpr int H = COOP_H;
+constexpr int G = COOP_G;
+constexpr int ROWS = COOP_ROWS;
 constexpr int UNITS = H / G;      // 32
-constexpr int KW = 16;            // candidate slots per row in the exchange buffer (n_per <= 16)
+constexpr int KW = 16;           // candidate slots per row in the exchange buffer (n_per <= 16)
 constexpr unsigned SPIN_LIMIT = 400000;
 constexpr int XP_GRANULES = ROWS * KW * G;   // partial-dot granules per parity buffer
 
@@ -549,59 +549,39 @@ __global__ __launch_bounds__(256) void pick_prob_kernel(PickProbArgs a, int64_t 
     out[row] = 1.0f / v[0];
 }
 
-int64_t gnnpn_decode_lean_workspace_bytes(int32_t B, int32_t T, int32_t n_per) {
-    const int64_t groups = 64, tiles = (B + ROWS - 1) / ROWS;
-    return COOP_STATUS_BYTES + groups * 2 * ROWS * H * 8 + groups * 2 * XP_GRANULES * 8 + tiles * T * ROWS * (int64_t)n_per * 8 +
-           COOP_OVERREAD_BYTES;
+// this file's workspace (coop_common.h: decode_workspace): partial-dot slots for KW candidates of every row from every member
+static DecodeWorkspace lean_workspace(int64_t groups, int64_t rows, int32_t T, int32_t K) {
+    return decode_workspace(groups, rows, T, K, XP_GRANULES);
 }
+
+int64_t gnnpn_decode_lean_workspace_bytes(int32_t B, int32_t T, int32_t n_per) { return lean_workspace(64, B, T, n_per).total(); }
 
 // folded, greedy nets only (the caller checked); shared_cu: the 256-register build (two workgroups per CU)
 int gnnpn_launch_decode_lean(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
                              void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode: cannot query the device");
     if (args.K > KW) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the cooperative form is built for n_per <= %d", KW);
-    const int n_tiles = (args.B + ROWS - 1) / ROWS;
-    int gpx = n_cu / (8 * G);
-    if (gpx > 8) gpx = 8;
-    while (gpx > 1 && (gpx - 1) * 8 >= n_nets * n_tiles) --gpx;
-    if (gpx < 1 || n_cu < 256) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: device has %d CUs, the cooperative form is built for 8 XCDs x 32 CUs", n_cu);
-    const int groups = gpx * 8;
-    if (groups < n_nets) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: %d groups for %d nets", groups, n_nets);
-    const int groups_per_net = groups / n_nets;
     // the tile-relative 32-bit offsets of the buffer resources
     if ((int64_t)ROWS * args.T * args.K * H * 4 >= (1ll << 32) || (int64_t)args.T * ROWS * args.K * 8 >= (1ll << 32))
         GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: a tile of 16 problems must stay below 4 GB of encoder output");
-    const int64_t h_bytes = (int64_t)groups * 2 * ROWS * H * 8;
-    const int64_t p_bytes = (int64_t)groups * 2 * XP_GRANULES * 8;
-    const int64_t l_bytes = (int64_t)n_tiles * args.T * ROWS * args.K * 8;
-    const int64_t need = COOP_STATUS_BYTES + h_bytes + p_bytes + l_bytes + COOP_OVERREAD_BYTES;
-    if (!workspace || workspace_bytes < need || !gnnpn_aligned(workspace, 256))
-        GNNPN_FAIL(GNNPN_E_ARG, "pointer_decode: workspace of %lld B (256-B aligned) required", (long long)need);
-    if (coop_zero_workspace(workspace, (size_t)need, s, opts.sticky, GNNPN_STATUS_DEC_EXPECTED, (unsigned)(G * n_nets * n_tiles),
-                            (gnnpn_option_lstm_ablate() & 0x2000) != 0) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode: workspace memset failed");
-    g_gnnpn_last_units = opts.sticky ? (int64_t)G * n_nets * n_tiles : 0;
-    unsigned* p_seats = gnnpn_cu_seat_table();
-    if (!p_seats) GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode: cannot allocate the seat table");
-    char* base = static_cast<char*>(workspace);
-    u64* p_h = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES);
-    u64* p_p = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES + h_bytes);
-    u64* p_l = reinterpret_cast<u64*>(base + COOP_STATUS_BYTES + h_bytes + p_bytes);
-    unsigned* p_err = reinterpret_cast<unsigned*>(base);
     const bool split = precision == GNNPN_PREC_SPLIT;
+    const bool wide = args.K > 8;
+    const bool stamps = (gnnpn_option_lstm_ablate() & 0x800) != 0;   // phase stamps (1-per-CU builds, n_per <= 8): a decoder-only bit
+    if (stamps && wide) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the stamped build exists for n_per <= 8");
+    CoopLaunch c;
+    const auto need = [&](int groups) { return lean_workspace(groups, args.B, args.T, args.K).total(); };
+    if (const int rc = coop_begin("pointer_decode", n_nets, args.B, need, GNNPN_STATUS_DEC_EXPECTED, opts, workspace, workspace_bytes, s, c))
+        return rc;
+    const DecodeWorkspace w = lean_workspace(c.groups, args.B, args.T, args.K);
+    u64* p_h = reinterpret_cast<u64*>(c.buffers);
+    u64* p_p = reinterpret_cast<u64*>(c.buffers + w.h_bytes);
+    u64* p_l = reinterpret_cast<u64*>(c.buffers + w.h_bytes + w.p_bytes);
     static unsigned* p_diag = gnnpn_decode_diag_buffer();   // failure record (written on a timed-out sweep only)
     const int wt = (opts.write_through ? 1 : 0) | (opts.paired_start ? 2 : 0);
-    const int lds_kb = opts.lds_kb;
-#define GNNPN_LEAN(SPLIT_, OCC_, EVH_, ...)                                                                                  \
-    hipLaunchKernelGGL((pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>), dim3(COOP_OVERSUB * groups * G), dim3(256), \
-                       coop_lds_padding((const void*)pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>, lds_kb), s, args, p_h, p_p, \
-                       p_l, p_err, opts.sticky, n_nets, groups_per_net, gpx, wt, p_seats, p_diag)
-    const bool wide = args.K > 8;
-    if (gnnpn_option_lstm_ablate() & 0x800) {       // phase stamps (1-per-CU builds, n_per <= 8): a decoder-only bit
-        if (wide) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the stamped build exists for n_per <= 8");
+#define GNNPN_LEAN(SPLIT_, OCC_, EVH_, ...)                                                                                           \
+    hipLaunchKernelGGL((pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),       \
+                       gnnpn_lds_padding((const void*)pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>, opts.lds_kb), s, args, \
+                       p_h, p_p, p_l, c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, wt, c.seats, p_diag)
+    if (stamps) {
         if (split) GNNPN_LEAN(true, 1, 2, true);
         else GNNPN_LEAN(false, 1, 2, true);
     } else if (split && shared_cu && wide) GNNPN_LEAN(true, 2, 1);

@@ -24,9 +24,9 @@
 #include "decode_shared.h"   // gnnpn_decode_diag_buffer: the failure record both recurrent kernels write
 
 namespace {
-constexpr int H = 256;
-constexpr int G = 8;              // workgroups per group
-constexpr int ROWS = 16;          // problems per tile (MFMA M)
+constexpr int H = COOP_H;
+constexpr int G = COOP_G;         // workgroups per group
+constexpr int ROWS = COOP_ROWS;   // problems per tile (MFMA M)
 constexpr int UNITS = H / G;      // hidden units per member
 constexpr unsigned SPIN_LIMIT = 400000;   // sweep passes before giving up (~0.3 s)
 constexpr int GROUP_GRANULES = 2 * ROWS * H + 2 * 4 * G;   // h granules (2 parities) + 64 spare
@@ -441,58 +441,36 @@ extern "C" int gnnpn_lstm_pack_split_weights_f32(const float* whh_packed, void* 
 
 // workspace: COOP_STATUS_BYTES of status (word 0 = error; per-XCD counters on lines of their own: coop_common.h;
 // stamps, hello granules), then the exchange buffers
+static int64_t encode_workspace_bytes(int groups) { return COOP_STATUS_BYTES + (int64_t)groups * GROUP_GRANULES * sizeof(u64); }
+
 extern "C" int64_t gnnpn_lstm_encode_workspace_bytes(void) {
     (void)gnnpn_cu_seat_table();   // callers size their workspace before the first launch and outside any capture: create the seat table here
-    return COOP_STATUS_BYTES + (int64_t)64 * GROUP_GRANULES * sizeof(u64);   // up to 64 groups
+    return encode_workspace_bytes(64);   // up to 64 groups
 }
 
 int gnnpn_launch_encode_coop(const LstmNets& nets, int n_nets, int32_t B, int32_t L, int precision, const CoopOpts& opts,
                              void* workspace, int64_t workspace_bytes, hipStream_t s) {
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "lstm_encode: cannot query the device");
-    const int n_tiles = (B + ROWS - 1) / ROWS;
-    // groups per XCD: every workgroup must be resident at once (one per CU), grid = 8 * G * gpx
-    int gpx = n_cu / (8 * G);
-    if (gpx > 8) gpx = 8;
-    while (gpx > 1 && (gpx - 1) * 8 >= n_nets * n_tiles) --gpx;
-    // coop_place assumes 8 XCDs with workgroup ids dealt round-robin over them (MI355X in SPX mode: 256 CUs); a partitioned
-    // device (CPX / DPX / QPX: fewer XCDs) would never finish staffing
-    if (gpx < 1 || n_cu < 256) GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_encode: device has %d CUs, the cooperative form is built for 8 XCDs x 32 CUs", n_cu);
-    const int groups = gpx * 8;
-    if (groups < n_nets) GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_encode: %d groups for %d nets", groups, n_nets);
-    const int groups_per_net = groups / n_nets;
-    const int64_t need = COOP_STATUS_BYTES + (int64_t)groups * GROUP_GRANULES * sizeof(u64);
-    if (!workspace || workspace_bytes < need || !gnnpn_aligned(workspace, 256))
-        GNNPN_FAIL(GNNPN_E_ARG, "lstm_encode: workspace of %lld B (256-B aligned) required", (long long)need);
-    // zero the status word and every tag before each launch (tags start at 1).  Test hook (lstm_ablate bit 13, tests only): leave
-    // the workspace as the previous launch left it — every workgroup must then notice (status code 8) instead of running on it
-    if (coop_zero_workspace(workspace, (size_t)need, s, opts.sticky, GNNPN_STATUS_ENC_EXPECTED, (unsigned)(G * n_nets * n_tiles),
-                            (gnnpn_option_lstm_ablate() & 0x2000) != 0) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "lstm_encode: workspace memset failed");
-    g_gnnpn_last_units = opts.sticky ? (int64_t)G * n_nets * n_tiles : 0;
-    unsigned* p_seats = gnnpn_cu_seat_table();
-    if (!p_seats) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot allocate the seat table", "lstm_encode");
-    u64* p_x = reinterpret_cast<u64*>(static_cast<char*>(workspace) + COOP_STATUS_BYTES);
-    unsigned* p_e = reinterpret_cast<unsigned*>(workspace);
     bool pre = nets.pregates[0] != nullptr;
     for (int n = 0; n < n_nets; ++n)
         if ((nets.pregates[n] != nullptr) != pre)
             GNNPN_FAIL(GNNPN_E_ARG, "lstm_encode: all nets of a call must use the same input-side form");
     const int prec = precision;   // GNNPN_PREC_*: 0 fp32, 1 fp16 operands, 2 fp16-split operands
-    const int abl = (gnnpn_option_lstm_ablate() & ~(0x800 | 0x1000 | 0x2000)) | (opts.write_through ? 128 : 0);   // bit 11 belongs to the decoder (phase stamps), 13 to the launch (above)
+    const int abl = (gnnpn_option_lstm_ablate() & ~(0x800 | 0x1000 | 0x2000)) | (opts.write_through ? 128 : 0);   // bit 11 belongs to the decoder (phase stamps), 13 to the launch (coop_begin)
+    const bool diag = (abl & ~128) != 0;   // diagnostic build (folded form; fp32 with every switch, exact split with the phase stamps)
+    if (diag && (prec == 1 || pre || (prec == 2 && (abl & ~(128 | 32)) != 0)))
+        GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_encode: diagnostics are built for the folded form (fp32: all switches; split: stamps only)");
+    CoopLaunch c;
+    if (const int rc = coop_begin("lstm_encode", n_nets, B, encode_workspace_bytes, GNNPN_STATUS_ENC_EXPECTED, opts, workspace,
+                                  workspace_bytes, s, c))
+        return rc;
+    u64* p_x = reinterpret_cast<u64*>(c.buffers);
     const int abl_arg = abl | (opts.paired_start ? 0x1000 : 0);   // bit 12 rides the kernel argument only (placement, coop_place)
-    const int lds_kb = opts.lds_kb;
-    unsigned* p_s = opts.sticky;
     static unsigned* p_diag = gnnpn_decode_diag_buffer();   // failure record (diagnostic build, timed-out sweep only)
-#define GNNPN_ENC(PREC_, PRE_, DIAG_)                                                                            \
-    hipLaunchKernelGGL((lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>), dim3(COOP_OVERSUB * groups * G), dim3(256),              \
-                       coop_lds_padding((const void*)lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>, lds_kb), s, nets, p_x, \
-                       p_e, p_s, B, L, n_nets, groups_per_net, gpx, abl_arg, p_seats, p_diag)
-    if ((abl & ~128) != 0) {   // diagnostic build (folded form; fp32 with every switch, exact split with the phase stamps)
-        if (prec == 1 || pre || (prec == 2 && (abl & ~(128 | 32)) != 0))
-            GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_encode: diagnostics are built for the folded form (fp32: all switches; split: stamps only)");
+#define GNNPN_ENC(PREC_, PRE_, DIAG_)                                                                                        \
+    hipLaunchKernelGGL((lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),             \
+                       gnnpn_lds_padding((const void*)lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>, opts.lds_kb), s, nets, p_x, \
+                       c.status, opts.sticky, B, L, n_nets, c.groups_per_net, c.gpx, abl_arg, c.seats, p_diag)
+    if (diag) {
         if (prec == 2) GNNPN_ENC(2, false, true);
         else GNNPN_ENC(0, false, true);
     } else if (prec == 2 && pre) GNNPN_ENC(2, true, false);

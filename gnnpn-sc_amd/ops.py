@@ -413,6 +413,21 @@ def pack_lstm_split_weights(whh_packed):
 # operand precision of the recurrent W_hh.h product -> GNNPN_PREC_* (include/gnnpn_hip.h)
 _PRECISIONS = {"f32": 0, "f16": 1, "split": 2}
 
+# The status area at the start of a cooperative launch's workspace, as csrc/coop_common.h lays it out (byte offsets;
+# tests/test_host_logic.py checks these against the header).  The per-XCD counters sit COOP_XCD_STRIDE words apart.
+COOP_STATUS_BYTES = 16384
+COOP_XCD_STRIDE = 32         # words between two XCDs' counters
+COOP_XCDCNT_OFFSET = 12288   # seats taken on each XCD
+COOP_ARRIVE_OFFSET = 13312   # workgroups of the launch that arrived on each XCD
+COOP_PLACED_OFFSET = 14336   # seated workgroups on the same-XCD hand-off, per XCD (statistics)
+COOP_TAKEN_OFFSET = 10240    # seat flags, 64 words per XCD
+
+
+def coop_per_xcd(words, offset):
+    """The eight per-XCD counters at byte ``offset`` of a status area, from its 32-bit ``words`` (a list or an int32 tensor)."""
+    w = offset // 4
+    return words[w:w + 8 * COOP_XCD_STRIDE:COOP_XCD_STRIDE]
+
 
 class Workspaces:
     """Hand-off workspaces + the sticky status word of the cooperative recurrent kernels, for ONE stream of launches.
@@ -533,7 +548,7 @@ class Workspaces:
         if self._encode is None:
             return None
         w = self._encode[:16].view(torch.int32).tolist()
-        placed = self._encode[14336:15360].view(torch.int32)[::32].sum().item()     # per-XCD words on lines of their own (coop_common.h: COOP_PLACED_OFFSET)
+        placed = coop_per_xcd(self._encode[:COOP_STATUS_BYTES].view(torch.int32), COOP_PLACED_OFFSET).sum().item()
         return {"members_placed": int(placed), "off_canonical_seats": w[2], "declined_seats": w[3]}
 
     def check(self, what="cooperative kernel"):
@@ -752,8 +767,8 @@ def pointer_decode(nets, inputs, n_cat, n_per, tanh_c=10.0, use_tanh=True, want_
     queries [B,T,H] | None.
     precision="split": the W_hh.h product from exact three-piece fp16 operands (cooperative, folded form only); "f16" is an
     encoder-only mode and leaves the decoder in fp32.
-    impl: 0 auto, 1 streaming, 2 cooperative (8-CU groups), 3 (16-CU groups), 4 (8-CU groups, 256-register build for two
-    workgroups per CU); lds_kb / write_through / ws as for lstm_encode."""
+    impl: 0 auto, 1 streaming, 2 cooperative (8-CU groups), 4 (8-CU groups, 256-register build for two workgroups per CU);
+    lds_kb / write_through / ws as for lstm_encode."""
     B, L, H = nets[0]["enc_out"].shape
     if precision not in _PRECISIONS:
         raise GnnpnError(f"pointer_decode: unknown precision {precision!r}")

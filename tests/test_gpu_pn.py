@@ -383,6 +383,15 @@ def test_folded_vs_two_stage_input_projection(dev, name):
         assert np.abs(out["win_low"].cpu().numpy()[s] - fx["win_low"][s]).max() < LOGIT_ATOL
     same = ((a["idx_low"] == b["idx_low"]).all(1) & (a["idx_high"] == b["idx_high"]).all(1))
     assert float((a["win_low"][same] - b["win_low"][same]).abs().max()) < LOGIT_ATOL
+    # High sampled on the two-stage input side: the general cooperative decoder has no such build and refuses the call before it
+    # books any work, so the auto choice (impl 0) falls through to the streaming form with the proof of work intact
+    from gnnpn_sc_amd import ops
+    ws = ops.new_workspaces(dev)
+    auto = two_level_greedy(low, high, x, fold=False, sample_high_seed=7, ws=ws)
+    ws.check()
+    streaming = two_level_greedy(low, high, x, fold=False, sample_high_seed=7, decode_impl=1, ws=ops.new_workspaces(dev))
+    for key in ("idx_low", "idx_high", "actions", "action_probs"):
+        assert torch.equal(auto[key], streaming[key]), key
 
 
 def test_saturated_logits_first_max_wins(dev):
@@ -607,23 +616,26 @@ def test_a_launch_on_a_dirty_workspace_is_loud(dev):
 
 
 # ---- proof of work (round 5): a cooperative launch that did not do its work cannot pass a check ------------------------------
-# layout of a workspace's status area in 32-bit words (csrc/coop_common.h): 0 the launch's error word, 4 staffing state, 5 seats
-# taken in all, 256.. seats taken per XCD, 288.. arrivals per XCD, 512..2559 CU claim statistics, 2560.. seat flags (64 per XCD)
+# layout of a workspace's status area in 32-bit words (csrc/coop_common.h, named in ops): 0 the launch's error word, 4 staffing
+# state, 5 XCDs whose seats are all taken, 512.. CU claim statistics, then from COOP_TAKEN_OFFSET the seat flags (64 per XCD), and
+# from COOP_XCDCNT_OFFSET / COOP_ARRIVE_OFFSET the seats taken / arrivals per XCD, one counter every COOP_XCD_STRIDE words
 def _poison(kind, words, gen):
     """Patterns for the status area of a workspace that the launch then does NOT zero (test hook).  The first two are what the
     failure record of round 4 showed (profiles/r04_handoff_timeouts_on_some_boxes.jsonl): the PREVIOUS launch's totals."""
+    from gnnpn_sc_amd import ops
+    cnt, arr, taken, stride = ops.COOP_XCDCNT_OFFSET // 4, ops.COOP_ARRIVE_OFFSET // 4, ops.COOP_TAKEN_OFFSET // 4, ops.COOP_XCD_STRIDE
     p = torch.zeros(words, dtype=torch.int32)
     if kind in ("previous_totals", "previous_totals_some_xcds"):
         xcds = range(8) if kind == "previous_totals" else (1, 4, 6)
-        for x in xcds:                            # (word offsets: csrc/coop_common.h, COOP_XCDCNT_OFFSET / COOP_ARRIVE_OFFSET / COOP_TAKEN_OFFSET)
-            p[3072 + 32 * x] = 32                 # the XCD's 32 seats taken
-            p[3328 + 32 * x] = 96                 # every workgroup of the 3 x over-subscribed launch arrived
-            p[2560 + 64 * x:2560 + 64 * x + 32] = 1
+        for x in xcds:
+            p[cnt + stride * x] = 32              # the XCD's 32 seats taken
+            p[arr + stride * x] = 96              # every workgroup of the 3 x over-subscribed launch arrived
+            p[taken + 64 * x:taken + 64 * x + 32] = 1
         p[4], p[5] = 2, len(list(xcds))          # "staffed", XCDs complete
     elif kind == "seat_counters_only":
-        p[3072:3072 + 256:32] = 32
+        p[cnt:cnt + 8 * stride:stride] = 32
     elif kind == "seat_flags_only":
-        p[2560:2560 + 512:3] = 1                 # every third seat looks taken: those members can never be seated
+        p[taken:taken + 8 * 64:3] = 1            # every third seat looks taken: those members can never be seated
     elif kind == "staffing_word":
         p[4] = 1
     elif kind == "random_dense":
@@ -674,7 +686,7 @@ def test_poisoned_status_area_ends_loud_or_correct(dev, which, kind):
         ws._encode.zero_()
         if ws._decode is not None:
             ws._decode.zero_()
-        buf[:16384].view(torch.int32).copy_(_poison(kind, 16384 // 4, gen))
+        buf[:ops.COOP_STATUS_BYTES].view(torch.int32).copy_(_poison(kind, ops.COOP_STATUS_BYTES // 4, gen))
         torch.cuda.synchronize()
         ops.set_option("lstm_ablate", 0x2000)
         got = launch()

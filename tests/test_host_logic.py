@@ -558,3 +558,17 @@ def test_slot_streams_keep_normal_priority_without_an_rccl_process_group():
     from gnnpn_sc_amd import pipeline
     import torch.distributed as td
     assert not td.is_initialized() and pipeline._has_collective_stream() is False
+
+
+def test_status_area_layout_matches_coop_common():
+    """ops' names for the words of a cooperative status area (Workspaces.placement, the proof-of-work tests, the probes) are the
+    constexpr values of csrc/coop_common.h: a move of the layout cannot leave a Python reader behind."""
+    import re
+    from gnnpn_sc_amd import ops
+    with open(os.path.join(ROOT, "gnnpn-sc_amd", "csrc", "coop_common.h")) as f:
+        header = dict(re.findall(r"^constexpr int (COOP_\w+) = (\d+);", f.read(), re.M))
+    for name in ("COOP_STATUS_BYTES", "COOP_XCD_STRIDE", "COOP_XCDCNT_OFFSET", "COOP_ARRIVE_OFFSET", "COOP_PLACED_OFFSET",
+                 "COOP_TAKEN_OFFSET"):
+        assert int(header[name]) == getattr(ops, name), name
+    assert ops.coop_per_xcd(list(range(ops.COOP_STATUS_BYTES // 4)), ops.COOP_ARRIVE_OFFSET) == \
+        [ops.COOP_ARRIVE_OFFSET // 4 + ops.COOP_XCD_STRIDE * x for x in range(8)]

@@ -21,8 +21,9 @@ keys = ("idx_low", "idx_high", "R")
 def area(buf):
     if buf is None:
         return None
-    wds = buf[:2048].view(torch.int32).tolist()
-    return {"words0_8": wds[:8], "seats_per_xcd": wds[256:264], "arrivals_per_xcd": wds[288:296]}
+    wds = buf[:ops.COOP_STATUS_BYTES].view(torch.int32).tolist()
+    return {"words0_8": wds[:8], "seats_per_xcd": ops.coop_per_xcd(wds, ops.COOP_XCDCNT_OFFSET),
+            "arrivals_per_xcd": ops.coop_per_xcd(wds, ops.COOP_ARRIVE_OFFSET)}
 
 
 for trial in range(trials):

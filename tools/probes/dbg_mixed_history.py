@@ -34,8 +34,9 @@ for rnd in range(rounds):
                 fr = ops.decode_failure_record()
                 rec["decode_failures"] = {"failures": fr["failures"], "first": fr["records"][:1]}
             if st:
-                wds = dws._encode[:2048].view(torch.int32).tolist()
-                rec["encode_seats_per_xcd"], rec["encode_arrivals_per_xcd"] = wds[256:264], wds[288:296]
+                wds = dws._encode[:ops.COOP_STATUS_BYTES].view(torch.int32).tolist()
+                rec["encode_seats_per_xcd"] = ops.coop_per_xcd(wds, ops.COOP_XCDCNT_OFFSET)
+                rec["encode_arrivals_per_xcd"] = ops.coop_per_xcd(wds, ops.COOP_ARRIVE_OFFSET)
             sts.append(rec)
             outs.append({k: out[k].clone() for k in keys})
         for _ in range(8):

@@ -29,8 +29,9 @@ for trial in range(trials):
     torch.cuda.synchronize()
     def area(buf):
         if buf is None: return None
-        w = buf[:2048].view(torch.int32).tolist()
-        return {"words0_8": w[:8], "seats_per_xcd": w[256:264], "arrivals_per_xcd": w[288:296]}
+        w = buf[:ops.COOP_STATUS_BYTES].view(torch.int32).tolist()
+        return {"words0_8": w[:8], "seats_per_xcd": ops.coop_per_xcd(w, ops.COOP_XCDCNT_OFFSET),
+                "arrivals_per_xcd": ops.coop_per_xcd(w, ops.COOP_ARRIVE_OFFSET)}
     dump_default = {"encode": area(dws._encode), "decode": area(dws._decode)}
     st_default = dws.poll()
     if st_default:
