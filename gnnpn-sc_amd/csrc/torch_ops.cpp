@@ -43,6 +43,15 @@ const T* cptr(const OptTensor& t, at::ScalarType dt, const char* name) {
     return (t.has_value() && t->defined()) ? cptr<T>(*t, dt, name) : nullptr;
 }
 const float* f32(const Tensor& t, const char* n) { return cptr<float>(t, at::kFloat, n); }
+// a whh_split operand: exactly the image gnnpn_lstm_pack_split_weights_f32 writes — the kernels read all of it, a shorter buffer
+// would be read out of bounds — on the device of the weights it splits; refused before any launch
+const void* lstm_split(const Tensor& t, const Tensor& whh, const char* name) {
+    const uint8_t* p = cptr<uint8_t>(t, at::kByte, name);
+    TORCH_CHECK(t.numel() == gnnpn_lstm_split_weights_bytes(), name, ": ", t.numel(), " bytes, expected the ",
+                gnnpn_lstm_split_weights_bytes(), " bytes of gnnpn_lstm_pack_split_weights_f32");
+    TORCH_CHECK(t.device() == whh.device(), name, ": on ", t.device(), ", the weights it splits on ", whh.device());
+    return p;
+}
 const float* f32(const OptTensor& t, const char* n) { return cptr<float>(t, at::kFloat, n); }
 const int32_t* i32(const Tensor& t, const char* n) { return cptr<int32_t>(t, at::kInt, n); }
 const int32_t* i32(const OptTensor& t, const char* n) { return cptr<int32_t>(t, at::kInt, n); }
@@ -294,6 +303,8 @@ std::vector<Tensor> lstm_encode(const c10::List<OptTensor>& net_tensors, int64_t
     TORCH_CHECK(prec == GNNPN_PREC_F32 || coop, "lstm_encode: precision='", precision, "' needs the cooperative form (H = 256)");
     std::vector<gnnpn_encode_net_t> nets(n_nets);
     std::vector<Tensor> enc, hn, cn, keep;
+    for (int64_t i = 0; i < n_nets; ++i)                     // before the first launch (the streaming form materialises the pregates below)
+        if (has(EK * i + 6) && has(EK * i + 4)) lstm_split(*t[EK * i + 6], *t[EK * i + 4], "nets.whh_split");
     for (int64_t i = 0; i < n_nets; ++i) {
         const size_t o = EK * i;
         Tensor pre = has(o) ? *t[o] : Tensor();
@@ -313,7 +324,7 @@ std::vector<Tensor> lstm_encode(const c10::List<OptTensor>& net_tensors, int64_t
         }
         TORCH_CHECK(has(o + 4) && has(o + 5), "lstm_encode: nets[", i, "].whh / bhh required");
         a.whh_packed = f32(*t[o + 4], "nets.whh"), a.bhh = f32(*t[o + 5], "nets.bhh");
-        a.whh_split = has(o + 6) ? cptr<uint8_t>(*t[o + 6], at::kByte, "nets.whh_split") : nullptr;   // the exact split, made once per model
+        a.whh_split = has(o + 6) ? lstm_split(*t[o + 6], *t[o + 4], "nets.whh_split") : nullptr;   // the exact split, made once per model
         a.enc_out = out_f32(enc.back()), a.h_n = out_f32(hn.back()), a.c_n = out_f32(cn.back());
     }
     const bool ws = coop && workspace.has_value() && workspace->defined();
@@ -345,6 +356,8 @@ std::vector<Tensor> pointer_decode(const c10::List<OptTensor>& net_tensors, at::
     const int prec = precision_code(precision, "pointer_decode");
     TORCH_CHECK(L == n_cat * n_per, "pointer_decode: seq_len ", L, " != ", n_cat, "*", n_per);
     const bool coop = coop_supported(H, n_per, impl);
+    for (size_t i = 0; i < n_nets; ++i)                      // before the first launch (the streaming form materialises `embedded` below)
+        if (has(NK * i + 15) && has(NK * i + 5)) lstm_split(*t[NK * i + 15], *t[NK * i + 5], "whh_split");
     std::vector<gnnpn_decode_net_t> nets(n_nets);
     std::vector<Tensor> out, keep;
     for (size_t i = 0; i < n_nets; ++i) {
@@ -370,7 +383,7 @@ std::vector<Tensor> pointer_decode(const c10::List<OptTensor>& net_tensors, at::
             a.emb_w = f32(*t[o + 9], "emb_w"), a.emb_b = f32(*t[o + 10], "emb_b");
         }
         a.latent_win = has(o + 14) ? f32(*t[o + 14], "latent_win") : nullptr;
-        a.whh_split = has(o + 15) ? cptr<uint8_t>(*t[o + 15], at::kByte, "whh_split") : nullptr;
+        a.whh_split = has(o + 15) ? lstm_split(*t[o + 15], *t[o + 5], "whh_split") : nullptr;
         a.latent_from = (int32_t)latent_from[i];
         const int64_t seed = i < sample_seeds.size() ? sample_seeds[i] : -1;     // >= 0: draw this net's picks from the stream of that seed
         a.sample = seed >= 0 ? 1 : 0;

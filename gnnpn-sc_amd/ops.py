@@ -397,6 +397,22 @@ def pack_lstm_weight(w):
     return w.reshape(4, H, H // 4, 4).permute(2, 0, 1, 3).contiguous()
 
 
+def lstm_split_ptr(split, whh_packed, name):
+    """The pointer of a ``whh_split`` entry (None -> NULL), refused before any launch unless it is what pack_lstm_split_weights
+    makes: uint8, exactly gnnpn_lstm_split_weights_bytes() bytes — the kernels read all of them, so a shorter buffer would be
+    read out of bounds — on the device of the weights it splits."""
+    if split is None:
+        return None
+    need = int(_lib.load().gnnpn_lstm_split_weights_bytes())
+    if not isinstance(split, torch.Tensor) or split.dtype != U8 or split.numel() != need:
+        raise GnnpnError(f"{name}: expected the {need}-byte uint8 image of pack_lstm_split_weights, got "
+                         f"{tuple(split.shape) if isinstance(split, torch.Tensor) else type(split).__name__} "
+                         f"{getattr(split, 'dtype', '')}")
+    if split.device != whh_packed.device:
+        raise GnnpnError(f"{name}: on {split.device}, the weights it splits on {whh_packed.device}")
+    return dev_ptr(split, U8, name).value
+
+
 def pack_lstm_split_weights(whh_packed):
     """The exact split ("split" precision) of a packed recurrent weight matrix [H/4, 4, H, 4], H = 256, made once per model
     (gnnpn_lstm_pack_split_weights_f32): what every cooperative launch otherwise works out for itself from ``whh_packed`` —
@@ -718,6 +734,8 @@ def lstm_encode(nets, precision="f32", impl=0, lds_kb=0, write_through=False, ws
     B, L = first.shape[0], first.shape[1]
     dev = first.device
     coop = coop_supported(H, impl=impl)
+    for i, d in enumerate(nets):                    # before the first launch (the streaming form materialises pregates below)
+        lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
     arr = (_lib.EncodeNet * n)()
     enc, h_n, c_n, keep = [], [], [], []
     for i, d in enumerate(nets):
@@ -737,7 +755,7 @@ def lstm_encode(nets, precision="f32", impl=0, lds_kb=0, write_through=False, ws
             a.w_in = dev_ptr(d["w_in"], F32, f"nets[{i}].w_in").value
             a.b_in = dev_ptr(d["b_in"], F32, f"nets[{i}].b_in").value
         a.whh_packed = dev_ptr(d["whh"], F32, f"nets[{i}].whh").value
-        a.whh_split = dev_ptr(d.get("whh_split"), U8, f"nets[{i}].whh_split", True).value if d.get("whh_split") is not None else None
+        a.whh_split = lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
         a.bhh = dev_ptr(d["bhh"], F32, f"nets[{i}].bhh").value
         a.enc_out, a.h_n, a.c_n = (dev_ptr(t, F32, "out").value for t in (e, hn, cn))
     wsp = workspaces(dev, ws) if coop else None
@@ -775,6 +793,8 @@ def pointer_decode(nets, inputs, n_cat, n_per, tanh_c=10.0, use_tanh=True, want_
     if L != n_cat * n_per:
         raise GnnpnError(f"pointer_decode: seq_len {L} != {n_cat}*{n_per}")   # modelPN.py:182
     dev = nets[0]["enc_out"].device
+    for i, d in enumerate(nets):                    # before the first launch (the streaming form materialises ``embedded`` below)
+        lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
     arr = (_lib.DecodeNet * len(nets))()
     outs = []
     for i, d in enumerate(nets):
@@ -788,8 +808,7 @@ def pointer_decode(nets, inputs, n_cat, n_per, tanh_c=10.0, use_tanh=True, want_
         for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"),
                           ("wih_packed", "wih"), ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
             setattr(a, name, dev_ptr(d[key], F32, f"nets[{i}].{key}").value)
-        if d.get("whh_split") is not None:
-            a.whh_split = dev_ptr(d["whh_split"], U8, f"nets[{i}].whh_split").value
+        a.whh_split = lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
         coop = coop_supported(H, n_per, impl)
         if d.get("xw_fold") is not None and coop:                          # folded input side (cooperative form)
             a.xw_fold = dev_ptr(d["xw_fold"], F32, f"nets[{i}].xw_fold").value

@@ -10,39 +10,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import record_agreement
+from kernel_checks import D, F32, I32, TINY, U, Recorder, exact as _exact, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
-D, F32, I32 = torch.float64, torch.float32, torch.int32
-U = 2.0 ** -24          # fp32 unit roundoff
-TINY = 1e-30
-WORST = {}              # kernel -> {measure: worst value}
+_REC = Recorder("train_kernels")     # the helpers live in tests/kernel_checks.py (shared with test_gpu_kernel_builds.py)
+WORST = _REC.worst                   # kernel -> {measure: worst value}
+_note, _bounded, _yardstick = _REC.note, _REC.bounded, _REC.yardstick
 
 
 def _ops():
     from gnnpn_sc_amd import ops
     return ops
-
-
-def _note(kernel, **kv):
-    w = WORST.setdefault(kernel, {})
-    for k, v in kv.items():
-        w[k] = max(w.get(k, 0.0), float(v))
-    record_agreement(f"train_kernels_{kernel}", w)
-
-
-def _same_bits(a, b):
-    a, b = a.detach().contiguous(), b.detach().contiguous()
-    if a.dtype == F32:
-        a, b = a.view(I32), b.view(I32)
-    elif a.dtype == D:
-        a, b = a.view(torch.int64), b.view(torch.int64)
-    return a.shape == b.shape and torch.equal(a, b)
-
-
-def _exact(a, b):
-    """Equal values (a zero's sign aside: the kernels' sums start from +0); the inputs hold no NaN."""
-    return a.shape == b.shape and torch.equal(a.detach().cpu(), b.detach().cpu())
 
 
 def _twice(fn):
@@ -54,26 +32,6 @@ def _twice(fn):
         if isinstance(x, torch.Tensor):
             assert _same_bits(x, y), "two runs on the same inputs differ"
     return r1
-
-
-def _bounded(kernel, what, got, ref, bound):
-    """|got - ref| <= bound elementwise (ref fp64); records the worst error / bound."""
-    err = (got.detach().cpu().double() - ref).abs()
-    ratio = float((err / bound).max()) if err.numel() else 0.0
-    _note(kernel, **{f"{what}_err_over_bound": ratio, "max_abs_err_vs_fp64": float(err.max()) if err.numel() else 0.0})
-    assert ratio <= 1.0, f"{kernel} {what}: error {float(err.max()):.3e} beyond the bound (ratio {ratio:.2f})"
-
-
-def _yardstick(kernel, what, got, ref64, ref32, floor_rel=2e-6, factor=4.0):
-    """max |got - ref64| <= factor * max |ref32 - ref64| + floor_rel * max |ref64|: the kernel's error within a few times that of
-    torch's own fp32 computation on the CPU (plus a floor for where that happens to be exact)."""
-    got = got.detach().cpu().double()
-    scale = float(ref64.abs().max()) if ref64.numel() else 0.0
-    ek = float((got - ref64).abs().max()) if ref64.numel() else 0.0
-    ey = float((ref32.double() - ref64).abs().max()) if ref64.numel() else 0.0
-    floor = floor_rel * scale + TINY
-    _note(kernel, **{f"{what}_yardstick_ratio": ek / (ey + floor), "max_rel_err_vs_fp64": ek / (scale + TINY)})
-    assert ek <= factor * ey + floor, f"{kernel} {what}: error {ek:.3e} vs fp32 yardstick {ey:.3e} (scale {scale:.3e})"
 
 
 def _ints(shape, lo, hi, g):
