@@ -53,6 +53,49 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// workgroup-wide max / sum of NT threads through LDS `red` (NT / 64 floats), the same in every thread: fixed butterfly inside a
+// wave, then the waves in ascending order (deterministic).  Every thread of the workgroup calls them.
+template <int NT>
+__device__ __forceinline__ float block_max(float v, float* red) {
+    constexpr int NW = NT / 64;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    if constexpr (NW == 1) return v;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float m = red[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) m = fmaxf(m, red[w]);
+    return m;
+}
+template <int NT>
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    constexpr int NW = NT / 64;
+    v = wave_sum(v);
+    if constexpr (NW == 1) return v;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = red[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) s = __fadd_rn(s, red[w]);
+    return s;
+}
+
+// the two hidden sizes the per-workgroup decode and training kernels are built for: the statement with HH = 256 or 32 (the
+// entry points refuse every other H first) and NT = the workgroup size that goes with it
+#define GNNPN_FOR_H(H_, ...)                                      \
+    do {                                                          \
+        if ((H_) == 256) {                                        \
+            [[maybe_unused]] constexpr int HH = 256, NT = 256;    \
+            __VA_ARGS__;                                          \
+        } else {                                                  \
+            [[maybe_unused]] constexpr int HH = 32, NT = 64;      \
+            __VA_ARGS__;                                          \
+        }                                                         \
+    } while (0)
+
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {

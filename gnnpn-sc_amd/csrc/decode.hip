@@ -91,17 +91,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
         for (int q = wave; q < BT * n_per; q += NW) {
             const int p = q / n_per, r = q - p * n_per;
             float part = 0.0f;
-            if (b0 + p < B) {
-                const float* row = enc_out + ((int64_t)prob_of(b0 + p) * L + (int64_t)k * n_per + r) * H;
-                for (int e = lane * 4; e < H; e += 256) {
-                    const float4 ev = *reinterpret_cast<const float4*>(row + e);
-                    const float4 hv = *reinterpret_cast<const float4*>(&hs[cur][p][e]);
-                    part = fmaf(ev.x, hv.x, part);
-                    part = fmaf(ev.y, hv.y, part);
-                    part = fmaf(ev.z, hv.z, part);
-                    part = fmaf(ev.w, hv.w, part);
-                }
-            }
+            if (b0 + p < B) part = lane_dot4<H>(enc_out + ((int64_t)prob_of(b0 + p) * L + (int64_t)k * n_per + r) * H, hs[cur][p]);
             const float dot = wave_sum(part);
             if (lane == 0) lg[p][r] = dot;
         }
@@ -112,38 +102,11 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
             const int p = j;
             const int64_t wbase = ((int64_t)(b0 + p) * T + k) * n_per;
             const int64_t lbase = ((int64_t)prob_of(b0 + p) * T + k) * n_per;
-            float best = 0.0f;
-            int best_r = -1;
-            for (int r = 0; r < n_per; ++r) {
-                float v = lg[p][r];
-                if (use_tanh) v = __fmul_rn(tanh_c, tanhf(v));
-                win_logits[wbase + r] = v;
-                if (latent_win) v = __fadd_rn(v, latent_win[lbase + r]);
-                lg[p][r] = v;
-                if (best_r < 0 || v > best) {   // strict '>' keeps the first maximum
-                    best = v;
-                    best_r = r;
-                }
-            }
-            float denom = 0.0f;
-            for (int r = 0; r < n_per; ++r) denom = __fadd_rn(denom, expf(__fsub_rn(lg[p][r], best)));
-            float prob = 1.0f / denom;                              // exp(best-best)/sum
-            if (sample) {   // multinomial(1) from the window softmax (modelPN.py:227-228): first r with u < cdf_r
-                const unsigned long long seed =
-                    REP ? replica_seed(sample_seed, (unsigned long long)(rep_first + (b0 + p) % rep_R)) : sample_seed;
-                const float u = stream_uniform24(seed, (unsigned long long)prob_of(b0 + p) * T + k);
-                float cdf = 0.0f;
-                int pick = -1, last_pos = 0;
-                for (int r = 0; r < n_per; ++r) {
-                    const float pr = expf(__fsub_rn(lg[p][r], best)) / denom;
-                    cdf = __fadd_rn(cdf, pr);
-                    if (pr > 0.0f) last_pos = r;
-                    if (pick < 0 && u < cdf) pick = r;
-                }
-                if (pick < 0) pick = last_pos;
-                best_r = pick;
-                prob = expf(__fsub_rn(lg[p][pick], best)) / denom;
-            }
+            const unsigned long long seed =
+                REP ? replica_seed(sample_seed, (unsigned long long)(rep_first + (b0 + p) % rep_R)) : sample_seed;
+            float prob;
+            const int best_r = window_pick(lg[p], n_per, tanh_c, use_tanh, win_logits, wbase, latent_win, lbase,
+                                           sample, seed, (unsigned long long)prob_of(b0 + p) * T + k, prob);
             pick_prob[(int64_t)(b0 + p) * T + k] = prob;
             idx_out[(int64_t)(b0 + p) * T + k] = k * n_per + best_r;
             sel[p] = k * n_per + best_r;
@@ -163,21 +126,20 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_kernel(
     }
 }
 
+// one net of `args` in the streaming form (BT problems per workgroup: more above 512 rows); `latent`: the window logits added to
+// the net's own, or null; `rep`: decode_shared.h ReplicaMap
 template <int H, bool REP = false>
-static void launch_decode(const float* embedded, const float* enc_out, const float* h0, const float* c0,
-                          const float* start, const float* wih, const float* whh, const float* bih,
-                          const float* bhh, const float* latent_win, const float* inputs, float tanh_c,
-                          int use_tanh, int32_t* idx, float* win_logits, float* pick_prob, float* actions,
-                          float* queries, int32_t B, int32_t T, int32_t n_per, int sample, unsigned long long sample_seed,
-                          hipStream_t s, int rep_R = 0, int rep_first = 0) {
+static void launch_decode(const DecodeArgs& args, const DecodeNet& d, const float* latent, hipStream_t s,
+                          ReplicaMap rep = ReplicaMap{0, 0}) {
     constexpr int NT = H < 64 ? 64 : H;
+    const int32_t B = args.B;
     int bt = 1;
     while (bt < 4 && B / (bt * 2) >= 256) bt *= 2;
     dim3 grid((B + bt - 1) / bt), block(NT);
-#define GNNPN_LAUNCH_DEC(BT_)                                                                                  \
-    hipLaunchKernelGGL((pointer_decode_kernel<H, BT_, REP>), grid, block, 0, s, embedded, enc_out, h0, c0, start, wih, \
-                       whh, bih, bhh, latent_win, inputs, tanh_c, use_tanh, idx, win_logits, pick_prob, actions,  \
-                       queries, B, T, n_per, sample, sample_seed, rep_R, rep_first)
+#define GNNPN_LAUNCH_DEC(BT_)                                                                                                    \
+    hipLaunchKernelGGL((pointer_decode_kernel<H, BT_, REP>), grid, block, 0, s, d.embedded, d.enc_out, d.h0, d.c0, d.start, d.wih, \
+                       d.whh, d.bih, d.bhh, latent, args.inputs, args.tanh_c, args.use_tanh, d.idx, d.win_logits, d.pick_prob,   \
+                       d.actions, d.queries, B, args.T, args.K, d.sample, (unsigned long long)d.sample_seed, rep.R, rep.first)
     switch (bt) {
         case 1: GNNPN_LAUNCH_DEC(1); break;
         case 2: GNNPN_LAUNCH_DEC(2); break;
@@ -200,26 +162,17 @@ extern "C" int gnnpn_pointer_decode_f32(int n_nets, const gnnpn_decode_net_t* ne
     GNNPN_REQUIRE(precision == GNNPN_PREC_F32 || precision == GNNPN_PREC_SPLIT, "pointer_decode: precision must be GNNPN_PREC_F32 or GNNPN_PREC_SPLIT, got %d", precision);
     GNNPN_REQUIRE(n_nets >= 1 && n_nets <= GNNPN_MAX_DECODE_NETS, "pointer_decode: n_nets must be 1..%d",
                   GNNPN_MAX_DECODE_NETS);
-    GNNPN_REQUIRE(B >= 0 && T > 0, "pointer_decode: bad shape");
     GNNPN_REQUIRE(n_per >= 1 && n_per <= 64, "pointer_decode: n_per must be in [1,64], got %d", n_per);
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: hidden size %d not built (256, 32)", H);
     DecodeArgs args{};
     for (int n = 0; n < n_nets; ++n) {
         const gnnpn_decode_net_t& d = nets[n];
-        GNNPN_REQUIRE(d.enc_out && d.h0 && d.c0 && d.start && d.wih_packed && d.whh_packed && d.bih && d.bhh,
-                      "pointer_decode: null input of net %d", n);
+        if (const int rc = decode_net_check(d, "pointer_decode", n)) return rc;
         GNNPN_REQUIRE(d.embedded || (d.emb_w && d.emb_b) || d.xw_fold,
                       "pointer_decode: net %d needs embedded, (emb_w, emb_b) or the folded input side", n);
-        GNNPN_REQUIRE((d.xw_fold != nullptr) == (d.xb_fold != nullptr) && (d.xw_fold != nullptr) == (d.start_fold != nullptr),
-                      "pointer_decode: net %d: xw_fold, xb_fold and start_fold go together", n);
-        GNNPN_REQUIRE(d.idx && d.win_logits && d.pick_prob && d.actions, "pointer_decode: null output of net %d", n);
         GNNPN_REQUIRE(d.latent_from < n && d.latent_from >= -1, "pointer_decode: latent_from of net %d must name an "
                       "earlier net of the call", n);
         GNNPN_REQUIRE(!(d.latent_win && d.latent_from >= 0), "pointer_decode: net %d has two latent sources", n);
-        GNNPN_REQUIRE(d.sample == 0 || d.sample == 1, "pointer_decode: net %d: sample must be 0 (greedy) or 1 (multinomial)", n);
-        GNNPN_REQUIRE(gnnpn_aligned(d.wih_packed, 16) && gnnpn_aligned(d.whh_packed, 16) &&
-                          gnnpn_aligned(d.enc_out, 16) && (!d.embedded || gnnpn_aligned(d.embedded, 16)),
-                      "pointer_decode: weights / enc_out / embedded must be 16-byte aligned");
         GNNPN_REQUIRE(!d.whh_split || gnnpn_aligned(d.whh_split, 16), "pointer_decode: whh_split must be 16-byte aligned");
         static_assert(sizeof(DecodeNet) == sizeof(gnnpn_decode_net_t), "layout");
         memcpy(&args.net[n], &d, sizeof(DecodeNet));
@@ -230,7 +183,6 @@ extern "C" int gnnpn_pointer_decode_f32(int n_nets, const gnnpn_decode_net_t* ne
     args.B = B;
     args.T = T;
     args.K = n_per;
-    if (B == 0) return GNNPN_OK;
     hipStream_t s = (hipStream_t)stream;
     bool any_sample = false;
     for (int n = 0; n < n_nets; ++n) any_sample |= nets[n].sample != 0;
@@ -262,14 +214,7 @@ extern "C" int gnnpn_pointer_decode_f32(int n_nets, const gnnpn_decode_net_t* ne
         const DecodeNet& d = args.net[n];
         if (!d.embedded) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the streaming form needs the embedded tensor");
         const float* latent = d.latent_from >= 0 ? args.net[d.latent_from].win_logits : d.latent_win;
-        if (H == 256)
-            launch_decode<256>(d.embedded, d.enc_out, d.h0, d.c0, d.start, d.wih, d.whh, d.bih, d.bhh, latent, inputs,
-                               tanh_c, use_tanh, d.idx, d.win_logits, d.pick_prob, d.actions, d.queries, B, T, n_per,
-                               d.sample, d.sample_seed, s);
-        else
-            launch_decode<32>(d.embedded, d.enc_out, d.h0, d.c0, d.start, d.wih, d.whh, d.bih, d.bhh, latent, inputs,
-                              tanh_c, use_tanh, d.idx, d.win_logits, d.pick_prob, d.actions, d.queries, B, T, n_per,
-                              d.sample, d.sample_seed, s);
+        GNNPN_FOR_H(H, launch_decode<HH>(args, d, latent, s));
     }
     GNNPN_CHECK_LAUNCH("pointer_decode_f32");
     return GNNPN_OK;
@@ -298,17 +243,10 @@ extern "C" int gnnpn_pointer_decode_replicas_f32(const gnnpn_decode_net_t* net, 
     GNNPN_REQUIRE(opts.impl >= 0 && opts.impl <= 2, "pointer_decode_replicas: opts.impl must be 0 (auto), 1 (streaming) or 2 (cooperative)");
     GNNPN_REQUIRE(opts.lds_kb >= 0 && opts.lds_kb <= 160, "pointer_decode_replicas: opts.lds_kb must be 0..160");
     const gnnpn_decode_net_t& d = *net;
-    GNNPN_REQUIRE(d.enc_out && d.h0 && d.c0 && d.start && d.wih_packed && d.whh_packed && d.bih && d.bhh,
-                  "pointer_decode_replicas: null input of the net");
+    if (const int rc = decode_net_check(d, "pointer_decode_replicas", 0)) return rc;
     GNNPN_REQUIRE(d.embedded || d.xw_fold, "pointer_decode_replicas: the net needs embedded or the folded input side");
-    GNNPN_REQUIRE((d.xw_fold != nullptr) == (d.xb_fold != nullptr) && (d.xw_fold != nullptr) == (d.start_fold != nullptr),
-                  "pointer_decode_replicas: xw_fold, xb_fold and start_fold go together");
-    GNNPN_REQUIRE(d.idx && d.win_logits && d.pick_prob && d.actions, "pointer_decode_replicas: null output");
     GNNPN_REQUIRE(!d.queries, "pointer_decode_replicas: queries are not written (must be NULL)");
     GNNPN_REQUIRE(d.latent_from == -1, "pointer_decode_replicas: latent_from must be -1 (Low's window logits come from latent_win)");
-    GNNPN_REQUIRE(gnnpn_aligned(d.wih_packed, 16) && gnnpn_aligned(d.whh_packed, 16) && gnnpn_aligned(d.enc_out, 16) &&
-                      (!d.embedded || gnnpn_aligned(d.embedded, 16)),
-                  "pointer_decode_replicas: weights / enc_out / embedded must be 16-byte aligned");
     DecodeArgs args{};
     memcpy(&args.net[0], &d, sizeof(DecodeNet));
     args.net[0].sample = 1;
@@ -335,15 +273,7 @@ extern "C" int gnnpn_pointer_decode_replicas_f32(const gnnpn_decode_net_t* net, 
     }
     if (opts.impl == 2) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_replicas: the cooperative form needs H = 256, n_per <= 16 and the folded input side");
     if (!d.embedded) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_replicas: the streaming form needs the embedded tensor");
-    const DecodeNet& n0 = args.net[0];
-    if (H == 256)
-        launch_decode<256, true>(n0.embedded, n0.enc_out, n0.h0, n0.c0, n0.start, n0.wih, n0.whh, n0.bih, n0.bhh, n0.latent_win,
-                                 inputs, tanh_c, use_tanh, n0.idx, n0.win_logits, n0.pick_prob, n0.actions, nullptr, (int32_t)rows,
-                                 T, n_per, 1, seed, s, R, first);
-    else
-        launch_decode<32, true>(n0.embedded, n0.enc_out, n0.h0, n0.c0, n0.start, n0.wih, n0.whh, n0.bih, n0.bhh, n0.latent_win,
-                                inputs, tanh_c, use_tanh, n0.idx, n0.win_logits, n0.pick_prob, n0.actions, nullptr, (int32_t)rows,
-                                T, n_per, 1, seed, s, R, first);
+    GNNPN_FOR_H(H, (launch_decode<HH, true>(args, args.net[0], args.net[0].latent_win, s, ReplicaMap{R, first})));
     GNNPN_CHECK_LAUNCH("pointer_decode_replicas_f32");
     return GNNPN_OK;
 }

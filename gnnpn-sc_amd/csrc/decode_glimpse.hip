@@ -25,34 +25,6 @@ struct AttnSide {          // one Attention module
     const float* v;        // [H]
 };
 
-template <int NT>
-__device__ __forceinline__ float block_max(float v, float* red) {
-    constexpr int NW = NT / 64;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    if (NW == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, red[w]);
-    return m;
-}
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red) {   // fixed order: butterfly inside a wave, waves ascending
-    constexpr int NW = NT / 64;
-    v = wave_sum(v);
-    if (NW == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s = __fadd_rn(s, red[w]);
-    return s;
-}
-
 // logits of positions [l0, l0+n) for query q (LDS), one wavefront per position; out[i] for position l0+i
 template <int H, int NT, bool BAHDANAU>
 __device__ __forceinline__ void attention_logits(const float* __restrict__ enc_b, const AttnSide& a, const float* ref_b,
@@ -62,22 +34,18 @@ __device__ __forceinline__ void attention_logits(const float* __restrict__ enc_b
     for (int i = wave; i < n; i += NW) {
         const float* row = (BAHDANAU ? ref_b : enc_b) + (int64_t)(l0 + i) * H;
         float part = 0.0f;
-        for (int e = lane * 4; e < H; e += 256) {
-            const float4 rv = *reinterpret_cast<const float4*>(row + e);
-            if constexpr (BAHDANAU) {
+        if constexpr (BAHDANAU) {
+            for (int e = lane * 4; e < H; e += 256) {
+                const float4 rv = *reinterpret_cast<const float4*>(row + e);
                 const float4 qv = *reinterpret_cast<const float4*>(qw + e);
                 const float4 vv = *reinterpret_cast<const float4*>(a.v + e);
                 part = fmaf(vv.x, tanhf(__fadd_rn(qv.x, rv.x)), part);
                 part = fmaf(vv.y, tanhf(__fadd_rn(qv.y, rv.y)), part);
                 part = fmaf(vv.z, tanhf(__fadd_rn(qv.z, rv.z)), part);
                 part = fmaf(vv.w, tanhf(__fadd_rn(qv.w, rv.w)), part);
-            } else {
-                const float4 qv = *reinterpret_cast<const float4*>(q + e);
-                part = fmaf(rv.x, qv.x, part);
-                part = fmaf(rv.y, qv.y, part);
-                part = fmaf(rv.z, qv.z, part);
-                part = fmaf(rv.w, qv.w, part);
             }
+        } else {
+            part = lane_dot4<H>(row, q);
         }
         const float dot = wave_sum(part);
         if (lane == 0) out[i] = dot;
@@ -197,37 +165,9 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void pointer_decode_glimpse_kern
         // ---- C*tanh, latent bias, softmax, first-max argmax
         if (j == 0) {
             const int64_t wbase = ((int64_t)b * T + k) * n_per;
-            float best = 0.0f;
-            int best_r = -1;
-            for (int r = 0; r < n_per; ++r) {
-                float v = win[r];
-                if (use_tanh) v = __fmul_rn(tanh_c, tanhf(v));
-                net.win_logits[wbase + r] = v;
-                if (net.latent_win) v = __fadd_rn(v, net.latent_win[wbase + r]);
-                win[r] = v;
-                if (best_r < 0 || v > best) {   // strict '>' keeps the first maximum
-                    best = v;
-                    best_r = r;
-                }
-            }
-            float denom = 0.0f;
-            for (int r = 0; r < n_per; ++r) denom = __fadd_rn(denom, expf(__fsub_rn(win[r], best)));
-            float prob = 1.0f / denom;
-            if (net.sample) {   // multinomial(1) from the window softmax (modelPN.py:227-228): first r with u < cdf_r — the draw of
-                                // decode.hip, from the same counter-based stream (problem b, step k -> counter b * T + k)
-                const float u = stream_uniform24(net.sample_seed, (unsigned long long)b * T + k);
-                float cdf = 0.0f;
-                int pick = -1, last_pos = 0;
-                for (int r = 0; r < n_per; ++r) {
-                    const float pr = expf(__fsub_rn(win[r], best)) / denom;
-                    cdf = __fadd_rn(cdf, pr);
-                    if (pr > 0.0f) last_pos = r;
-                    if (pick < 0 && u < cdf) pick = r;
-                }
-                if (pick < 0) pick = last_pos;
-                best_r = pick;
-                prob = expf(__fsub_rn(win[pick], best)) / denom;
-            }
+            float prob;   // the draw of decode.hip: problem b, step k -> counter b * T + k of the stream of sample_seed
+            const int best_r = window_pick(win, n_per, tanh_c, use_tanh, net.win_logits, wbase, net.latent_win, wbase,
+                                           net.sample, net.sample_seed, (unsigned long long)b * T + k, prob);
             net.pick_prob[(int64_t)b * T + k] = prob;
             net.idx[(int64_t)b * T + k] = k * n_per + best_r;
             sel = k * n_per + best_r;
@@ -249,17 +189,16 @@ int launch_glimpse(const DecodeNet& net, const AttnSide& ptr, const AttnSide& gl
     constexpr int NT = H < 64 ? 64 : H;
     const size_t dyn = ((size_t)T * n_per + (size_t)T) * 4;
     if (dyn > 120 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_attn: seq_len %d does not fit the LDS buffer", T * n_per);
-    if (attention == 1) {
-        auto k = pointer_decode_glimpse_kernel<H, true>;
-        if (dyn > 48 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode_attn: cannot reserve %zu B of LDS", dyn);
-        hipLaunchKernelGGL(k, dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c, use_tanh, B, T, n_per);
-    } else {
-        auto k = pointer_decode_glimpse_kernel<H, false>;
-        if (dyn > 48 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode_attn: cannot reserve %zu B of LDS", dyn);
-        hipLaunchKernelGGL(k, dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c, use_tanh, B, T, n_per);
-    }
+    const void* k = attention == 1 ? (const void*)pointer_decode_glimpse_kernel<H, true>
+                                   : (const void*)pointer_decode_glimpse_kernel<H, false>;
+    if (dyn > 48 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode_attn: cannot reserve %zu B of LDS", dyn);
+    if (attention == 1)
+        hipLaunchKernelGGL((pointer_decode_glimpse_kernel<H, true>), dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c,
+                           use_tanh, B, T, n_per);
+    else
+        hipLaunchKernelGGL((pointer_decode_glimpse_kernel<H, false>), dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c,
+                           use_tanh, B, T, n_per);
     return GNNPN_OK;
 }
 
@@ -274,13 +213,10 @@ extern "C" int gnnpn_pointer_decode_attn_f32(const gnnpn_decode_net_t* net_in, c
     GNNPN_REQUIRE(H == 256 || H == 32, "pointer_decode_attn: built for H = 256 and H = 32, got %d", H);
     GNNPN_REQUIRE(attn->attention == 0 || attn->attention == 1, "pointer_decode_attn: attention 0 ('Dot') or 1 ('Bahdanau')");
     GNNPN_REQUIRE(attn->n_glimpses >= 0, "pointer_decode_attn: n_glimpses >= 0");
+    if (const int rc = decode_net_check(*net_in, "pointer_decode_attn", 0)) return rc;
+    GNNPN_REQUIRE(net_in->embedded, "pointer_decode_attn: the embedded tensor is required");
     DecodeNet net;
-    static_assert(sizeof(net) == sizeof(*net_in), "layout");
     memcpy(&net, net_in, sizeof(net));
-    GNNPN_REQUIRE(net.embedded && net.enc_out && net.h0 && net.c0 && net.start && net.wih && net.whh && net.bih && net.bhh,
-                  "pointer_decode_attn: embedded, enc_out, h0, c0, start and the decoder weights are required");
-    GNNPN_REQUIRE(net.idx && net.win_logits && net.pick_prob && net.actions, "pointer_decode_attn: output pointers required");
-    GNNPN_REQUIRE(net.sample == 0 || net.sample == 1, "pointer_decode_attn: sample must be 0 (greedy) or 1 (multinomial)");
     AttnSide ptr{attn->pointer_wq, attn->pointer_bq, attn->pointer_ref, attn->pointer_v};
     AttnSide gl{attn->glimpse_wq, attn->glimpse_bq, attn->glimpse_ref, attn->glimpse_v};
     if (attn->attention == 1) {
@@ -288,11 +224,9 @@ extern "C" int gnnpn_pointer_decode_attn_f32(const gnnpn_decode_net_t* net_in, c
         if (attn->n_glimpses > 0)
             GNNPN_REQUIRE(gl.wq && gl.bq && gl.ref && gl.v, "pointer_decode_attn: 'Bahdanau' glimpses need the glimpse's W_query, bias, W_ref(enc_out) and V");
     }
-    if (B == 0) return GNNPN_OK;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (H == 256) rc = launch_glimpse<256>(net, ptr, gl, inputs, attn->attention, attn->n_glimpses, tanh_c, use_tanh, B, T, n_per, s);
-    else rc = launch_glimpse<32>(net, ptr, gl, inputs, attn->attention, attn->n_glimpses, tanh_c, use_tanh, B, T, n_per, s);
+    GNNPN_FOR_H(H, rc = launch_glimpse<HH>(net, ptr, gl, inputs, attn->attention, attn->n_glimpses, tanh_c, use_tanh, B, T, n_per, s));
     if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH("pointer_decode_attn_f32");
     return GNNPN_OK;

@@ -42,8 +42,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void lstm_train_forward_kernel(
                 gate[g] = (gate[g] + bhh[g * H + j]) + pregates[base + g * H + j];
                 gates_pre[base + g * H + j] = gate[g];
             }
-            c = sigm(gate[1]) * c + sigm(gate[0]) * tanhf(gate[2]);
-            h = sigm(gate[3]) * tanhf(c);
+            h = cell_forward(gate, c);
             c_all[((int64_t)b * L + t) * H + j] = c;
             enc_out[((int64_t)b * L + t) * H + j] = h;
         }
@@ -55,24 +54,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void lstm_train_forward_kernel(
 
 // ---- 1b. teacher-forced decoder forward with saves.  picks idx [B,T] (global positions) are GIVEN.
 struct DecTrain {
-    const float* embedded;   // [B,L,H]
-    const float* enc_out;    // [B,L,H]
-    const float* h0;         // [B,H]  encoder final h (= enc_out[:, L-1])
-    const float* c0;         // [B,H]
-    const float* start;      // [H]
-    const float* wih;        // TRANSPOSED [H,4H] (forward products); the backward takes the plain [4H,H]
-    const float* whh;
-    const float* bih;
-    const float* bhh;
-    const float* latent_win; // [B,T,K] or null
-    const int32_t* idx;      // [B,T]
-    float* x_all;            // [B,T,H] decoder inputs
-    float* gates_pre;        // [B,T,4H]
-    float* c_all;            // [B,T,H]
-    float* h_all;            // [B,T,H]
-    float* z0;               // [B,T,K]  C*tanh(dot) (or dot)
-    float* probs;            // [B,T,K]
-    float* logp;             // [B,T]    log-probability of the pick
+    gnnpn_decode_train_t t;  // wih, whh: TRANSPOSED [H,4H] (forward products); the backward takes the plain [4H,H]
     float tanh_c;
     int use_tanh;
     int32_t B, T, K;
@@ -83,63 +65,28 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_train_forward_kernel
     __shared__ __attribute__((aligned(16))) float xs[H];
     __shared__ __attribute__((aligned(16))) float hs[H];
     __shared__ float lg[64];
-    const int b = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
-    constexpr int NW = (H < 64 ? 64 : H) / 64;
+    const int b = blockIdx.x, j = threadIdx.x;
+    constexpr int NT = H < 64 ? 64 : H;
+    const gnnpn_decode_train_t& t = a.t;
     const bool owner = j < H;
     const int T = a.T, K = a.K, L = T * K;
-    float c = owner ? a.c0[(int64_t)b * H + j] : 0.0f;
+    float c = owner ? t.c0[(int64_t)b * H + j] : 0.0f;
     if (owner) {
-        hs[j] = a.h0[(int64_t)b * H + j];
-        xs[j] = a.start[j];
+        hs[j] = t.h0[(int64_t)b * H + j];
+        xs[j] = t.start[j];
     }
     __syncthreads();
     for (int k = 0; k < T; ++k) {
+        const int64_t step = (int64_t)b * T + k;
         float h = 0.0f;
-        if (owner) {
-            float gi[4] = {0.f, 0.f, 0.f, 0.f}, gh[4] = {0.f, 0.f, 0.f, 0.f};
-            matvec_rows<H>(a.wih, xs, j, gi);
-            matvec_rows<H>(a.whh, hs, j, gh);
-            const int64_t base = ((int64_t)b * T + k) * (4 * H);
-            float gate[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                gate[g] = (gh[g] + a.bhh[g * H + j]) + (gi[g] + a.bih[g * H + j]);
-                a.gates_pre[base + g * H + j] = gate[g];
-            }
-            a.x_all[((int64_t)b * T + k) * H + j] = xs[j];
-            c = sigm(gate[1]) * c + sigm(gate[0]) * tanhf(gate[2]);
-            h = sigm(gate[3]) * tanhf(c);
-            a.c_all[((int64_t)b * T + k) * H + j] = c;
-            a.h_all[((int64_t)b * T + k) * H + j] = h;
-        }
+        if (owner) h = decoder_cell_forward<H>(t, xs, hs, step, j, c);
         __syncthreads();
         if (owner) hs[j] = h;
         __syncthreads();
-        for (int r = wave; r < K; r += NW) {          // window dots: one wave per candidate row
-            const float* row = a.enc_out + ((int64_t)b * L + (int64_t)k * K + r) * H;
-            float part = 0.0f;
-            for (int e = lane; e < H; e += 64) part = fmaf(row[e], hs[e], part);
-            const float dot = wave_sum(part);
-            if (lane == 0) lg[r] = dot;
-        }
+        attention_logits<H, NT>(false, t.enc_out + (int64_t)b * L * H, hs, nullptr, k * K, K, lg);   // window dots
         __syncthreads();
-        if (j == 0) {
-            const int64_t wb = ((int64_t)b * T + k) * K;
-            float best = -INFINITY;
-            for (int r = 0; r < K; ++r) {
-                float v = a.use_tanh ? a.tanh_c * tanhf(lg[r]) : lg[r];
-                a.z0[wb + r] = v;
-                if (a.latent_win) v += a.latent_win[wb + r];
-                lg[r] = v;
-                best = fmaxf(best, v);
-            }
-            float denom = 0.0f;
-            for (int r = 0; r < K; ++r) denom += expf(lg[r] - best);
-            const int pick = a.idx[(int64_t)b * T + k] - k * K;
-            for (int r = 0; r < K; ++r) a.probs[wb + r] = expf(lg[r] - best) / denom;
-            a.logp[(int64_t)b * T + k] = (lg[pick] - best) - logf(denom);
-        }
-        if (owner) xs[j] = a.embedded[((int64_t)b * L + a.idx[(int64_t)b * T + k]) * H + j];   // modelPN.py:235
+        if (j == 0) window_softmax_logp(t, lg, step, k, K, a.tanh_c, a.use_tanh);
+        if (owner) xs[j] = t.embedded[((int64_t)b * L + t.idx[step]) * H + j];   // modelPN.py:235
         __syncthreads();
     }
 }
@@ -178,25 +125,22 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_train_backward_kerne
     float dh = 0.0f, dc = 0.0f;
     for (int k = T - 1; k >= 0; --k) {
         const int64_t wb = ((int64_t)b * T + k) * K;
-        if (j < K) {   // softmax -> (+latent: constant) -> C*tanh backward
-            const int pick = a.idx[(int64_t)b * T + k] - k * K;
-            const float dz = gs * ((j == pick ? 1.0f : 0.0f) - a.probs[wb + j]);
-            const float z = a.z0[wb + j];
-            du[j] = a.use_tanh ? dz * (a.tanh_c - z * z / a.tanh_c) : dz;
-        }
+        const int64_t step = (int64_t)b * T + k;
+        if (j < K) du[j] = window_du(a.probs[wb + j], a.z0[wb + j], j == a.idx[step] - k * K, gs, a.tanh_c, a.use_tanh);
         __syncthreads();
         if (owner) {
-            const float hk = a.h_all[((int64_t)b * T + k) * H + j];
+            const float hk = a.h_all[step * H + j];
             for (int r = 0; r < K; ++r) {
                 const int64_t row = ((int64_t)b * L + (int64_t)k * K + r) * H + j;
                 dh = fmaf(du[r], a.enc_out[row], dh);
                 a.d_enc_out[row] = du[r] * hk;
             }
-            const int64_t base = ((int64_t)b * T + k) * (4 * H);
-            const float c_prev = k > 0 ? a.c_all[((int64_t)b * T + k - 1) * H + j] : a.c0[(int64_t)b * H + j];
+            // the statements of cell_backward_step (train_common.h), kept here: see there
+            const int64_t base = step * (4 * H);
+            const float c_prev = k > 0 ? a.c_all[(step - 1) * H + j] : a.c0[(int64_t)b * H + j];
             float dg[4];
             cell_backward(a.gates_pre[base + j], a.gates_pre[base + H + j], a.gates_pre[base + 2 * H + j],
-                          a.gates_pre[base + 3 * H + j], c_prev, a.c_all[((int64_t)b * T + k) * H + j], dh, dc, dg);
+                          a.gates_pre[base + 3 * H + j], c_prev, a.c_all[step * H + j], dh, dc, dg);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 dgs[g * H + j] = dg[g];
@@ -205,7 +149,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_train_backward_kerne
         }
         __syncthreads();
         if (owner) {
-            a.dx[((int64_t)b * T + k) * H + j] = matvec_cols<H>(a.wih, dgs, j);
+            a.dx[step * H + j] = matvec_cols<H>(a.wih, dgs, j);
             dh = matvec_cols<H>(a.whh, dgs, j);
         }
         __syncthreads();
@@ -227,22 +171,10 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void lstm_train_backward_kernel(
     const bool owner = j < H;
     float dh = owner ? dh0[(int64_t)b * H + j] : 0.0f, dc = owner ? dc0[(int64_t)b * H + j] : 0.0f;
     for (int t = L - 1; t >= 0; --t) {
-        if (owner) {
-            const int64_t base = ((int64_t)b * L + t) * (4 * H);
-            dh += d_enc_out[((int64_t)b * L + t) * H + j];
-            const float c_prev = t > 0 ? c_all[((int64_t)b * L + t - 1) * H + j] : 0.0f;
-            float dg[4];
-            cell_backward(gates_pre[base + j], gates_pre[base + H + j], gates_pre[base + 2 * H + j], gates_pre[base + 3 * H + j],
-                          c_prev, c_all[((int64_t)b * L + t) * H + j], dh, dc, dg);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                dgs[g * H + j] = dg[g];
-                dgates[base + g * H + j] = dg[g];
-            }
-        }
-        __syncthreads();
-        if (owner) dh = matvec_cols<H>(whh, dgs, j);
-        __syncthreads();
+        const int64_t row = (int64_t)b * L + t;
+        if (owner) dh += d_enc_out[row * H + j];
+        const float c_prev = owner && t > 0 ? c_all[(row - 1) * H + j] : 0.0f;
+        dh = cell_backward_step<H>(gates_pre, c_all, row, c_prev, dh, dc, dgs, dgates, nullptr, nullptr, whh, j);
     }
 }
 
@@ -315,12 +247,6 @@ __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict_
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------
-#define GNNPN_H_DISPATCH(H_, KERNEL, GRID, ...)                                                              \
-    do {                                                                                                     \
-        if ((H_) == 256) hipLaunchKernelGGL((KERNEL<256>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-        else hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(64), 0, s, __VA_ARGS__);                            \
-    } while (0)
-
 extern "C" int gnnpn_lstm_train_forward_f32(const float* pregates, const float* whh, const float* bhh, float* enc_out,
                                             float* gates_pre, float* c_all, int32_t B, int32_t L, int32_t H, void* stream) {
     GNNPN_REQUIRE(B == 0 || (pregates && whh && bhh && enc_out && gates_pre && c_all), "lstm_train_forward: null operand");
@@ -329,7 +255,8 @@ extern "C" int gnnpn_lstm_train_forward_f32(const float* pregates, const float* 
     GNNPN_REQUIRE(gnnpn_aligned(whh, 16), "lstm_train_forward: weights must be 16-byte aligned");
     if (B == 0) return GNNPN_OK;
     hipStream_t s = (hipStream_t)stream;
-    GNNPN_H_DISPATCH(H, lstm_train_forward_kernel, dim3(B), pregates, whh, bhh, enc_out, gates_pre, c_all, B, L);
+    GNNPN_FOR_H(H, hipLaunchKernelGGL((lstm_train_forward_kernel<HH>), dim3(B), dim3(NT), 0, s, pregates, whh, bhh, enc_out, gates_pre,
+                                      c_all, B, L));
     GNNPN_CHECK_LAUNCH("lstm_train_forward_f32");
     return GNNPN_OK;
 }
@@ -343,10 +270,9 @@ extern "C" int gnnpn_decode_train_forward_f32(const gnnpn_decode_train_t* t, int
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "decode_train_forward: hidden size %d not built (256, 32)", H);
     GNNPN_REQUIRE(gnnpn_aligned(t->wih, 16) && gnnpn_aligned(t->whh, 16), "decode_train_forward: weights must be 16-byte aligned");
     if (B == 0) return GNNPN_OK;
-    DecTrain a{t->embedded, t->enc_out, t->h0, t->c0, t->start, t->wih, t->whh, t->bih, t->bhh, t->latent_win, t->idx, t->x_all,
-               t->gates_pre, t->c_all, t->h_all, t->z0, t->probs, t->logp, tanh_c, use_tanh, B, T, n_per};
+    DecTrain a{*t, tanh_c, use_tanh, B, T, n_per};
     hipStream_t s = (hipStream_t)stream;
-    GNNPN_H_DISPATCH(H, decode_train_forward_kernel, dim3(B), a);
+    GNNPN_FOR_H(H, hipLaunchKernelGGL((decode_train_forward_kernel<HH>), dim3(B), dim3(NT), 0, s, a));
     GNNPN_CHECK_LAUNCH("decode_train_forward_f32");
     return GNNPN_OK;
 }
@@ -362,7 +288,7 @@ extern "C" int gnnpn_decode_train_backward_f32(const gnnpn_decode_train_t* t, co
     DecBack a{t->enc_out, t->whh, t->wih, t->c0, t->gates_pre, t->c_all, t->h_all, t->z0, t->probs, t->idx, gscale, d_enc_out,
               dgates, dx, dh0, dc0, tanh_c, use_tanh, B, T, n_per};
     hipStream_t s = (hipStream_t)stream;
-    GNNPN_H_DISPATCH(H, decode_train_backward_kernel, dim3(B), a);
+    GNNPN_FOR_H(H, hipLaunchKernelGGL((decode_train_backward_kernel<HH>), dim3(B), dim3(NT), 0, s, a));
     GNNPN_CHECK_LAUNCH("decode_train_backward_f32");
     return GNNPN_OK;
 }
@@ -375,7 +301,8 @@ extern "C" int gnnpn_lstm_train_backward_f32(const float* whh, const float* gate
     if (H != 256 && H != 32) GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_train_backward: hidden size %d not built (256, 32)", H);
     if (B == 0) return GNNPN_OK;
     hipStream_t s = (hipStream_t)stream;
-    GNNPN_H_DISPATCH(H, lstm_train_backward_kernel, dim3(B), whh, gates_pre, c_all, d_enc_out, dh0, dc0, dgates, B, L);
+    GNNPN_FOR_H(H, hipLaunchKernelGGL((lstm_train_backward_kernel<HH>), dim3(B), dim3(NT), 0, s, whh, gates_pre, c_all, d_enc_out, dh0,
+                                      dc0, dgates, B, L));
     GNNPN_CHECK_LAUNCH("lstm_train_backward_f32");
     return GNNPN_OK;
 }

@@ -32,39 +32,6 @@ struct AttnTrain {
     int32_t B, T, K;
 };
 
-// deterministic workgroup reductions through LDS (wave sums in lane order, then the waves in order)
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    constexpr int NW = NT / 64;
-    v = wave_sum(v);
-    if constexpr (NW == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s += red[w];
-    return s;
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-template <int NT>
-__device__ __forceinline__ float block_max(float v, float* red) {
-    constexpr int NW = NT / 64;
-    v = wave_maxf(v);
-    if constexpr (NW == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s = fmaxf(s, red[w]);
-    return s;
-}
-
 // qp[j] = b[j] + sum_k W[j][k] q[k] from the TRANSPOSED matrix Wt[k][j] (coalesced along j), k ascending
 template <int H>
 __device__ __forceinline__ float project(const float* __restrict__ Wt, const float* __restrict__ bias, const float* q, int j) {
@@ -82,21 +49,6 @@ __device__ __forceinline__ float project_back(const float* __restrict__ W, const
         a1 = fmaf(W[(size_t)(m + 1) * H + j], d[m + 1], a1);
     }
     return a0 + a1;
-}
-
-// logits of the positions [i0, i0 + n) against the query in LDS: one wavefront per position.  bah: V . tanh(qp + ref_i); else enc_i . q
-template <int H, int NT>
-__device__ __forceinline__ void attention_logits(bool bah, const float* __restrict__ rows, const float* qv, const float* __restrict__ v,
-                                                 int i0, int n, float* out) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = wave; i < n; i += NW) {
-        const float* row = rows + (size_t)(i0 + i) * H;
-        float part = 0.0f;
-        for (int e = lane; e < H; e += 64) part = bah ? fmaf(v[e], tanhf(qv[e] + row[e]), part) : fmaf(row[e], qv[e], part);
-        const float dot = wave_sum(part);
-        if (lane == 0) out[i] = dot;
-    }
 }
 
 // ---- forward with saves --------------------------------------------------------------------------------------------------
@@ -123,24 +75,9 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_attn_train_forward_k
     const float* gref_b = bah && G ? t.g_ref + (int64_t)b * L * H : enc_b;
     const float* pref_b = bah ? t.p_ref + (int64_t)b * L * H : enc_b;
     for (int k = 0; k < T; ++k) {
+        const int64_t step = (int64_t)b * T + k;
         float h = 0.0f;
-        if (owner) {                                                      // the decoder's LSTM cell (train.hip)
-            float gi[4] = {0.f, 0.f, 0.f, 0.f}, gh[4] = {0.f, 0.f, 0.f, 0.f};
-            matvec_rows<H>(t.base.wih, xs, j, gi);
-            matvec_rows<H>(t.base.whh, hs, j, gh);
-            const int64_t base = ((int64_t)b * T + k) * (4 * H);
-            float gate[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                gate[g] = (gh[g] + t.base.bhh[g * H + j]) + (gi[g] + t.base.bih[g * H + j]);
-                t.base.gates_pre[base + g * H + j] = gate[g];
-            }
-            t.base.x_all[((int64_t)b * T + k) * H + j] = xs[j];
-            c = sigm(gate[1]) * c + sigm(gate[0]) * tanhf(gate[2]);
-            h = sigm(gate[3]) * tanhf(c);
-            t.base.c_all[((int64_t)b * T + k) * H + j] = c;
-            t.base.h_all[((int64_t)b * T + k) * H + j] = h;
-        }
+        if (owner) h = decoder_cell_forward<H>(t.base, xs, hs, step, j, c);   // the decoder's LSTM cell (train.hip)
         __syncthreads();
         if (owner) {
             hs[j] = h;
@@ -191,22 +128,7 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_attn_train_forward_k
         }
         attention_logits<H, NT>(bah, pref_b, bah ? qp : qs, t.p_v, k * K, K, lg);
         __syncthreads();
-        if (j == 0) {
-            const int64_t wb = ((int64_t)b * T + k) * K;
-            float best = -INFINITY;
-            for (int r = 0; r < K; ++r) {
-                float v = a.use_tanh ? a.tanh_c * tanhf(lg[r]) : lg[r];
-                t.base.z0[wb + r] = v;
-                if (t.base.latent_win) v += t.base.latent_win[wb + r];
-                lg[r] = v;
-                best = fmaxf(best, v);
-            }
-            float denom = 0.0f;
-            for (int r = 0; r < K; ++r) denom += expf(lg[r] - best);
-            const int pick = t.base.idx[(int64_t)b * T + k] - k * K;
-            for (int r = 0; r < K; ++r) t.base.probs[wb + r] = expf(lg[r] - best) / denom;
-            t.base.logp[(int64_t)b * T + k] = (lg[pick] - best) - logf(denom);
-        }
+        if (j == 0) window_softmax_logp(t.base, lg, step, k, K, a.tanh_c, a.use_tanh);
         if (owner) xs[j] = t.base.embedded[((int64_t)b * L + t.base.idx[(int64_t)b * T + k]) * H + j];   // :235
         __syncthreads();
     }
@@ -237,12 +159,8 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_attn_train_backward_
     const float vp = bah && owner ? t.p_v[j] : 0.0f, vg = bah && G && owner ? t.g_v[j] : 0.0f;
     for (int k = T - 1; k >= 0; --k) {
         const int64_t wb = ((int64_t)b * T + k) * K;
-        if (j < K) {                                                      // softmax -> (+ latent: constant) -> C*tanh backward
-            const int pick = t.base.idx[(int64_t)b * T + k] - k * K;
-            const float dz = gs * ((j == pick ? 1.0f : 0.0f) - t.base.probs[wb + j]);
-            const float z = t.base.z0[wb + j];
-            du[j] = a.use_tanh ? dz * (a.tanh_c - z * z / a.tanh_c) : dz;
-        }
+        const int64_t step = (int64_t)b * T + k;
+        if (j < K) du[j] = window_du(t.base.probs[wb + j], t.base.z0[wb + j], j == t.base.idx[step] - k * K, gs, a.tanh_c, a.use_tanh);
         if (owner) qs[j] = t.q_all[(((int64_t)b * T + k) * (G + 1) + G) * H + j];   // q_G: the pointer's query
         __syncthreads();
         // ---- the pointer: d q_G, d ref (window rows) / d enc_out, d V, d qp
@@ -327,25 +245,9 @@ __global__ __launch_bounds__((H < 64 ? 64 : H)) void decode_attn_train_backward_
             dqj = dnew;
         }
         // ---- the LSTM cell (train.hip): dh_k = recurrent part + the attention's d q_0
-        if (owner) {
-            dh += dqj;
-            const int64_t base = ((int64_t)b * T + k) * (4 * H);
-            const float c_prev = k > 0 ? t.base.c_all[((int64_t)b * T + k - 1) * H + j] : t.base.c0[(int64_t)b * H + j];
-            float dg[4];
-            cell_backward(t.base.gates_pre[base + j], t.base.gates_pre[base + H + j], t.base.gates_pre[base + 2 * H + j],
-                          t.base.gates_pre[base + 3 * H + j], c_prev, t.base.c_all[((int64_t)b * T + k) * H + j], dh, dc, dg);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                dgs[g * H + j] = dg[g];
-                a.dgates[base + g * H + j] = dg[g];
-            }
-        }
-        __syncthreads();
-        if (owner) {
-            a.dx[((int64_t)b * T + k) * H + j] = matvec_cols<H>(t.base.wih, dgs, j);
-            dh = matvec_cols<H>(t.base.whh, dgs, j);
-        }
-        __syncthreads();
+        if (owner) dh += dqj;
+        const float c_prev = !owner ? 0.0f : k > 0 ? t.base.c_all[(step - 1) * H + j] : t.base.c0[(int64_t)b * H + j];
+        dh = cell_backward_step<H>(t.base.gates_pre, t.base.c_all, step, c_prev, dh, dc, dgs, a.dgates, t.base.wih, a.dx, t.base.whh, j);
     }
     if (owner) {
         a.dh0[(int64_t)b * H + j] = dh;
@@ -373,18 +275,16 @@ int check(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_pe
     if ((int64_t)T * n_per * 12 > 150 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d positions do not fit the LDS", who, T * n_per);
     return GNNPN_OK;
 }
-}  // namespace
 
 // above 64 KB the dynamic LDS must be allowed first: a refusal is reported, nothing is launched
-#define GNNPN_ATTN_DISPATCH(H_, KERNEL, GRID, LDS_, ARG)                                                                      \
-    do {                                                                                                                     \
-        const void* f_ = (H_) == 256 ? (const void*)KERNEL<256> : (const void*)KERNEL<32>;                                  \
-        const hipError_t e_ = hipFuncSetAttribute(f_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_));           \
-        if (e_ != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: %u bytes of LDS refused: %s", #KERNEL, (unsigned)(LDS_),      \
-                                         hipGetErrorString(e_));                                                             \
-        if ((H_) == 256) hipLaunchKernelGGL((KERNEL<256>), GRID, dim3(256), LDS_, s, ARG);                                   \
-        else hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(64), LDS_, s, ARG);                                                 \
-    } while (0)
+template <int H>
+int launch(void (*kernel)(AttnTrain), const char* who, const AttnTrain& a, unsigned lds, hipStream_t s) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: %u bytes of LDS refused: %s", who, lds, hipGetErrorString(e));
+    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(H < 64 ? 64 : H), lds, s, a);
+    return GNNPN_OK;
+}
+}  // namespace
 
 extern "C" int gnnpn_decode_attn_train_forward_f32(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_per, int32_t H,
                                                    float tanh_c, int use_tanh, void* stream) {
@@ -393,7 +293,9 @@ extern "C" int gnnpn_decode_attn_train_forward_f32(const gnnpn_decode_attn_train
     AttnTrain a{*t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tanh_c, use_tanh, B, T, n_per};
     hipStream_t s = (hipStream_t)stream;
     const unsigned lds = (unsigned)((size_t)T * n_per * 4 + ((size_t)T * n_per + 15) / 16 * 16);
-    GNNPN_ATTN_DISPATCH(H, decode_attn_train_forward_kernel, dim3(B), lds, a);
+    int rc;
+    GNNPN_FOR_H(H, rc = launch<HH>(decode_attn_train_forward_kernel<HH>, "decode_attn_train_forward_kernel", a, lds, s));
+    if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH("decode_attn_train_forward_f32");
     return GNNPN_OK;
 }
@@ -412,7 +314,9 @@ extern "C" int gnnpn_decode_attn_train_backward_f32(const gnnpn_decode_attn_trai
     AttnTrain a{*t, gscale, d_enc_out, dgates, dx, dh0, dc0, tanh_c, use_tanh, B, T, n_per};
     hipStream_t s = (hipStream_t)stream;
     const unsigned lds = (unsigned)((size_t)T * n_per * 8);
-    GNNPN_ATTN_DISPATCH(H, decode_attn_train_backward_kernel, dim3(B), lds, a);
+    int rc;
+    GNNPN_FOR_H(H, rc = launch<HH>(decode_attn_train_backward_kernel<HH>, "decode_attn_train_backward_kernel", a, lds, s));
+    if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH("decode_attn_train_backward_f32");
     return GNNPN_OK;
 }

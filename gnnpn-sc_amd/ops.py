@@ -773,6 +773,37 @@ def lstm_encode(nets, precision="f32", impl=0, lds_kb=0, write_through=False, ws
     return enc, h_n, c_n
 
 
+def _decode_outputs(lead, n_cat, n_per, dev):
+    """The output dictionary of a decode call over ``lead`` = (B,) problems or (B, R) rows."""
+    return {"idx": torch.empty((*lead, n_cat), dtype=I32, device=dev),
+            "win_logits": torch.empty((*lead, n_cat, n_per), dtype=F32, device=dev),
+            "pick_prob": torch.empty((*lead, n_cat), dtype=F32, device=dev),
+            "actions": torch.empty((*lead, n_cat, 8), dtype=F32, device=dev)}
+
+
+def _fill_decode_net(a, d, tag, out, emb, fold):
+    """gnnpn_decode_net_t ``a`` from the net dictionary ``d`` (``tag`` names it in error texts) and its output dictionary: the
+    required operands, the decoder inputs (``emb`` [B,L,H] or None; with ``fold`` the folded input side), latent_win, the draw
+    (sample, sample_seed) and the outputs.  latent_from is -1; emb_w / emb_b and whh_split are left to the caller."""
+    for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"), ("wih_packed", "wih"),
+                      ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
+        setattr(a, name, dev_ptr(d[key], F32, f"{tag}.{key}").value)
+    if fold:
+        for key in ("xw_fold", "xb_fold", "start_fold"):
+            setattr(a, key, dev_ptr(d[key], F32, f"{tag}.{key}").value)
+    a.embedded = None if emb is None else dev_ptr(emb, F32, f"{tag}.embedded").value
+    lw = d.get("latent_win")
+    a.latent_win = None if lw is None else dev_ptr(lw, F32, f"{tag}.latent_win").value
+    a.latent_from = -1
+    a.sample = int(bool(d.get("sample", False)))                   # draw every pick from the window softmax (stream of sample_seed)
+    a.sample_seed = int(d.get("sample_seed", 0)) & 0xFFFFFFFFFFFFFFFF
+    a.idx = dev_ptr(out["idx"], I32, "idx").value
+    a.win_logits = dev_ptr(out["win_logits"], F32, "win").value
+    a.pick_prob = dev_ptr(out["pick_prob"], F32, "prob").value
+    a.actions = dev_ptr(out["actions"], F32, "actions").value
+    a.queries = None if out.get("queries") is None else dev_ptr(out["queries"], F32, "queries").value
+
+
 def pointer_decode(nets, inputs, n_cat, n_per, tanh_c=10.0, use_tanh=True, want_queries=False, precision="f32",
                    impl=0, lds_kb=0, write_through=False, ws=None, paired_start=False):
     """Greedy decode of 1 or 2 pointer networks in ONE call (gnnpn_pointer_decode_f32).
@@ -798,40 +829,21 @@ def pointer_decode(nets, inputs, n_cat, n_per, tanh_c=10.0, use_tanh=True, want_
     arr = (_lib.DecodeNet * len(nets))()
     outs = []
     for i, d in enumerate(nets):
-        out = {"idx": torch.empty((B, n_cat), dtype=I32, device=dev),
-               "win_logits": torch.empty((B, n_cat, n_per), dtype=F32, device=dev),
-               "pick_prob": torch.empty((B, n_cat), dtype=F32, device=dev),
-               "actions": torch.empty((B, n_cat, 8), dtype=F32, device=dev),
-               "queries": torch.empty((B, n_cat, H), dtype=F32, device=dev) if want_queries else None}
+        out = _decode_outputs((B,), n_cat, n_per, dev)
+        out["queries"] = torch.empty((B, n_cat, H), dtype=F32, device=dev) if want_queries else None
         outs.append(out)
         a = arr[i]
-        for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"),
-                          ("wih_packed", "wih"), ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
-            setattr(a, name, dev_ptr(d[key], F32, f"nets[{i}].{key}").value)
-        a.whh_split = lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
         coop = coop_supported(H, n_per, impl)
-        if d.get("xw_fold") is not None and coop:                          # folded input side (cooperative form)
-            a.xw_fold = dev_ptr(d["xw_fold"], F32, f"nets[{i}].xw_fold").value
-            a.xb_fold = dev_ptr(d["xb_fold"], F32, f"nets[{i}].xb_fold").value
-            a.start_fold = dev_ptr(d["start_fold"], F32, f"nets[{i}].start_fold").value
         emb = d.get("embedded")
         if emb is None and not coop:                                       # no in-kernel embedding there
             emb = linear(inputs.reshape(B * L, inputs.shape[2]), d["emb_w"], d["emb_b"]).view(B, L, H)
-            outs[-1]["_embedded"] = emb
-        a.embedded = None if emb is None else dev_ptr(emb, F32, f"nets[{i}].embedded").value
+            out["_embedded"] = emb
+        _fill_decode_net(a, d, f"nets[{i}]", out, emb, fold=d.get("xw_fold") is not None and coop)   # folded input side: cooperative form
+        a.whh_split = lstm_split_ptr(d.get("whh_split"), d["whh"], f"nets[{i}].whh_split")
         if emb is None:
             a.emb_w = dev_ptr(d["emb_w"], F32, f"nets[{i}].emb_w").value
             a.emb_b = dev_ptr(d["emb_b"], F32, f"nets[{i}].emb_b").value
-        lw = d.get("latent_win")
-        a.latent_win = None if lw is None else dev_ptr(lw, F32, f"nets[{i}].latent_win").value
         a.latent_from = int(d.get("latent_from", -1))
-        a.sample = int(bool(d.get("sample", False)))
-        a.sample_seed = int(d.get("sample_seed", 0)) & 0xFFFFFFFFFFFFFFFF
-        a.idx = dev_ptr(out["idx"], I32, "idx").value
-        a.win_logits = dev_ptr(out["win_logits"], F32, "win").value
-        a.pick_prob = dev_ptr(out["pick_prob"], F32, "prob").value
-        a.actions = dev_ptr(out["actions"], F32, "actions").value
-        a.queries = None if out["queries"] is None else dev_ptr(out["queries"], F32, "queries").value
     coop = coop_supported(H, n_per, impl)
     wsp = workspaces(dev, ws) if coop else None
     buf = wsp.decode(B, n_cat, n_per) if coop else None
@@ -866,26 +878,10 @@ def pointer_decode_attn(net, inputs, n_cat, n_per, attention="Dot", n_glimpses=0
     emb = net.get("embedded")
     if emb is None:
         emb = linear(inputs.reshape(B * L, inputs.shape[2]), net["emb_w"], net["emb_b"]).view(B, L, H)
-    out = {"idx": torch.empty((B, n_cat), dtype=I32, device=dev),
-           "win_logits": torch.empty((B, n_cat, n_per), dtype=F32, device=dev),
-           "pick_prob": torch.empty((B, n_cat), dtype=F32, device=dev),
-           "actions": torch.empty((B, n_cat, 8), dtype=F32, device=dev),
-           "queries": torch.empty((B, n_cat, H), dtype=F32, device=dev) if want_queries else None}
+    out = _decode_outputs((B,), n_cat, n_per, dev)
+    out["queries"] = torch.empty((B, n_cat, H), dtype=F32, device=dev) if want_queries else None
     a = _lib.DecodeNet()
-    for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"), ("wih_packed", "wih"),
-                      ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
-        setattr(a, name, dev_ptr(net[key], F32, f"net.{key}").value)
-    a.embedded = dev_ptr(emb, F32, "net.embedded").value
-    lw = net.get("latent_win")
-    a.latent_win = None if lw is None else dev_ptr(lw, F32, "net.latent_win").value
-    a.latent_from = -1
-    a.sample = int(bool(net.get("sample", False)))                 # draw every pick from the window softmax (stream of sample_seed)
-    a.sample_seed = int(net.get("sample_seed", 0)) & 0xFFFFFFFFFFFFFFFF
-    a.idx = dev_ptr(out["idx"], I32, "idx").value
-    a.win_logits = dev_ptr(out["win_logits"], F32, "win").value
-    a.pick_prob = dev_ptr(out["pick_prob"], F32, "prob").value
-    a.actions = dev_ptr(out["actions"], F32, "actions").value
-    a.queries = None if out["queries"] is None else dev_ptr(out["queries"], F32, "queries").value
+    _fill_decode_net(a, net, "net", out, emb, fold=False)
     at = _lib.Attention()
     at.attention, at.n_glimpses = ATTENTION_NAMES[attention], int(n_glimpses)
     if attention == "Bahdanau":
@@ -977,32 +973,15 @@ def pointer_decode_replicas(net, inputs, n_cat, n_per, replicas, seed, first=1, 
     if L != n_cat * n_per:
         raise GnnpnError(f"pointer_decode_replicas: seq_len {L} != {n_cat}*{n_per}")
     dev = net["enc_out"].device
-    out = {"idx": torch.empty((B, R, n_cat), dtype=I32, device=dev),
-           "win_logits": torch.empty((B, R, n_cat, n_per), dtype=F32, device=dev),
-           "pick_prob": torch.empty((B, R, n_cat), dtype=F32, device=dev),
-           "actions": torch.empty((B, R, n_cat, 8), dtype=F32, device=dev)}
+    out = _decode_outputs((B, R), n_cat, n_per, dev)
 
     def launch(impl_):
         coop = coop_supported(H, n_per, impl_) and net.get("xw_fold") is not None
         a = _lib.DecodeNet()
-        for name, key in (("enc_out", "enc_out"), ("h0", "h0"), ("c0", "c0"), ("start", "start"), ("wih_packed", "wih"),
-                          ("whh_packed", "whh"), ("bih", "bih"), ("bhh", "bhh")):
-            setattr(a, name, dev_ptr(net[key], F32, f"net.{key}").value)
         emb = net.get("embedded")
-        if coop:
-            a.xw_fold = dev_ptr(net["xw_fold"], F32, "net.xw_fold").value
-            a.xb_fold = dev_ptr(net["xb_fold"], F32, "net.xb_fold").value
-            a.start_fold = dev_ptr(net["start_fold"], F32, "net.start_fold").value
-        elif emb is None:                          # the streaming form gathers embedded rows: formed once per problem, not per row
+        if emb is None and not coop:               # the streaming form gathers embedded rows: formed once per problem, not per row
             emb = linear(inputs.reshape(B * L, inputs.shape[2]), net["emb_w"], net["emb_b"]).view(B, L, H)
-        a.embedded = None if emb is None else dev_ptr(emb, F32, "net.embedded").value
-        lw = net.get("latent_win")
-        a.latent_win = None if lw is None else dev_ptr(lw, F32, "net.latent_win").value
-        a.latent_from = -1
-        a.idx = dev_ptr(out["idx"], I32, "idx").value
-        a.win_logits = dev_ptr(out["win_logits"], F32, "win").value
-        a.pick_prob = dev_ptr(out["pick_prob"], F32, "prob").value
-        a.actions = dev_ptr(out["actions"], F32, "actions").value
+        _fill_decode_net(a, net, "net", out, emb, fold=coop)
         wsp = workspaces(dev, ws) if coop else None
         buf = wsp.decode(B * R, n_cat, n_per) if coop else None
         opts = _launch_opts(wsp, impl_, lds_kb, write_through)
@@ -1291,20 +1270,28 @@ def _decode_train_struct(d):
     return t
 
 
+def _decode_train_operands(embedded, enc_out, h0, c0, start, wih, whh, bih, bhh, latent_win, idx, n_cat, n_per, extra=()):
+    """The validated operand dictionary of a teacher-forced decode with its save buffers (x_all, gates_pre, c_all, h_all, z0,
+    probs, logp, and ``extra``: (name, shape) pairs) allocated."""
+    B, L, H = enc_out.shape
+    d = {"embedded": embedded, "enc_out": enc_out, "h0": h0, "c0": c0, "start": start, "wih": wih, "whh": whh, "bih": bih,
+         "bhh": bhh, "latent_win": latent_win, "idx": idx}
+    for name, shape in (("x_all", (B, n_cat, H)), ("gates_pre", (B, n_cat, 4 * H)), ("c_all", (B, n_cat, H)),
+                        ("h_all", (B, n_cat, H)), ("z0", (B, n_cat, n_per)), ("probs", (B, n_cat, n_per)), ("logp", (B, n_cat)),
+                        *extra):
+        d[name] = torch.empty(shape, dtype=F32, device=enc_out.device)
+    for k, v in d.items():
+        if v is not None:
+            dev_ptr(v, I32 if k == "idx" else F32, k)        # validation (device, dtype, contiguity)
+    return d
+
+
 def decode_train_forward(embedded, enc_out, h0, c0, start, wih, whh, bih, bhh, latent_win, idx, n_cat, n_per, tanh_c=10.0,
                          use_tanh=True):
     """Teacher-forced decode (picks ``idx`` [B,T] int32 given) that saves what the backward needs; returns the dict of
     operands + saves that decode_train_backward takes, with ``logp`` [B,T] = log-probability of every pick."""
     B, L, H = enc_out.shape
-    dev = enc_out.device
-    d = {"embedded": embedded, "enc_out": enc_out, "h0": h0, "c0": c0, "start": start, "wih": wih, "whh": whh, "bih": bih,
-         "bhh": bhh, "latent_win": latent_win, "idx": idx}
-    for name, shape in (("x_all", (B, n_cat, H)), ("gates_pre", (B, n_cat, 4 * H)), ("c_all", (B, n_cat, H)),
-                        ("h_all", (B, n_cat, H)), ("z0", (B, n_cat, n_per)), ("probs", (B, n_cat, n_per)), ("logp", (B, n_cat))):
-        d[name] = torch.empty(shape, dtype=F32, device=dev)
-    for k, v in d.items():
-        if v is not None:
-            dev_ptr(v, I32 if k == "idx" else F32, k)        # validation (device, dtype, contiguity)
+    d = _decode_train_operands(embedded, enc_out, h0, c0, start, wih, whh, bih, bhh, latent_win, idx, n_cat, n_per)
     check(_lib.load().gnnpn_decode_train_forward_f32(_lib.ctypes.byref(_decode_train_struct(d)), B, n_cat, n_per, H,
                                                      float(tanh_c), int(bool(use_tanh)), stream_ptr()),
           "gnnpn_decode_train_forward_f32")
@@ -1346,13 +1333,10 @@ def decode_attn_train_forward(embedded, enc_out, h0, c0, start, wih, whh, bih, b
     bah = attention == "Bahdanau"
     if attention not in ("Dot", "Bahdanau"):
         raise NotImplementedError(f"attention '{attention}' (modelPN.py:116-117)")
-    d = {"embedded": embedded, "enc_out": enc_out, "h0": h0, "c0": c0, "start": start, "wih": wih, "whh": whh, "bih": bih,
-         "bhh": bhh, "latent_win": latent_win, "idx": idx, "bahdanau": bah, "n_glimpses": int(n_glimpses)}
     G = int(n_glimpses)
-    for name, shape in (("x_all", (B, n_cat, H)), ("gates_pre", (B, n_cat, 4 * H)), ("c_all", (B, n_cat, H)),
-                        ("h_all", (B, n_cat, H)), ("z0", (B, n_cat, n_per)), ("probs", (B, n_cat, n_per)), ("logp", (B, n_cat)),
-                        ("q_all", (B, n_cat, G + 1, H))):
-        d[name] = torch.empty(shape, dtype=F32, device=dev)
+    d = _decode_train_operands(embedded, enc_out, h0, c0, start, wih, whh, bih, bhh, latent_win, idx, n_cat, n_per,
+                               extra=(("q_all", (B, n_cat, G + 1, H)),))
+    d.update(bahdanau=bah, n_glimpses=G)
     if G:
         d["a_all"] = torch.empty((B, n_cat, G, L), dtype=F32, device=dev)
     if bah:
