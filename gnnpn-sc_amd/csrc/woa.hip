@@ -94,37 +94,30 @@ __device__ __forceinline__ void gather_row(const double* cand, int base, int len
 }
 }  // namespace
 
-// Where a problem's categories come from.  FixedT: one T for the whole launch, problem p owns entries p*T .. p*T+T-1 of
-// cand_ptr / len_init / start_pos (gnnpn_eswoa_f64, gnnpn_eswoa_wide_f64).  RaggedT: prob_ptr [B+1], problem p owns entries
-// prob_ptr[p] .. prob_ptr[p+1]-1 and its outputs are rows of `stride` (gnnpn_eswoa_ragged_f64); it also checks that a problem
-// fits what the launch was sized for, and may write the best composition's rows.
-struct FixedT {
-    int32_t T;
-    __device__ __forceinline__ int count(int) const { return T; }
-    __device__ __forceinline__ size_t first(int p) const { return (size_t)p * T; }
-    __device__ __forceinline__ size_t out_row(int p) const { return (size_t)p * T; }
-    __device__ __forceinline__ bool fits(int) const { return true; }
-    __device__ __forceinline__ bool fits_cand(int) const { return true; }
-    __device__ __forceinline__ double* rows_out(int) const { return nullptr; }
-};
-struct RaggedT {
-    const int32_t* prob_ptr;
-    int32_t stride;      // max_slots: row length of best_pos / best_rows, and the largest T the launch is sized for
-    int32_t max_T;       // 64 for the lane-per-category form, stride for the workgroup form
-    int32_t max_cand;    // lane-per-category form: candidates of the largest problem (LDS); workgroup form: unused
-    int32_t n_lists;     // entries of len_init / start_pos (cand_ptr has one more)
-    double* best_rows;   // [B, stride, 4] or NULL
-    __device__ __forceinline__ int count(int p) const { return prob_ptr[p + 1] - prob_ptr[p]; }
-    __device__ __forceinline__ size_t first(int p) const { return (size_t)prob_ptr[p]; }
+// Where a problem's categories come from: ONE shape for every entry point.  Problem p owns entries first(p) .. first(p) +
+// count(p) - 1 of cand_ptr / len_init / start_pos and row p (of `stride` entries) of best_pos / best_rows.  prob_ptr [B+1] gives a
+// ragged batch (gnnpn_eswoa_ragged_f64: problem p owns prob_ptr[p] .. prob_ptr[p+1]-1); prob_ptr == NULL is the same launch with
+// uniform counts (gnnpn_eswoa_f64, gnnpn_eswoa_wide_f64: T categories each, stride = T, the host has checked T).  Either way a
+// problem that does not fit what the launch was sized for is not searched (fits, fits_cand: best_fitness NaN, draws -1, no LDS
+// touched), and the best composition's rows are written where best_rows is given.
+struct Shape {
+    const int32_t* prob_ptr;   // [B+1], or NULL: every problem has T categories
+    int32_t T;                 // categories per problem where prob_ptr is NULL
+    int32_t stride;            // row length of best_pos / best_rows, and the largest count the launch is sized for
+    int32_t max_T;             // 64 for the lane-per-category form, stride for the workgroup form
+    int32_t max_cand;          // lane-per-category form: candidates of the largest problem (LDS); workgroup form: 0, unused
+    int32_t n_lists;           // entries of len_init / start_pos (cand_ptr has one more)
+    double* best_rows;         // [B, stride, 4] or NULL
+    __device__ __forceinline__ int count(int p) const { return prob_ptr ? prob_ptr[p + 1] - prob_ptr[p] : T; }
+    __device__ __forceinline__ size_t first(int p) const { return prob_ptr ? (size_t)prob_ptr[p] : (size_t)p * T; }
     __device__ __forceinline__ size_t out_row(int p) const { return (size_t)p * stride; }
-    __device__ __forceinline__ bool fits(int T) const {
-        return T >= 1 && T <= max_T && T <= stride && prob_ptr[blockIdx.x] >= 0 && prob_ptr[blockIdx.x + 1] <= n_lists;
+    __device__ __forceinline__ bool fits(int p, int n) const {
+        return !prob_ptr || (n >= 1 && n <= max_T && n <= stride && prob_ptr[p] >= 0 && prob_ptr[p + 1] <= n_lists);
     }
     __device__ __forceinline__ bool fits_cand(int n_cand) const { return max_cand <= 0 || n_cand <= max_cand; }
     __device__ __forceinline__ double* rows_out(int p) const { return best_rows ? best_rows + (size_t)p * stride * 4 : nullptr; }
 };
 
-template <class Shape>
 __global__ __launch_bounds__(64) void eswoa_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                    const int32_t* __restrict__ len_init, const double* __restrict__ cand_g,
                                                    const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(64) void eswoa_kernel(Shape sh, const int32_t* __re
     const int p = blockIdx.x, lane = threadIdx.x;
     const int T = sh.count(p);
     const size_t s0 = sh.first(p);
-    const bool fits = sh.fits(T);
+    const bool fits = sh.fits(p, T);
     const int c0 = fits ? cand_ptr[s0] : 0, n_cand = fits ? cand_ptr[s0 + T] - c0 : 0;
     if (!fits || !sh.fits_cand(n_cand)) {                             // not what the launch was sized for: no search
         if (lane == 0) {
@@ -393,7 +386,6 @@ __device__ double wide_merit(const WideLds& L, const int* pos, const double* can
 }
 }  // namespace
 
-template <class Shape>
 __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                          const int32_t* __restrict__ len_init, const double* __restrict__ cand_g,
                                                          const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
@@ -405,7 +397,7 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(Shape sh, const int32_t
     const int p = blockIdx.x, tid = threadIdx.x;
     const int T = sh.count(p);
     const size_t s0 = sh.first(p);
-    if (!sh.fits(T)) {                                             // not what the launch was sized for: no search
+    if (!sh.fits(p, T)) {                                             // not what the launch was sized for: no search
         if (tid == 0) {
             best_fitness[p] = NAN;
             draws_out[p] = -1;
@@ -532,7 +524,42 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(Shape sh, const int32_t
     }
 }
 
+// LDS bytes one problem needs (host side).  Workgroup form: three columns, red[8] + bounds[4], base / len tables, cnt[4].
+// Lane form: scratch + bounds + its candidate table + the population's positions.
 static size_t eswoa_wide_lds_bytes(int T) { return ((size_t)3 * T + 12) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int); }
+static size_t eswoa_lds_bytes(int n_cand, int pop, int T) {
+    return (256 + 4) * sizeof(double) + (size_t)n_cand * 4 * sizeof(double) + (size_t)pop * T * sizeof(int);
+}
+
+// The one launch of both forms (`wide`: the workgroup form, positions in `workspace`), sized for sh.stride categories per
+// problem; `who` names the entry point in the messages, `entry` in a launch error.
+static int eswoa_launch(const char* who, const char* entry, bool wide, int32_t B, const Shape& sh, const int32_t* cand_ptr,
+                        const int32_t* len_init, const double* cand, const double* bounds, const int32_t* start_pos, int32_t pop,
+                        int32_t max_iter, const uint64_t* seeds, void* workspace, double* best_fitness, int32_t* best_pos,
+                        double* history, int64_t* draws, void* stream) {
+    const int T = sh.stride;
+    const size_t lds = wide ? eswoa_wide_lds_bytes(T) : eswoa_lds_bytes(sh.max_cand, pop, T);
+    if (lds > 160 * 1024 - 1024) {
+        if (wide)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %s%d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", who,
+                       sh.prob_ptr ? "" : "T=", T, lds);
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", who, lds, pop, T,
+                   sh.max_cand);
+    }
+    const void* kernel = wide ? (const void*)eswoa_wide_kernel : (const void*)eswoa_kernel;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot reserve %zu B of LDS", who, lds);
+    const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
+    auto* dr = reinterpret_cast<long long*>(draws);
+    if (wide)
+        hipLaunchKernelGGL(eswoa_wide_kernel, dim3(B), dim3(WNT), lds, (hipStream_t)stream, sh, cand_ptr, len_init, cand, bounds,
+                           start_pos, pop, max_iter, sd, reinterpret_cast<int32_t*>(workspace), best_fitness, best_pos, history, dr);
+    else
+        hipLaunchKernelGGL(eswoa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, sh, cand_ptr, len_init, cand, bounds,
+                           start_pos, pop, max_iter, sd, best_fitness, best_pos, history, dr);
+    GNNPN_CHECK_LAUNCH(entry);
+    return GNNPN_OK;
+}
 
 extern "C" int64_t gnnpn_eswoa_wide_workspace_bytes(int32_t P, int32_t T, int32_t pop) {
     return (int64_t)(P > 0 ? P : 0) * (int64_t)(pop > 0 ? pop : 0) * (int64_t)(T > 0 ? T : 0) * (int64_t)sizeof(int32_t);
@@ -547,21 +574,8 @@ extern "C" int gnnpn_eswoa_wide_f64(int32_t P, int32_t T, const int32_t* cand_pt
     GNNPN_REQUIRE(P >= 0 && T >= 1 && pop > 0 && max_iter >= 0, "eswoa_wide: bad argument");
     if (P == 0) return GNNPN_OK;
     GNNPN_REQUIRE(workspace && workspace_bytes >= gnnpn_eswoa_wide_workspace_bytes(P, T, pop), "eswoa_wide: workspace too small");
-    const size_t lds = eswoa_wide_lds_bytes(T);
-    if (lds > 160 * 1024 - 1024)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_wide: T=%d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", T, lds);
-    if (hipFuncSetAttribute((const void*)eswoa_wide_kernel<FixedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_wide: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(eswoa_wide_kernel<FixedT>, dim3(P), dim3(WNT), lds, (hipStream_t)stream, FixedT{T}, cand_ptr, len_init, cand, bounds,
-                       start_pos, pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds),
-                       reinterpret_cast<int32_t*>(workspace), best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
-    GNNPN_CHECK_LAUNCH("eswoa_wide_f64");
-    return GNNPN_OK;
-}
-
-// LDS bytes one problem needs (host side): scratch + bounds + its candidate table + the population's positions
-static size_t eswoa_lds_bytes(int n_cand, int pop, int T) {
-    return (256 + 4) * sizeof(double) + (size_t)n_cand * 4 * sizeof(double) + (size_t)pop * T * sizeof(int);
+    return eswoa_launch("eswoa_wide", "eswoa_wide_f64", true, P, Shape{nullptr, T, T, T, 0, 0, nullptr}, cand_ptr, len_init, cand,
+                        bounds, start_pos, pop, max_iter, seeds, workspace, best_fitness, best_pos, history, draws, stream);
 }
 
 extern "C" int gnnpn_eswoa_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const int32_t* len_init, const double* cand,
@@ -573,16 +587,8 @@ extern "C" int gnnpn_eswoa_f64(int32_t P, int32_t T, const int32_t* cand_ptr, co
     GNNPN_REQUIRE(P >= 0 && pop > 0 && max_iter >= 0 && max_cand > 0, "eswoa: bad argument");
     if (T < 1 || T > 64) GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa: T=%d categories (this form maps one category to one lane: 1..64; gnnpn_eswoa_wide_f64 takes any T)", T);
     if (P == 0) return GNNPN_OK;
-    const size_t lds = eswoa_lds_bytes(max_cand, pop, T);
-    if (lds > 160 * 1024 - 1024)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", lds, pop, T, max_cand);
-    if (hipFuncSetAttribute((const void*)eswoa_kernel<FixedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(eswoa_kernel<FixedT>, dim3(P), dim3(64), lds, (hipStream_t)stream, FixedT{T}, cand_ptr, len_init, cand, bounds, start_pos,
-                       pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds), best_fitness, best_pos, history,
-                       reinterpret_cast<long long*>(draws));
-    GNNPN_CHECK_LAUNCH("eswoa_f64");
-    return GNNPN_OK;
+    return eswoa_launch("eswoa", "eswoa_f64", false, P, Shape{nullptr, T, T, 64, max_cand, 0, nullptr}, cand_ptr, len_init, cand,
+                        bounds, start_pos, pop, max_iter, seeds, nullptr, best_fitness, best_pos, history, draws, stream);
 }
 
 // ---- a ragged batch: problem p has prob_ptr[p+1] - prob_ptr[p] categories, all problems in ONE launch ----------------------
@@ -601,31 +607,13 @@ extern "C" int gnnpn_eswoa_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_
     GNNPN_REQUIRE(prob_ptr && cand_ptr && len_init && cand && bounds && start_pos && seeds && best_fitness && best_pos && history &&
                   draws, "eswoa_ragged: null operand");
     const bool use_wide = wide || max_slots > 64;
-    if (use_wide) {
+    if (use_wide)
         GNNPN_REQUIRE(workspace && workspace_bytes >= gnnpn_eswoa_ragged_workspace_bytes(n_lists, max_slots, pop, wide),
                       "eswoa_ragged: the workgroup form needs a workspace of gnnpn_eswoa_ragged_workspace_bytes");
-        const size_t lds = eswoa_wide_lds_bytes(max_slots);
-        if (lds > 160 * 1024 - 1024)
-            GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_ragged: %d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", max_slots, lds);
-        if (hipFuncSetAttribute((const void*)eswoa_wide_kernel<RaggedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_ragged: cannot reserve %zu B of LDS", lds);
-        hipLaunchKernelGGL(eswoa_wide_kernel<RaggedT>, dim3(B), dim3(WNT), lds, (hipStream_t)stream,
-                           RaggedT{prob_ptr, max_slots, max_slots, 0, n_lists, best_rows}, cand_ptr, len_init, cand, bounds, start_pos, pop,
-                           max_iter, reinterpret_cast<const unsigned long long*>(seeds), reinterpret_cast<int32_t*>(workspace),
-                           best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
-        GNNPN_CHECK_LAUNCH("eswoa_ragged_f64 (workgroup form)");
-        return GNNPN_OK;
-    }
-    GNNPN_REQUIRE(max_cand >= 1, "eswoa_ragged: max_cand must be >= 1 for the lane-per-category form");
-    const size_t lds = eswoa_lds_bytes(max_cand, pop, max_slots);
-    if (lds > 160 * 1024 - 1024)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "eswoa_ragged: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", lds, pop,
-                   max_slots, max_cand);
-    if (hipFuncSetAttribute((const void*)eswoa_kernel<RaggedT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "eswoa_ragged: cannot reserve %zu B of LDS", lds);
-    hipLaunchKernelGGL(eswoa_kernel<RaggedT>, dim3(B), dim3(64), lds, (hipStream_t)stream, RaggedT{prob_ptr, max_slots, 64, max_cand, n_lists, best_rows},
-                       cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, reinterpret_cast<const unsigned long long*>(seeds),
-                       best_fitness, best_pos, history, reinterpret_cast<long long*>(draws));
-    GNNPN_CHECK_LAUNCH("eswoa_ragged_f64");
-    return GNNPN_OK;
+    else
+        GNNPN_REQUIRE(max_cand >= 1, "eswoa_ragged: max_cand must be >= 1 for the lane-per-category form");
+    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, n_lists, best_rows};
+    return eswoa_launch("eswoa_ragged", use_wide ? "eswoa_ragged_f64 (workgroup form)" : "eswoa_ragged_f64", use_wide, B, sh, cand_ptr,
+                        len_init, cand, bounds, start_pos, pop, max_iter, seeds, workspace, best_fitness, best_pos, history, draws,
+                        stream);
 }

@@ -1032,6 +1032,14 @@ def debug_cell_activations(x):
     return sig, th
 
 
+def _eswoa_buffers(P, row, max_iter, ws_bytes, dev, fill=torch.empty):
+    """Outputs and workspace of one ES-WOA launch over P problems: best_fitness [P] f64, best_pos [P, row] i32 (made by ``fill``),
+    history [P, max(max_iter, 1)] f64, draws [P] i64, workspace of ws_bytes as int32 (one element at least)."""
+    return (torch.empty(P, dtype=F64, device=dev), fill(P, row, dtype=I32, device=dev),
+            torch.empty(P, max(int(max_iter), 1), dtype=F64, device=dev), torch.empty(P, dtype=torch.int64, device=dev),
+            torch.empty(max(ws_bytes // 4, 1), dtype=I32, device=dev))
+
+
 def eswoa(cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, n_cat, wide=None):
     """ES-WOA fine-tuning of P problems in one launch (gnnpn_eswoa_f64 for T <= 64 categories, gnnpn_eswoa_wide_f64 above;
     reference src/baselines/WOA.py:8-162).
@@ -1039,36 +1047,25 @@ def eswoa(cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, n_c
     problem < 0: no seed solution), seeds [P] int64 (bit pattern of the uint64 seed); ``wide`` True forces the any-T kernel
     for T <= 64 as well (tests: both forms give the same run).  Returns (best_fitness [P] f64,
     best_pos [P,T] i32, history [P,max_iter] f64, draws [P] i64)."""
-    dev = cand.device
     T = int(n_cat)
     P = (cand_ptr.numel() - 1) // T
     I64 = torch.int64
-    best_fit = torch.empty(P, dtype=torch.float64, device=dev)
-    best_pos = torch.empty(P, T, dtype=I32, device=dev)
-    history = torch.empty(P, max(int(max_iter), 1), dtype=torch.float64, device=dev)
-    draws = torch.empty(P, dtype=I64, device=dev)
-    if T > 64 or wide:      # one workgroup per problem, positions in a workspace (csrc/woa.hip: eswoa_wide_kernel)
-        lib = _lib.load()
-        nbytes = int(lib.gnnpn_eswoa_wide_workspace_bytes(P, T, int(pop)))
-        ws = torch.empty(max(nbytes // 4, 1), dtype=I32, device=dev)
-        check(lib.gnnpn_eswoa_wide_f64(P, T, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
-                                       dev_ptr(cand, torch.float64, "cand"), dev_ptr(bounds, torch.float64, "bounds"),
-                                       dev_ptr(start_pos, I32, "start_pos"), int(pop), int(max_iter),
-                                       dev_ptr(seeds, I64, "seeds"), dev_ptr(ws, I32, "workspace"), nbytes,
-                                       dev_ptr(best_fit, torch.float64, "best_fitness"), dev_ptr(best_pos, I32, "best_pos"),
-                                       dev_ptr(history, torch.float64, "history"), dev_ptr(draws, I64, "draws"), stream_ptr()),
-              "gnnpn_eswoa_wide_f64")
-        return best_fit, best_pos, history[:, :int(max_iter)], draws
-    per_problem = cand_ptr[T::T] - cand_ptr[:-1:T] if P else cand_ptr[:0]
-    max_cand = int(per_problem.max().item()) if P else 1
-    check(_lib.load().gnnpn_eswoa_f64(P, T, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
-                                      dev_ptr(cand, torch.float64, "cand"), dev_ptr(bounds, torch.float64, "bounds"),
-                                      dev_ptr(start_pos, I32, "start_pos"), int(pop), int(max_iter),
-                                      dev_ptr(seeds, I64, "seeds"), max_cand, dev_ptr(best_fit, torch.float64, "best_fitness"),
-                                      dev_ptr(best_pos, I32, "best_pos"), dev_ptr(history, torch.float64, "history"),
-                                      dev_ptr(draws, I64, "draws"), stream_ptr()), "gnnpn_eswoa_f64")
+    lib = _lib.load()
+    use_wide = T > 64 or bool(wide)     # one workgroup per problem, positions in a workspace (csrc/woa.hip: eswoa_wide_kernel)
+    nbytes = int(lib.gnnpn_eswoa_wide_workspace_bytes(P, T, int(pop))) if use_wide else 0
+    best_fit, best_pos, history, draws, ws = _eswoa_buffers(P, T, max_iter, nbytes, cand.device)
+    operands = (P, T, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"), dev_ptr(cand, F64, "cand"),
+                dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(pop), int(max_iter),
+                dev_ptr(seeds, I64, "seeds"))
+    outputs = (dev_ptr(best_fit, F64, "best_fitness"), dev_ptr(best_pos, I32, "best_pos"), dev_ptr(history, F64, "history"),
+               dev_ptr(draws, I64, "draws"), stream_ptr())
+    if use_wide:
+        check(lib.gnnpn_eswoa_wide_f64(*operands, dev_ptr(ws, I32, "workspace"), nbytes, *outputs), "gnnpn_eswoa_wide_f64")
+    else:
+        per_problem = cand_ptr[T::T] - cand_ptr[:-1:T] if P else cand_ptr[:0]
+        max_cand = int(per_problem.max().item()) if P else 1
+        check(lib.gnnpn_eswoa_f64(*operands, max_cand, *outputs), "gnnpn_eswoa_f64")
     return best_fit, best_pos, history[:, :int(max_iter)], draws
-
 
 
 def debug_round5(x):
@@ -1172,14 +1169,10 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
     if max_cand is None:
         max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
     max_slots, max_cand = max(int(max_slots), 1), max(int(max_cand), 1)
-    best_fit = torch.empty(B, dtype=F64, device=dev)
-    best_pos = torch.zeros(B, max_slots, dtype=I32, device=dev)
-    best_rows = torch.zeros(B, max_slots, 4, dtype=F64, device=dev)
-    history = torch.empty(B, max(int(max_iter), 1), dtype=F64, device=dev)
-    draws = torch.empty(B, dtype=I64, device=dev)
     lib = _lib.load()
     nbytes = int(lib.gnnpn_eswoa_ragged_workspace_bytes(n, max_slots, int(pop), int(bool(wide))))
-    ws = torch.empty(max(nbytes // 4, 1), dtype=I32, device=dev)
+    best_fit, best_pos, history, draws, ws = _eswoa_buffers(B, max_slots, max_iter, nbytes, dev, fill=torch.zeros)
+    best_rows = torch.zeros(B, max_slots, 4, dtype=F64, device=dev)
     check(lib.gnnpn_eswoa_ragged_f64(B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"),
                                      dev_ptr(len_init, I32, "len_init"), dev_ptr(cand, F64, "cand"), dev_ptr(bounds, F64, "bounds"),
                                      dev_ptr(start_pos, I32, "start_pos"), int(pop), int(max_iter), dev_ptr(seeds, I64, "seeds"),

@@ -713,6 +713,9 @@ int gnnpn_debug_mfma_f16(const float* A, const float* B, const float* C, float* 
  *   max_cand         : the largest cand_ptr[(p+1)*T] - cand_ptr[p*T] (sizes the LDS)
  * Outputs: best_fitness [P], best_pos [P*T] (may be negative: Python list positions), history [P*max_iter] (best
  * fitness after every iteration, WOA.py:128,161), draws [P] (stream positions consumed).
+ * This is the launch of gnnpn_eswoa_ragged_f64 (lane-per-category form) with uniform counts: problem p owns entries
+ * p*T .. p*T+T-1, rows of T, no best_rows.  As there, a problem with more candidates than max_cand is not searched:
+ * best_fitness NaN, draws -1, its best_pos and history rows not written.
  * GNNPN_E_UNSUP: T outside 1..64 (one category per lane: use gnnpn_eswoa_wide_f64), or a problem that does not fit a CU's LDS. */
 int gnnpn_eswoa_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const int32_t* len_init, const double* cand,
                     const double* bounds, const int32_t* start_pos, int32_t pop, int32_t max_iter, const uint64_t* seeds,
@@ -723,7 +726,8 @@ int gnnpn_eswoa_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const int32_t
  * population's positions in `workspace` (gnnpn_eswoa_wide_workspace_bytes = P * pop * T int32), the three QoS columns of
  * the composition under evaluation in LDS (24 T + 8 T bytes: T <= ~5000).  Same draws, same float64 evaluation orders
  * (np.cumprod sequential; np.sum pairwise — for n > 128 numpy's recursion: halves rounded down to a multiple of 8), so a
- * run equals gnnpn_eswoa_f64's wherever both apply and the oracle's (oracle/woa.py) everywhere.
+ * run equals gnnpn_eswoa_f64's wherever both apply and the oracle's (oracle/woa.py) everywhere.  This is the workgroup-form
+ * launch of gnnpn_eswoa_ragged_f64 with uniform counts (the candidate table stays in global memory: no max_cand, no guard).
  * GNNPN_E_UNSUP: the columns do not fit a CU's LDS. */
 int64_t gnnpn_eswoa_wide_workspace_bytes(int32_t P, int32_t T, int32_t pop);
 int gnnpn_eswoa_wide_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const int32_t* len_init, const double* cand,
@@ -734,14 +738,15 @@ int gnnpn_eswoa_wide_f64(int32_t P, int32_t T, const int32_t* cand_ptr, const in
 /* The ES-WOA search over a RAGGED batch in one launch: problem p has prob_ptr[p+1] - prob_ptr[p] categories (lists), its
  * entries of cand_ptr / len_init / start_pos are prob_ptr[p] .. prob_ptr[p+1]-1 (cand_ptr has n_lists + 1 entries), the rest
  * as gnnpn_eswoa_f64.  Replaces the per-problem loop of src/baselines/WOA.py:271-288 (one ESWOA per test problem) where
- * problems differ in their number of categories; a problem's run is the one gnnpn_eswoa_f64 / _wide_f64 give it alone.
+ * problems differ in their number of categories; a problem's run is the one gnnpn_eswoa_f64 / _wide_f64 give it alone
+ * (those two are this launch with prob_ptr[p] = p*T: one kernel per form serves all three entry points).
  *   max_slots : the largest category count (rows of best_pos / best_rows); max_slots <= 64 and wide == 0: the
  *               lane-per-category form (max_cand sizes its LDS as in gnnpn_eswoa_f64), else the workgroup form for the whole
  *               launch (workspace of gnnpn_eswoa_ragged_workspace_bytes = pop * n_lists int32, 0 for the lane form)
  * Outputs: best_fitness [B], best_pos [B, max_slots] (entries past a problem's count are not written), best_rows
  * [B, max_slots, 4] or NULL (the recorded best's candidate rows, Python indexing), history [B, max_iter], draws [B].  A
- * problem with no category, more than the launch was sized for, or entries past n_lists is not searched: best_fitness NaN,
- * draws -1. */
+ * problem with no category, more than the launch was sized for (categories: max_slots, 64 in the lane form; candidates:
+ * max_cand in the lane form), or entries past n_lists is not searched: best_fitness NaN, draws -1, its other rows not written. */
 int64_t gnnpn_eswoa_ragged_workspace_bytes(int32_t n_lists, int32_t max_slots, int32_t pop, int32_t wide);
 int gnnpn_eswoa_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
                            const int32_t* cand_ptr, const int32_t* len_init, const double* cand, const double* bounds,

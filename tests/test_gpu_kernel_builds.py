@@ -662,11 +662,16 @@ def test_whh_split_of_the_wrong_size_is_refused(dev):
     ops.check_status(dev)
 
 
-# ---- the ragged ES-WOA search: eswoa_kernel<RaggedT>, eswoa_wide_kernel<RaggedT> ---------------------------------------------------------
-@pytest.mark.parametrize("build,sizes", [("lanes", (1, 3, 10, 33, 64, 7)), ("wide", (5, 64, 65, 100, 2, 130))])
-def test_eswoa_ragged_build(dev, build, sizes):
-    """Problems of different sizes in one ragged launch against oracle/woa.py run live on each of them: the same draws, the
-    same float64 history bit for bit, the same final composition.  With at most 64 categories per problem the launch is the
+# ---- the ES-WOA search: eswoa_kernel, eswoa_wide_kernel, each through the ragged and the fixed entry points -------------------------------
+@pytest.mark.parametrize("build,entry,sizes,per_size", [
+    pytest.param("lanes", "ragged", (1, 3, 10, 33, 64, 7), 2, id="lanes-sizes0"),
+    pytest.param("wide", "ragged", (5, 64, 65, 100, 2, 130), 2, id="wide-sizes1"),
+    pytest.param("lanes", "fixed", (7,), 3, id="lanes-fixed"),
+    pytest.param("wide", "fixed", (65,), 2, id="wide-fixed")])
+def test_eswoa_ragged_build(dev, build, entry, sizes, per_size):
+    """Problems of different sizes in one ragged launch (ops.eswoa_ragged), and problems of one size in one fixed launch
+    (ops.eswoa: the same kernel with uniform counts), against oracle/woa.py run live on each of them: the same draws, the same
+    float64 history bit for bit, the same final composition.  With at most 64 categories per problem the launch is the
     lane-per-category kernel; one problem beyond 64 makes it the workgroup-per-problem ("wide") kernel."""
     import copy
     from oracle import woa as owoa
@@ -677,19 +682,74 @@ def test_eswoa_ragged_build(dev, build, sizes):
     g = np.random.default_rng(sum(sizes) + 1)
     problems = []
     for T in sizes:
-        problems += _random_problems(g, T, 2)
+        problems += _random_problems(g, T, per_size)
     seeds = [77 + 3 * i for i in range(len(problems))]
     pop, iters = 10, 7
     prob_ptr, cand_ptr, flat, len0, start, bounds = _pack(problems)
     t = lambda a, dt: torch.as_tensor(np.asarray(a), dtype=dt).to(dev)      # noqa: E731
-    fit, pos, hist, draws, rows = twice(lambda: ops.eswoa_ragged(
-        t(prob_ptr, torch.int32), t(cand_ptr, torch.int32), t(len0, torch.int32), t(flat, torch.float64).reshape(-1, 4),
-        t(bounds, torch.float64), t(start, torch.int32), pop, iters, t(seeds, torch.int64)))
-    fit, pos, hist, draws, rows = fit.cpu().tolist(), pos.cpu().tolist(), hist.cpu().tolist(), draws.cpu().tolist(), rows.cpu().tolist()
+    tables = (t(cand_ptr, torch.int32), t(len0, torch.int32), t(flat, torch.float64).reshape(-1, 4), t(bounds, torch.float64),
+              t(start, torch.int32), pop, iters, t(seeds, torch.int64))
+    if entry == "ragged":
+        fit, pos, hist, draws, rows = twice(lambda: ops.eswoa_ragged(t(prob_ptr, torch.int32), *tables))
+        rows = rows.cpu().tolist()
+    else:
+        fit, pos, hist, draws = twice(lambda: ops.eswoa(*tables, sizes[0]))
+    fit, pos, hist, draws = fit.cpu().tolist(), pos.cpu().tolist(), hist.cpu().tolist(), draws.cpu().tolist()
     for p, (services, cons, sol) in enumerate(problems):
         T = len(services)
         want = owoa.eswoa(services, cons, copy.deepcopy(sol), pop, iters, owoa.DrawStream(seeds[p]))
         assert draws[p] == want["draws"] and hist[p] == want["history"] and fit[p] == want["best_fitness"], p
         assert pos[p][:T] == [int(v) for v in want["best_pos"]], p
-        assert [tuple(r) for r in rows[p][:T]] == [tuple(r[:4]) for r in want["best_rows"]], p
-    REC.note(f"eswoa_ragged_{build}", exact_cases=len(problems))
+        if entry == "ragged":
+            assert [tuple(r) for r in rows[p][:T]] == [tuple(r[:4]) for r in want["best_rows"]], p
+    REC.note(f"eswoa_{entry}_{build}", exact_cases=len(problems))
+
+
+def test_eswoa_refuses_a_problem_beyond_max_cand(dev):
+    """The lane-per-category kernel copies a problem's candidate table into LDS sized for max_cand rows.  Through the C entry
+    points (ops computes the exact maximum itself): 3 problems of 3 categories with 6, 9 and 6 candidates in a launch sized for
+    6, once through gnnpn_eswoa_f64 and once through gnnpn_eswoa_ragged_f64.  Problem 1 is not searched (best_fitness NaN,
+    draws -1, its best_pos and history rows untouched); problems 0 and 2 run as the oracle does."""
+    import copy
+    import ctypes
+    import math
+    from gnnpn_sc_amd import _lib
+    from oracle import woa as owoa
+    from test_gpu_refine import _pack
+    T, pop, iters, max_cand, sentinel = 3, 4, 2, 6, -12345
+    g = np.random.default_rng(6096)
+    problems = []
+    for p, per_cat in enumerate((2, 3, 2)):
+        services = [[tuple(float(v) for v in np.r_[g.random(2), 1.0 - g.random(2) * 0.2 / T]) for _ in range(per_cat)] for _ in range(T)]
+        sol = [list(cat[int(g.integers(0, per_cat))]) for cat in services] if p == 0 else None      # a seed among its own candidates
+        problems.append((services, [[[0.5, 1.0]], [[0.5, 1.0]]], sol))
+    seeds = [901, 902, 903]
+    prob_ptr, cand_ptr, flat, len0, start, bounds = _pack(problems)
+    assert prob_ptr == [0, 3, 6, 9] and [cand_ptr[3 * (p + 1)] - cand_ptr[3 * p] for p in range(3)] == [6, 9, 6]
+    t = lambda a, dt: torch.as_tensor(np.asarray(a), dtype=dt).to(dev)      # noqa: E731
+    prob_ptr, cand_ptr, len0, start, seeds_d = (t(a, dt) for a, dt in ((prob_ptr, torch.int32), (cand_ptr, torch.int32),
+                                                (len0, torch.int32), (start, torch.int32), (seeds, torch.int64)))
+    flat, bounds = t(flat, torch.float64).reshape(-1, 4), t(bounds, torch.float64)
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr())      # noqa: E731
+    lib, stream = _lib.load(), _lib.stream_ptr()
+    want = {p: owoa.eswoa(problems[p][0], problems[p][1], copy.deepcopy(problems[p][2]), pop, iters, owoa.DrawStream(seeds[p]))
+            for p in (0, 2)}
+    for entry in ("fixed", "ragged"):
+        fit = torch.zeros(3, dtype=torch.float64, device=dev)
+        pos = torch.full((3, T), sentinel, dtype=torch.int32, device=dev)
+        hist = torch.full((3, iters), float(sentinel), dtype=torch.float64, device=dev)
+        draws = torch.zeros(3, dtype=torch.int64, device=dev)
+        if entry == "fixed":
+            rc = lib.gnnpn_eswoa_f64(3, T, ptr(cand_ptr), ptr(len0), ptr(flat), ptr(bounds), ptr(start), pop, iters, ptr(seeds_d),
+                                     max_cand, ptr(fit), ptr(pos), ptr(hist), ptr(draws), stream)
+        else:
+            rc = lib.gnnpn_eswoa_ragged_f64(3, ptr(prob_ptr), 9, T, max_cand, ptr(cand_ptr), ptr(len0), ptr(flat), ptr(bounds),
+                                            ptr(start), pop, iters, ptr(seeds_d), 0, None, 0, ptr(fit), ptr(pos), None, ptr(hist),
+                                            ptr(draws), stream)
+        _lib.check(rc, f"eswoa ({entry})")
+        fit, pos, hist, draws = fit.cpu().tolist(), pos.cpu().tolist(), hist.cpu().tolist(), draws.cpu().tolist()
+        assert math.isnan(fit[1]) and draws[1] == -1, entry
+        assert pos[1] == [sentinel] * T and hist[1] == [float(sentinel)] * iters, entry
+        for p in (0, 2):
+            assert draws[p] == want[p]["draws"] and hist[p] == want[p]["history"] and fit[p] == want[p]["best_fitness"], (entry, p)
+            assert pos[p] == [int(v) for v in want[p]["best_pos"]], (entry, p)
