@@ -43,6 +43,18 @@ inline unsigned gnnpn_lds_padding(const void* func, int target_kb) {
 }
 unsigned gnnpn_front_lds_pad(const void* func);   // api.hip: gnnpn_lds_padding up to the thread's gnnpn_lds_footprint_kb
 
+// The one launch of a kernel that reserves `lds` bytes of dynamic LDS: the reservation is allowed first (required above 64 KB), and a
+// refusal is reported as GNNPN_E_LAUNCH with the entry point's name, the byte count and HIP's reason — nothing is launched then.
+// The arguments are converted to the kernel's parameter types; the caller checks the launch itself (GNNPN_CHECK_LAUNCH).
+template <typename... P, typename... A>
+inline int gnnpn_launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const char* entry,
+                            const A&... args) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot reserve %zu B of LDS: %s", entry, lds, hipGetErrorString(e));
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<P>(args)...);
+    return GNNPN_OK;
+}
+
 // ---- device helpers -------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -219,4 +231,13 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == GNNPN_ACT_RELU) return v < 0.0f ? 0.0f : v;   // NaN stays NaN, as torch.relu
     if (act == GNNPN_ACT_SIGMOID) return sigmoid_f32(v);
     return v;
+}
+// One element of the dense epilogue, act((v + bias) * scale + shift): THE definition of its rounding — the bias add, the multiply
+// and the shift add each round on their own (BatchNorm in inference form after a Linear, as three torch operations).  Used by
+// linear_f32_kernel, the fp32 GIN layer and the gather and LDS-staged aggregates, which is what makes them agree bit for bit;
+// the packed (csr_aggregate_tiled_kernel) and vector (gin_layer_split.hip, request_branch.hip) epilogues spell the same operations.
+__device__ __forceinline__ float epilogue_element(float v, bool has_bias, float bias, bool has_scale, float scale, float shift, int act) {
+    if (has_bias) v = __fadd_rn(v, bias);
+    if (has_scale) v = __fadd_rn(__fmul_rn(v, scale), shift);
+    return apply_act(v, act);
 }

@@ -189,17 +189,8 @@ int launch_glimpse(const DecodeNet& net, const AttnSide& ptr, const AttnSide& gl
     constexpr int NT = H < 64 ? 64 : H;
     const size_t dyn = ((size_t)T * n_per + (size_t)T) * 4;
     if (dyn > 120 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode_attn: seq_len %d does not fit the LDS buffer", T * n_per);
-    const void* k = attention == 1 ? (const void*)pointer_decode_glimpse_kernel<H, true>
-                                   : (const void*)pointer_decode_glimpse_kernel<H, false>;
-    if (dyn > 48 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "pointer_decode_attn: cannot reserve %zu B of LDS", dyn);
-    if (attention == 1)
-        hipLaunchKernelGGL((pointer_decode_glimpse_kernel<H, true>), dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c,
-                           use_tanh, B, T, n_per);
-    else
-        hipLaunchKernelGGL((pointer_decode_glimpse_kernel<H, false>), dim3(B), dim3(NT), dyn, s, net, ptr, gl, inputs, n_glimpses, tanh_c,
-                           use_tanh, B, T, n_per);
-    return GNNPN_OK;
+    return gnnpn_launch_lds(attention == 1 ? pointer_decode_glimpse_kernel<H, true> : pointer_decode_glimpse_kernel<H, false>, dim3(B),
+                            dim3(NT), dyn, s, "pointer_decode_attn_f32", net, ptr, gl, inputs, n_glimpses, tanh_c, use_tanh, B, T, n_per);
 }
 
 }  // namespace

@@ -5,7 +5,8 @@
 // 32x32 MFMA tiles).  Both operands are "row-major with k contiguous" (A[M,K], W[N,K]); tiles go
 // global -> registers -> LDS transposed to k-major so that an MFMA fragment read is 32
 // consecutive floats per half-wave (conflict free), with the next tile's global loads issued
-// before the current tile's MFMAs (register double buffering).
+// before the current tile's MFMAs (register double buffering).  The epilogue element act((v + bias) * scale + shift) is
+// epilogue_element (common.h), shared with the GIN layer and the aggregates.
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(
         __syncthreads();
     }
 
-    // epilogue: D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    // epilogue (epilogue_element, common.h): D[row][col], col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
 #pragma unroll
     for (int j = 0; j < Cfg::TN; ++j) {
         const int col = n0 + wn * (BN / 2) + j * 32 + l32;
@@ -130,10 +131,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(
             for (int r = 0; r < 16; ++r) {
                 const int64_t row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (row >= M) continue;
-                float v = acc[i][j][r];
-                if (bias) v = __fadd_rn(v, bv);
-                if (scale) v = __fadd_rn(__fmul_rn(v, sc), sh);
-                C[row * ldc + col] = apply_act(v, act);
+                C[row * ldc + col] = epilogue_element(acc[i][j][r], bias != nullptr, bv, scale != nullptr, sc, sh, act);
             }
         }
     }

@@ -18,9 +18,11 @@
 // per tile, one workgroup per CU (133 KB of LDS): 2.33 ms for the branch at the 1000-task shape against 2.20 ms layered; the
 // same on 32-row tiles with two workgroups per CU: 1.71 ms.)
 // Every product is the k-ordered fp32 fma chain of the matrix core, zero-padded to whole 32-k tiles exactly as
-// linear_f32_kernel pads, and the aggregate and epilogues round as csr_aggregate_kernel / linear_f32_kernel round:
+// linear_f32_kernel pads; the aggregate (gin_aggregate.h, shared with gin_layer_split.hip) rounds as csr_aggregate_kernel rounds,
+// and the epilogue element is the function linear_f32_kernel and the aggregates call (common.h: epilogue_element):
 // the layer's output is BIT-IDENTICAL to the layered kernels' (tests/test_gpu_ops.py).
 #include "common.h"
+#include "gin_aggregate.h"
 
 namespace {
 
@@ -68,10 +70,7 @@ __device__ __forceinline__ void epilogue(const f32x16& acc, const float* __restr
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-        float v = acc[r];
-        if (bias) v = __fadd_rn(v, bv);
-        if (scale) v = __fadd_rn(__fmul_rn(v, sc), sh);
-        v = apply_act(v, act);
+        const float v = epilogue_element(acc[r], bias != nullptr, bv, scale != nullptr, sc, sh, act);
         if (TO_LDS) Ts[col * LDT + row] = v;
         else if (m0 + row < M) out[(m0 + row) * ldo + col] = v;
     }
@@ -90,8 +89,8 @@ __global__ __launch_bounds__(256, 3) void gin_layer_kernel(
     float* Ts = As + (size_t)(k1a > 128 ? k1a : 128) * LDT;   // [256][LDT]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
     const int64_t m0 = (int64_t)blockIdx.x * BM;
-    // ---- 0. aggregate: 8 lanes per row; a lane's channels: chunks of 4 dealt round-robin (or single channels when rows are not
-    // 16-byte aligned); the edge loop is the OUTER one, so that a lane has all its chunks of a neighbour row in flight at once
+    // ---- 0. aggregate: 8 lanes per row; a lane's channels: chunks of 4 dealt round-robin (gin_aggregate.h), or single channels when
+    // rows are not 16-byte aligned
     {
         const int r = tid >> 3, sub = tid & 7;
         const int64_t row = m0 + r;
@@ -103,41 +102,15 @@ __global__ __launch_bounds__(256, 3) void gin_layer_kernel(
             e1 = rowptr[row + 1];
         }
         if (vec) {
-            float4 acc[NCH_MAX];
-#pragma unroll
-            for (int i = 0; i < NCH_MAX; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int nch = (c_in / 4 - sub + 7) / 8;     // this lane's chunks: 4 * (sub + 8 i) < c_in
-            for (int e = e0; e <= e1; ++e) {              // e == e1: the row itself, scaled by 1 + eps, AFTER the neighbours
-                if (row >= M) break;
-                const bool own = e == e1;
-                const float* src = x + (own ? row : (int64_t)col[e]) * ldx + 4 * sub;
-                float4 t[NCH_MAX];
-#pragma unroll
-                for (int i = 0; i < NCH_MAX; ++i)
-                    if (i < nch) t[i] = *reinterpret_cast<const float4*>(src + 32 * i);
-#pragma unroll
-                for (int i = 0; i < NCH_MAX; ++i)
-                    if (i < nch) {
-                        if (own) {
-                            t[i].x = __fmul_rn(one_plus_eps, t[i].x);
-                            t[i].y = __fmul_rn(one_plus_eps, t[i].y);
-                            t[i].z = __fmul_rn(one_plus_eps, t[i].z);
-                            t[i].w = __fmul_rn(one_plus_eps, t[i].w);
-                        }
-                        acc[i].x = __fadd_rn(acc[i].x, t[i].x);
-                        acc[i].y = __fadd_rn(acc[i].y, t[i].y);
-                        acc[i].z = __fadd_rn(acc[i].z, t[i].z);
-                        acc[i].w = __fadd_rn(acc[i].w, t[i].w);
-                    }
-            }
+            const GinRowSum<NCH_MAX> sum = gin_aggregate_row<NCH_MAX>(col, x, ldx, c_in, row, M, e0, e1, sub, one_plus_eps);
 #pragma unroll
             for (int i = 0; i < NCH_MAX; ++i) {
                 const int c = 4 * (sub + 8 * i);
                 if (c < k1a) {                            // (chunks beyond c_in are the zero padding of the last k-tile)
-                    As[(c + 0) * LDT + r] = acc[i].x;
-                    As[(c + 1) * LDT + r] = acc[i].y;
-                    As[(c + 2) * LDT + r] = acc[i].z;
-                    As[(c + 3) * LDT + r] = acc[i].w;
+                    As[(c + 0) * LDT + r] = sum.chunk[i].x;
+                    As[(c + 1) * LDT + r] = sum.chunk[i].y;
+                    As[(c + 2) * LDT + r] = sum.chunk[i].z;
+                    As[(c + 3) * LDT + r] = sum.chunk[i].w;
                 }
             }
         } else {
@@ -192,17 +165,10 @@ extern "C" int gnnpn_gin_layer_f32(const int32_t* rowptr, const int32_t* col, co
     const int k1a = (c_in + BK - 1) / BK * BK;
     const unsigned lds = (unsigned)(((size_t)(k1a > 128 ? k1a : 128) * LDT + (size_t)H1 * LDT) * sizeof(float));
     dim3 grid((unsigned)((n_rows + BM - 1) / BM)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define GNNPN_GIN_LAYER(L3_)                                                                                                      \
-    do {                                                                                                                        \
-        if (hipFuncSetAttribute((const void*)gin_layer_kernel<L3_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "gin_layer: cannot reserve %u B of LDS", lds);                                           \
-        hipLaunchKernelGGL((gin_layer_kernel<L3_>), grid, block, lds, st, rowptr, col, x, ldx, c_in, eps, w1, b1, bn1_scale,    \
-                           bn1_shift, w2, b2, bn2_scale, bn2_shift, w3, b3, out, ldo, n_rows, k1a);                             \
-    } while (0)
-    if (lin3) GNNPN_GIN_LAYER(true);
-    else GNNPN_GIN_LAYER(false);
-#undef GNNPN_GIN_LAYER
+    if (const int rc = gnnpn_launch_lds(lin3 ? gin_layer_kernel<true> : gin_layer_kernel<false>, grid, block, lds, (hipStream_t)stream,
+                                        "gin_layer_f32", rowptr, col, x, ldx, c_in, eps, w1, b1, bn1_scale, bn1_shift, w2, b2, bn2_scale,
+                                        bn2_shift, w3, b3, out, ldo, n_rows, k1a))
+        return rc;
     GNNPN_CHECK_LAUNCH("gin_layer_f32");
     return GNNPN_OK;
 }

@@ -2,7 +2,8 @@
 // of coop_common.h (the arithmetic the recurrent kernels use; profiles/LOG_r01_r04.md section 12): every fp32 operand — activations and
 // weights — is decomposed into three fp16 pieces that reproduce it bit for bit, the six cross products that can reach
 // 2^-24 of a term run on v_mfma_f32_16x16x32_f16 into three fp32 accumulators (one per magnitude class), and nothing else
-// of the layer changes: the neighbour aggregate, bias, BatchNorm and ReLU are the fp32 instructions of gin_layer.hip.
+// of the layer changes: the neighbour aggregate is gin_layer.hip's (gin_aggregate.h), and bias, BatchNorm and ReLU are the fp32
+// operations of epilogue_element (common.h) on four features at a time.
 // Replaces, per layer, GINConv.propagate + nn (Linear, BN, ReLU, Linear, ReLU) + BN + ReLU [+ nodeLin],
 // modelML.py:75-93,139-143,165.  6 x 126 GFLOP of f16 products at the 1000-task shape: 0.30 ms of matrix time against the
 // 0.80 ms of the fp32 matrix core.
@@ -21,6 +22,7 @@
 // Accuracy: tests/test_gpu_ops.py measures the layer against an fp64 evaluation next to the fp32 kernels'.
 #include "common.h"
 #include "coop_common.h"
+#include "gin_aggregate.h"
 
 // (The timing-only builds and the tile / depth / occupancy / piece-form variants that were measured and not kept live in
 // tools/experiments/gin_layer_split_switches.patch, applied by tools/ablate_gin_layer.py; profiles/LOG_r01_r04.md has the numbers.)
@@ -153,7 +155,7 @@ __device__ __forceinline__ void split_gemm(const _Float16* a_lane, int lda, int 
 __device__ __forceinline__ f32x4 load4_or(const float* p, int at, float dflt) {
     return p ? *reinterpret_cast<const f32x4*>(p + at) : f32x4{dflt, dflt, dflt, dflt};
 }
-// (v * row factor + bias) * scale + shift, activation — the fp32 epilogue of linear_f32_kernel
+// (v * row factor + bias) * scale + shift, activation — epilogue_element (common.h) defines the rounding; here on f32x4
 __device__ __forceinline__ void finish(f32x4 (&v)[RT][NCT], const float (&rinv)[RT], const float* __restrict__ bias,
                                        const float* __restrict__ scale, const float* __restrict__ shift, int act, int ct0, int kq) {
 #pragma unroll
@@ -164,7 +166,7 @@ __device__ __forceinline__ void finish(f32x4 (&v)[RT][NCT], const float (&rinv)[
         for (int rt = 0; rt < RT; ++rt) {
             f32x4 t = v[rt][n] * rinv[rt];
             if (bias) t = t + bv;
-            if (scale) t = t * sc + sh;                      // (-ffp-contract=off: a multiply and an add, as linear_f32_kernel rounds)
+            if (scale) t = t * sc + sh;                      // (-ffp-contract=off: a multiply and an add, as epilogue_element rounds)
 #pragma unroll
             for (int r = 0; r < 4; ++r) t[r] = apply_act(t[r], act);
             v[rt][n] = t;
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void gin_layer_split_kernel(
     const int64_t m0 = (int64_t)blockIdx.x * BM;
     const int pieceA = BM * lda, pieceT = BM * ldt, pieceA3 = BM * lda3;
     BFrag q[DEPTH][NCT];
-    // ---- 0. aggregate (the fp32 instructions of gin_layer_kernel), 8 lanes per row, then scale + split
+    // ---- 0. aggregate (gin_aggregate.h: the function gin_layer_kernel calls), 8 lanes per row, then scale + split
     for (int r = tid >> 3; r < BM; r += 32) {
         const int sub = tid & 7;
         const int64_t row = m0 + r;
@@ -268,35 +270,13 @@ __global__ __launch_bounds__(256, 2) void gin_layer_split_kernel(
             e1 = rowptr[row + 1];
         }
         if (r < 32) prefetch_b(w1, 4 * wave, k1a / 32, lane, q);   // the first product's first weights travel under the aggregate's gathers
-        float4 acc[NCH_MAX];
-#pragma unroll
-        for (int i = 0; i < NCH_MAX; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        GinRowSum<NCH_MAX> sum;
+        float4 (&acc)[NCH_MAX] = sum.chunk;
         if (vec) {
-            const int nch = (c_in / 4 - sub + 7) / 8;
-            for (int e = e0; e <= e1; ++e) {
-                if (row >= M) break;
-                const bool own = e == e1;
-                const float* src = x + (own ? row : (int64_t)col[e]) * ldx + 4 * sub;
-                float4 t[NCH_MAX];
-#pragma unroll
-                for (int i = 0; i < NCH_MAX; ++i)
-                    if (i < nch) t[i] = *reinterpret_cast<const float4*>(src + 32 * i);
-#pragma unroll
-                for (int i = 0; i < NCH_MAX; ++i)
-                    if (i < nch) {
-                        if (own) {
-                            t[i].x = __fmul_rn(one_plus_eps, t[i].x);
-                            t[i].y = __fmul_rn(one_plus_eps, t[i].y);
-                            t[i].z = __fmul_rn(one_plus_eps, t[i].z);
-                            t[i].w = __fmul_rn(one_plus_eps, t[i].w);
-                        }
-                        acc[i].x = __fadd_rn(acc[i].x, t[i].x);
-                        acc[i].y = __fadd_rn(acc[i].y, t[i].y);
-                        acc[i].z = __fadd_rn(acc[i].z, t[i].z);
-                        acc[i].w = __fadd_rn(acc[i].w, t[i].w);
-                    }
-            }
+            sum = gin_aggregate_row<NCH_MAX>(col, x, ldx, c_in, row, M, e0, e1, sub, one_plus_eps);
         } else {                                            // c_in <= 32 (the host checks): channel 4 sub + j of chunk 0
+#pragma unroll
+            for (int i = 0; i < NCH_MAX; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (row < M) {
                 float s[4] = {0.f, 0.f, 0.f, 0.f};
                 for (int e = e0; e < e1; ++e) {
@@ -474,19 +454,11 @@ extern "C" int gnnpn_gin_layer_split(const int32_t* rowptr, const int32_t* col, 
     const int k1a = (c_in + 31) / 32 * 32;
     const unsigned lds = (unsigned)((size_t)3 * BM * (H1 + 8) * 2 + 5 * BM * sizeof(float));   // k1a <= 128 < H1: every operand fits T's tile
     dim3 grid((unsigned)((n_rows + BM - 1) / BM)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define GNNPN_GIN_SPLIT(L3_)                                                                                                    \
-    do {                                                                                                                        \
-        if (hipFuncSetAttribute((const void*)gin_layer_split_kernel<L3_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != \
-            hipSuccess)                                                                                                         \
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "gin_layer_split: cannot reserve %u B of LDS", lds);                                     \
-        hipLaunchKernelGGL((gin_layer_split_kernel<L3_>), grid, block, lds, st, rowptr, col, x, ldx, c_in, eps,                 \
-                           (const unsigned char*)w1, inv1, b1, bn1_scale, bn1_shift, (const unsigned char*)w2, inv2, b2, bn2_scale, \
-                           bn2_shift, (const unsigned char*)w3, inv3, b3, out, ldo, n_rows, k1a, (int)vec);                             \
-    } while (0)
-    if (lin3) GNNPN_GIN_SPLIT(true);
-    else GNNPN_GIN_SPLIT(false);
-#undef GNNPN_GIN_SPLIT
+    if (const int rc = gnnpn_launch_lds(lin3 ? gin_layer_split_kernel<true> : gin_layer_split_kernel<false>, grid, block, lds,
+                                        (hipStream_t)stream, "gin_layer_split", rowptr, col, x, ldx, c_in, eps, (const unsigned char*)w1,
+                                        inv1, b1, bn1_scale, bn1_shift, (const unsigned char*)w2, inv2, b2, bn2_scale, bn2_shift,
+                                        (const unsigned char*)w3, inv3, b3, out, ldo, n_rows, k1a, (int)vec))
+        return rc;
     GNNPN_CHECK_LAUNCH("gin_layer_split");
     return GNNPN_OK;
 }

@@ -4,6 +4,8 @@
 // coalesced load per array and broadcast lane-by-lane, feature rows read as whole 16 B/lane
 // coalesced rows, 4 neighbour rows in flight per wave, accumulation strictly in CSR order with
 // separate multiply and add (the rounding of a materialised message followed by scatter_add).
+// What follows a row's sum and its GIN self term — + bias, * scale + shift, activation — is epilogue_element (common.h) in
+// both aggregate kernels of this file: the function linear_f32_kernel ends with.
 #include "common.h"
 #include "graph_lds.h"
 
@@ -85,9 +87,13 @@ __global__ __launch_bounds__(256) void csr_aggregate_kernel(
         for (int v = 0; v < V; ++v) {
             float r = acc[v];
             if (self_coef) r = __fadd_rn(r, __fmul_rn(one_plus_eps, x[(int64_t)row * ldx + c + v]));
-            if (bias) r = __fadd_rn(r, bias[c + v]);
-            if (scale) r = __fadd_rn(__fmul_rn(r, scale[c + v]), shift[c + v]);
-            acc[v] = apply_act(r, act);
+            float bv = 0.0f, sc = 1.0f, sh = 0.0f;
+            if (bias) bv = bias[c + v];
+            if (scale) {
+                sc = scale[c + v];
+                sh = shift[c + v];
+            }
+            acc[v] = epilogue_element(r, bias != nullptr, bv, scale != nullptr, sc, sh, act);
         }
         float* dst = y + (int64_t)row * ldy + c;
         if (VEC4) {
@@ -107,8 +113,7 @@ extern "C" int gnnpn_csr_aggregate_f32(const int32_t* rowptr, const int32_t* col
     GNNPN_REQUIRE(rowptr && x && y, "csr_aggregate: null operand");
     GNNPN_REQUIRE((scale == nullptr) == (shift == nullptr), "csr_aggregate: scale and shift go together");
     GNNPN_REQUIRE(x != y, "csr_aggregate: in-place aggregation is not supported");
-    if (n_rows == 0) return GNNPN_OK;
-    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && gnnpn_aligned(x, 16) && gnnpn_aligned(y, 16);
+    const bool vec = agg_rows_vec4(x, ldx, y, ldy, C);
     dim3 grid((n_rows + 3) / 4), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (vec)
@@ -133,7 +138,8 @@ extern "C" int gnnpn_csr_aggregate_f32(const int32_t* rowptr, const int32_t* col
 // (the next batch's while the current one is consumed) and the lanes of a row take each other's entries by DPP quad
 // permutes; rows are dealt to the waves by descending degree (gnnpn_csr_block_row_order) so that rows walking in step have
 // the same length.  Sums are strictly in CSR order with separately rounded (packed) multiply and add: bit-identical to
-// csr_aggregate_kernel.  24.7 % of the HBM roofline at 2507 x 256 copies (gather form 15.4 %); what bounds it: DESIGN.md 8.
+// csr_aggregate_kernel (the epilogue element is the same function, common.h: epilogue_element).  24.7 % of the HBM roofline
+// at 2507 x 256 copies (gather form 15.4 %); what bounds it: DESIGN.md 8.
 // Placement (speed only): the SLICE-WGs of one block get equal blockIdx % 8 (one XCD), so the two halves of every 128-B
 // line of x — read by two different slices — meet in that XCD's L2 and the (col, w) lists are fetched from HBM once.
 // the 4 consecutive (col, w) entries at idx of one lane of a row's lane group.  SAFE = no row of the wave ends within 4
@@ -274,9 +280,7 @@ __global__ __launch_bounds__(1024) void csr_aggregate_lds_kernel(
         for (int v = 0; v < 4; ++v) {
             float t = acc[v];
             if (self_coef) t = __fadd_rn(t, __fmul_rn(one_plus_eps, o4[v]));
-            if (bias) t = __fadd_rn(t, bv[v]);
-            if (scale) t = __fadd_rn(__fmul_rn(t, sc[v]), sh[v]);
-            acc[v] = apply_act(t, act);
+            acc[v] = epilogue_element(t, bias != nullptr, bv[v], scale != nullptr, sc[v], sh[v], act);
         }
         *reinterpret_cast<float4*>(y + (int64_t)(r0 + r) * ldy + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
@@ -291,7 +295,7 @@ extern "C" int gnnpn_csr_aggregate_blocks_f32(const int32_t* rowptr, const int32
     GNNPN_REQUIRE((scale == nullptr) == (shift == nullptr), "csr_aggregate_blocks: scale and shift go together");
     GNNPN_REQUIRE(x != y, "csr_aggregate_blocks: in-place aggregation is not supported");
     if (n_rows == 0) return GNNPN_OK;
-    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && gnnpn_aligned(x, 16) && gnnpn_aligned(y, 16);
+    const bool vec = agg_rows_vec4(x, ldx, y, ldy, C);
     constexpr int64_t LDS_BYTES = 160 * 1024;
     int lpr = 0;                                   // lanes per row = SLICE / 4: the widest slice whose block fits the LDS
     for (int cand = 4; cand >= 1; cand >>= 1)
@@ -305,22 +309,15 @@ extern "C" int gnnpn_csr_aggregate_blocks_f32(const int32_t* rowptr, const int32
     const int n_blocks = (n_rows + block_rows - 1) / block_rows, n_slices = C / (4 * lpr);
     const unsigned lds = (unsigned)(((int64_t)block_rows + 1) * 16 * lpr);
     dim3 grid((unsigned)(((n_blocks + 7) / 8) * n_slices * 8)), block(1024);
-    hipStream_t st = (hipStream_t)stream;
-#define GNNPN_AGG_LDS(LPR_, W_)                                                                                          \
-    do {                                                                                                                 \
-        if (hipFuncSetAttribute((const void*)csr_aggregate_lds_kernel<LPR_, W_>,                                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)                      \
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "csr_aggregate_blocks: cannot reserve %u B of LDS", lds);                          \
-        hipLaunchKernelGGL((csr_aggregate_lds_kernel<LPR_, W_>), grid, block, lds, st, rowptr, col, w, x, ldx, self_coef, \
-                           bias, scale, shift, act, y, ldy, n_rows, C, block_rows, n_blocks, n_slices, row_order);       \
-    } while (0)
-    if (lpr == 4 && w) GNNPN_AGG_LDS(4, true);
-    else if (lpr == 4) GNNPN_AGG_LDS(4, false);
-    else if (lpr == 2 && w) GNNPN_AGG_LDS(2, true);
-    else if (lpr == 2) GNNPN_AGG_LDS(2, false);
-    else if (w) GNNPN_AGG_LDS(1, true);
-    else GNNPN_AGG_LDS(1, false);
-#undef GNNPN_AGG_LDS
+    // the six builds, by (lanes per row: 1, 2, 4; weighted)
+    static constexpr decltype(&csr_aggregate_lds_kernel<1, false>) BUILDS[3][2] = {
+        {csr_aggregate_lds_kernel<1, false>, csr_aggregate_lds_kernel<1, true>},
+        {csr_aggregate_lds_kernel<2, false>, csr_aggregate_lds_kernel<2, true>},
+        {csr_aggregate_lds_kernel<4, false>, csr_aggregate_lds_kernel<4, true>}};
+    if (const int rc = gnnpn_launch_lds(BUILDS[lpr >> 1][w != nullptr], grid, block, lds, (hipStream_t)stream, "csr_aggregate_blocks_f32",
+                                        rowptr, col, w, x, ldx, self_coef, bias, scale, shift, act, y, ldy, n_rows, C, block_rows,
+                                        n_blocks, n_slices, row_order))
+        return rc;
     GNNPN_CHECK_LAUNCH("csr_aggregate_blocks_f32");
     return GNNPN_OK;
 }
@@ -368,11 +365,10 @@ extern "C" int gnnpn_csr_block_row_order(const int32_t* rowptr, int32_t n_rows, 
     int P = 2;
     while (P < block_rows) P <<= 1;
     const unsigned lds = (unsigned)P * 4u;
-    if (hipFuncSetAttribute((const void*)csr_block_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "csr_block_row_order: cannot reserve %u B of LDS", lds);
     const int n_blocks = (n_rows + block_rows - 1) / block_rows;
-    hipLaunchKernelGGL(csr_block_order_kernel, dim3((unsigned)n_blocks), dim3(1024), lds, (hipStream_t)stream, rowptr, n_rows,
-                       block_rows, P, row_order);
+    if (const int rc = gnnpn_launch_lds(csr_block_order_kernel, dim3((unsigned)n_blocks), dim3(1024), lds, (hipStream_t)stream,
+                                        "csr_block_row_order", rowptr, n_rows, block_rows, P, row_order))
+        return rc;
     GNNPN_CHECK_LAUNCH("csr_block_row_order");
     return GNNPN_OK;
 }

@@ -13,6 +13,11 @@ __device__ __forceinline__ int quad_from(int v) {
     else return v;
 }
 
+// host: x and y rows that a lane reads and writes in 16-byte pieces — what the vector forms of the three aggregate entry points need
+static inline bool agg_rows_vec4(const float* x, int64_t ldx, const float* y, int64_t ldy, int C) {
+    return C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && gnnpn_aligned(x, 16) && gnnpn_aligned(y, 16);
+}
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(4))) i32x4_u { int32_t v[4]; };     // 16 bytes at 4-byte alignment: one global_load_dwordx4
 struct __attribute__((packed, aligned(4))) f32x4_u { float v[4]; };

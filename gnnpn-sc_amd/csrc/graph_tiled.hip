@@ -472,7 +472,8 @@ __global__ __launch_bounds__(WAVES * 64) void csr_aggregate_tiled_kernel(
             }
         }
     }
-    // ---- epilogue: the trailing self loop of rows outside the last source tile, then what the gather form's epilogue does.
+    // ---- epilogue: the trailing self loop of rows outside the last source tile, then what the gather form's epilogue does (GIN self
+    // term, then the operations of epilogue_element, common.h, which defines their rounding).
     // Every condition but `has_loop` is uniform over the launch: the stages run pass by pass on the packed accumulators, with the
     // uniform tests outside the element arithmetic (round 5: the per-element test chain with an inlined sigmoid per element was
     // 1.8 k instructions and 13 % of the launch, issue-bound — profiles/r05_aggregate_phases.json).
@@ -569,6 +570,16 @@ __global__ __launch_bounds__(WAVES * 64) void csr_aggregate_tiled_kernel(
     }
 }
 
+// The 24 builds: TILED_WALK<two-quad walk>[header registers - 1][passes - 1]; two header registers are only built for 9 and 10 passes.
+using TiledKernel = decltype(&csr_aggregate_tiled_kernel<1, 1, false>);
+template <int PASSES, int HREGS, bool PAIRS>
+constexpr TiledKernel tiled = csr_aggregate_tiled_kernel<PASSES, HREGS, PAIRS>;
+template <bool X>
+constexpr TiledKernel TILED_WALK[2][PASSES_MAX] = {
+    {tiled<1, 1, X>, tiled<2, 1, X>, tiled<3, 1, X>, tiled<4, 1, X>, tiled<5, 1, X>, tiled<6, 1, X>, tiled<7, 1, X>, tiled<8, 1, X>,
+     tiled<9, 1, X>, tiled<10, 1, X>},
+    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tiled<9, 2, X>, tiled<10, 2, X>}};
+
 }  // namespace
 
 extern "C" int gnnpn_csr_tile_plan_geometry(int32_t n_rows, int32_t block_rows, gnnpn_tile_plan_geom_t* out) {
@@ -605,10 +616,10 @@ extern "C" int gnnpn_csr_tile_plan_rows(const int32_t* rowptr, const int32_t* co
     int P = 16;
     while (P < g.U * 16) P <<= 1;
     const unsigned lds = (unsigned)((size_t)P * 10 + (size_t)g.DR * g.NT * 2 + (HIST_BINS + 4) * 4 + (size_t)g.DR * 4 + 16);
-    if (hipFuncSetAttribute((const void*)tile_plan_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "csr_tile_plan_rows: cannot reserve %u B of LDS", lds);
-    hipLaunchKernelGGL(tile_plan_rows_kernel, dim3((unsigned)(g.n_blocks * g.ND)), dim3(1024), lds, st, rowptr, col, w, n_rows, g, P,
-                       header, order, tstart, selfw, reinterpret_cast<unsigned*>(meta));
+    if (const int rc = gnnpn_launch_lds(tile_plan_rows_kernel, dim3((unsigned)(g.n_blocks * g.ND)), dim3(1024), lds, st,
+                                        "csr_tile_plan_rows", rowptr, col, w, n_rows, g, P, header, order, tstart, selfw,
+                                        reinterpret_cast<unsigned*>(meta)))
+        return rc;
     const int64_t n = (int64_t)g.n_blocks * g.ND * g.NT * g.U;
     hipLaunchKernelGGL(tile_plan_scan_kernel, dim3(1), dim3(1024), 0, st, header, n, reinterpret_cast<unsigned*>(meta));
     GNNPN_CHECK_LAUNCH("csr_tile_plan_rows");
@@ -642,8 +653,7 @@ extern "C" int gnnpn_csr_aggregate_tiled_f32(const int32_t* header, const int32_
     GNNPN_REQUIRE((int64_t)block_rows * ldx < (1ll << 29) && (int64_t)block_rows * ldy < (1ll << 29),
                   "csr_aggregate_tiled: a block's rows must span less than 2 GiB (32-bit offsets inside a block)");
     Geom g;
-    const bool vec = (C % 16 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && gnnpn_aligned(x, 16) && gnnpn_aligned(y, 16) &&
-                     gnnpn_aligned(batches, 16);
+    const bool vec = C % 16 == 0 && agg_rows_vec4(x, ldx, y, ldy, C) && gnnpn_aligned(batches, 16);
     if (!vec || !tile_geometry(n_rows, block_rows, g))
         GNNPN_FAIL(GNNPN_E_UNSUP, "csr_aggregate_tiled: %d channels (a multiple of 16, 16-byte aligned rows) in blocks of %d rows "
                    "(at most %d source tiles of %d) do not fit the tiled form: use gnnpn_csr_aggregate_f32", C, block_rows,
@@ -652,48 +662,16 @@ extern "C" int gnnpn_csr_aggregate_tiled_f32(const int32_t* header, const int32_
     const unsigned lds = (unsigned)(g.TR + 1) * 64u;
     const int n_jj = ((g.n_blocks + 7) / 8) * g.ND * n_slices;
     dim3 grid((unsigned)(n_jj * 8)), block(WAVES * 64);
-    hipStream_t st = (hipStream_t)stream;
     // which walk (speed only: the two give the same bits).  GNNPN_TILED_WALK = quads | pairs overrides the rule (tests run both).
     const char* walk = getenv("GNNPN_TILED_WALK");
     const bool pairs = walk && walk[0] == 'p' ? true : walk && walk[0] == 'q' ? false : g.NT >= 3;
-#define GNNPN_AGG_TILED(P_, H_)                                                                                             \
-    do {                                                                                                                  \
-        if (hipFuncSetAttribute((const void*)csr_aggregate_tiled_kernel<P_, H_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds) != hipSuccess)                                                                  \
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "csr_aggregate_tiled: cannot reserve %u B of LDS", lds);                           \
-        if (pairs) {                                                                                                      \
-            if (hipFuncSetAttribute((const void*)csr_aggregate_tiled_kernel<P_, H_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)lds) != hipSuccess)                                                              \
-                GNNPN_FAIL(GNNPN_E_LAUNCH, "csr_aggregate_tiled: cannot reserve %u B of LDS", lds);                       \
-            hipLaunchKernelGGL((csr_aggregate_tiled_kernel<P_, H_, true>), grid, block, lds, st, reinterpret_cast<const int2*>(header), \
-                               order, selfw, static_cast<const uint4*>(batches), x, ldx, self_coef, bias, scale, shift, act, \
-                               y, ldy, n_rows, g, n_slices);                                                        \
-        } else                                                                                                            \
-        hipLaunchKernelGGL((csr_aggregate_tiled_kernel<P_, H_>), grid, block, lds, st, reinterpret_cast<const int2*>(header), \
-                           order, selfw, static_cast<const uint4*>(batches), x, ldx, self_coef, bias, scale, shift, act, \
-                           y, ldy, n_rows, g, n_slices);                                                            \
-    } while (0)
     // more than 64 (source tile, pass) headers per wavefront only occur with 7 or 8 source tiles, i.e. full destination tiles
-    switch (g.passes) {
-        case 1: GNNPN_AGG_TILED(1, 1); break;
-        case 2: GNNPN_AGG_TILED(2, 1); break;
-        case 3: GNNPN_AGG_TILED(3, 1); break;
-        case 4: GNNPN_AGG_TILED(4, 1); break;
-        case 5: GNNPN_AGG_TILED(5, 1); break;
-        case 6: GNNPN_AGG_TILED(6, 1); break;
-        case 7: GNNPN_AGG_TILED(7, 1); break;
-        case 8: GNNPN_AGG_TILED(8, 1); break;
-        default:
-            if (g.NT * g.passes <= 64) {
-                if (g.passes == 9) GNNPN_AGG_TILED(9, 1);
-                else GNNPN_AGG_TILED(10, 1);
-            } else {
-                if (g.passes == 9) GNNPN_AGG_TILED(9, 2);
-                else GNNPN_AGG_TILED(10, 2);
-            }
-            break;
-    }
-#undef GNNPN_AGG_TILED
+    const int hregs = g.NT * g.passes <= 64 ? 1 : 2;
+    if (const int rc = gnnpn_launch_lds((pairs ? TILED_WALK<true> : TILED_WALK<false>)[hregs - 1][g.passes - 1], grid, block, lds, (hipStream_t)stream,
+                                        "csr_aggregate_tiled_f32", reinterpret_cast<const int2*>(header), order, selfw,
+                                        static_cast<const uint4*>(batches), x, ldx, self_coef, bias, scale, shift, act, y, ldy, n_rows, g,
+                                        n_slices))
+        return rc;
     GNNPN_CHECK_LAUNCH("csr_aggregate_tiled_f32");
     return GNNPN_OK;
 }

@@ -2,7 +2,8 @@
 // per-row ranking.  Integer/compare work, HBM-bound on the score rows: one wavefront per
 // (problem, category) segment, each lane scanning a strided share of the segment; the K picks are
 // K wave-wide max-reductions over 64-bit keys (score order bits : inverted id), so ties resolve to
-// the lowest service id and the result does not depend on lane count or launch geometry.
+// the lowest service id and the result does not depend on lane count or launch geometry.  The two full-ranking kernels share one
+// bitonic network (bitonic_sort_desc): on 64-bit keys, or on ids that form their keys from the score row.
 #include <vector>
 
 #include "common.h"
@@ -206,28 +207,35 @@ extern "C" int gnnpn_select_candidates(const float* scores, int64_t ld_scores, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// Full ranking of one score row per workgroup: bitonic sort of 64-bit keys in LDS (descending).
-__global__ __launch_bounds__(1024) void rank_rows_kernel(const float* __restrict__ scores, int64_t ld_scores,
-                                                         int32_t* __restrict__ ranking, int32_t S, int32_t P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
-    const float* srow = scores + (int64_t)blockIdx.x * ld_scores;
-    for (int i = threadIdx.x; i < P; i += blockDim.x) keys[i] = i < S ? rank_key(srow[i], (uint32_t)i) : 0ull;
-    __syncthreads();
+// The bitonic network of a workgroup over the P (a power of two) slots in LDS, descending by `less` on two slot values.  Every
+// thread of the workgroup calls it, after a barrier behind the slots' initialisation; it ends with a barrier.
+template <typename Slot, typename Less>
+__device__ __forceinline__ void bitonic_sort_desc(Slot* __restrict__ slots, int P, Less less) {
     for (int k = 2; k <= P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
                 const int i = 2 * t - (t & (j - 1));   // lower index of the pair (bit j clear)
                 const int p = i + j;
                 const bool desc = (i & k) == 0;        // descending blocks first -> overall descending
-                const unsigned long long a = keys[i], b = keys[p];
-                if ((a < b) == desc) {
-                    keys[i] = b;
-                    keys[p] = a;
+                const Slot a = slots[i], b = slots[p];
+                if (less(a, b) == desc) {
+                    slots[i] = b;
+                    slots[p] = a;
                 }
             }
             __syncthreads();
         }
     }
+}
+
+// Full ranking of one score row per workgroup: bitonic sort of 64-bit keys in LDS (descending; ties -> lowest id).
+__global__ __launch_bounds__(1024) void rank_rows_kernel(const float* __restrict__ scores, int64_t ld_scores,
+                                                         int32_t* __restrict__ ranking, int32_t S, int32_t P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    const float* srow = scores + (int64_t)blockIdx.x * ld_scores;
+    for (int i = threadIdx.x; i < P; i += blockDim.x) keys[i] = i < S ? rank_key(srow[i], (uint32_t)i) : 0ull;
+    __syncthreads();
+    bitonic_sort_desc(keys, P, [](unsigned long long a, unsigned long long b) { return a < b; });
     int32_t* out = ranking + (int64_t)blockIdx.x * S;
     for (int i = threadIdx.x; i < S; i += blockDim.x) out[i] = (int32_t)(0xffffffffu - (uint32_t)(keys[i] & 0xffffffffu));
 }
@@ -242,21 +250,7 @@ __global__ __launch_bounds__(1024) void rank_rows_indirect_kernel(const float* _
     auto key_of = [&](unsigned int i) { return i < (unsigned)S ? rank_key(srow[i], i) : 0ull; };
     for (int i = threadIdx.x; i < P; i += blockDim.x) ids[i] = (unsigned)i;
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-                const int i = 2 * t - (t & (j - 1));
-                const int p = i + j;
-                const bool desc = (i & k) == 0;
-                const unsigned int ia = ids[i], ib = ids[p];
-                if ((key_of(ia) < key_of(ib)) == desc) {
-                    ids[i] = ib;
-                    ids[p] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_desc(ids, P, [&](unsigned int ia, unsigned int ib) { return key_of(ia) < key_of(ib); });
     int32_t* out = ranking + (int64_t)blockIdx.x * S;
     for (int i = threadIdx.x; i < S; i += blockDim.x) out[i] = (int32_t)ids[i];
 }
@@ -267,23 +261,13 @@ extern "C" int gnnpn_rank_rows(const float* scores, int64_t ld_scores, int32_t* 
     if (B == 0) return GNNPN_OK;
     GNNPN_REQUIRE(scores && ranking, "rank_rows: null operand");
     if (S > 32768) GNNPN_FAIL(GNNPN_E_UNSUP, "rank_rows: S=%d exceeds the single-workgroup LDS sort (32768)", S);
-    if (B == 0) return GNNPN_OK;
     int P = 2;
     while (P < S) P <<= 1;
-    if (S > 16384) {
-        const size_t lds_i = (size_t)P * sizeof(unsigned int);
-        hipError_t ei = hipFuncSetAttribute((const void*)rank_rows_indirect_kernel,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_i);
-        if (ei != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "rank_rows: cannot reserve %zu B of LDS: %s", lds_i, hipGetErrorString(ei));
-        hipLaunchKernelGGL(rank_rows_indirect_kernel, dim3(B), dim3(1024), lds_i, (hipStream_t)stream, scores, ld_scores,
-                           ranking, S, P);
-        GNNPN_CHECK_LAUNCH("rank_rows");
-        return GNNPN_OK;
-    }
-    const size_t lds = (size_t)P * sizeof(unsigned long long);
-    hipError_t e = hipFuncSetAttribute((const void*)rank_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "rank_rows: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-    hipLaunchKernelGGL(rank_rows_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, scores, ld_scores, ranking, S, P);
+    const bool indirect = S > 16384;                                   // the 64-bit keys no longer fit the LDS: sort ids
+    const size_t lds = (size_t)P * (indirect ? sizeof(unsigned int) : sizeof(unsigned long long));
+    if (const int rc = gnnpn_launch_lds(indirect ? rank_rows_indirect_kernel : rank_rows_kernel, dim3(B), dim3(1024), lds,
+                                        (hipStream_t)stream, "rank_rows", scores, ld_scores, ranking, S, P))
+        return rc;
     GNNPN_CHECK_LAUNCH("rank_rows");
     return GNNPN_OK;
 }

@@ -276,14 +276,6 @@ int check(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_pe
     return GNNPN_OK;
 }
 
-// above 64 KB the dynamic LDS must be allowed first: a refusal is reported, nothing is launched
-template <int H>
-int launch(void (*kernel)(AttnTrain), const char* who, const AttnTrain& a, unsigned lds, hipStream_t s) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: %u bytes of LDS refused: %s", who, lds, hipGetErrorString(e));
-    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(H < 64 ? 64 : H), lds, s, a);
-    return GNNPN_OK;
-}
 }  // namespace
 
 extern "C" int gnnpn_decode_attn_train_forward_f32(const gnnpn_decode_attn_train_t* t, int32_t B, int32_t T, int32_t n_per, int32_t H,
@@ -294,7 +286,7 @@ extern "C" int gnnpn_decode_attn_train_forward_f32(const gnnpn_decode_attn_train
     hipStream_t s = (hipStream_t)stream;
     const unsigned lds = (unsigned)((size_t)T * n_per * 4 + ((size_t)T * n_per + 15) / 16 * 16);
     int rc;
-    GNNPN_FOR_H(H, rc = launch<HH>(decode_attn_train_forward_kernel<HH>, "decode_attn_train_forward_kernel", a, lds, s));
+    GNNPN_FOR_H(H, rc = gnnpn_launch_lds(decode_attn_train_forward_kernel<HH>, dim3(B), dim3(NT), lds, s, "decode_attn_train_forward_f32", a));
     if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH("decode_attn_train_forward_f32");
     return GNNPN_OK;
@@ -315,7 +307,7 @@ extern "C" int gnnpn_decode_attn_train_backward_f32(const gnnpn_decode_attn_trai
     hipStream_t s = (hipStream_t)stream;
     const unsigned lds = (unsigned)((size_t)T * n_per * 8);
     int rc;
-    GNNPN_FOR_H(H, rc = launch<HH>(decode_attn_train_backward_kernel<HH>, "decode_attn_train_backward_kernel", a, lds, s));
+    GNNPN_FOR_H(H, rc = gnnpn_launch_lds(decode_attn_train_backward_kernel<HH>, dim3(B), dim3(NT), lds, s, "decode_attn_train_backward_f32", a));
     if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH("decode_attn_train_backward_f32");
     return GNNPN_OK;

@@ -532,7 +532,8 @@ static size_t eswoa_lds_bytes(int n_cand, int pop, int T) {
 }
 
 // The one launch of both forms (`wide`: the workgroup form, positions in `workspace`), sized for sh.stride categories per
-// problem; `who` names the entry point in the messages, `entry` in a launch error.
+// problem; `who` names the entry point in the messages, `entry` in a launch error
+// (gnnpn_launch_lds, common.h).
 static int eswoa_launch(const char* who, const char* entry, bool wide, int32_t B, const Shape& sh, const int32_t* cand_ptr,
                         const int32_t* len_init, const double* cand, const double* bounds, const int32_t* start_pos, int32_t pop,
                         int32_t max_iter, const uint64_t* seeds, void* workspace, double* best_fitness, int32_t* best_pos,
@@ -546,17 +547,14 @@ static int eswoa_launch(const char* who, const char* entry, bool wide, int32_t B
         GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", who, lds, pop, T,
                    sh.max_cand);
     }
-    const void* kernel = wide ? (const void*)eswoa_wide_kernel : (const void*)eswoa_kernel;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot reserve %zu B of LDS", who, lds);
     const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
     auto* dr = reinterpret_cast<long long*>(draws);
-    if (wide)
-        hipLaunchKernelGGL(eswoa_wide_kernel, dim3(B), dim3(WNT), lds, (hipStream_t)stream, sh, cand_ptr, len_init, cand, bounds,
-                           start_pos, pop, max_iter, sd, reinterpret_cast<int32_t*>(workspace), best_fitness, best_pos, history, dr);
-    else
-        hipLaunchKernelGGL(eswoa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, sh, cand_ptr, len_init, cand, bounds,
-                           start_pos, pop, max_iter, sd, best_fitness, best_pos, history, dr);
+    const int rc = wide ? gnnpn_launch_lds(eswoa_wide_kernel, dim3(B), dim3(WNT), lds, (hipStream_t)stream, entry, sh, cand_ptr, len_init,
+                                           cand, bounds, start_pos, pop, max_iter, sd, reinterpret_cast<int32_t*>(workspace),
+                                           best_fitness, best_pos, history, dr)
+                        : gnnpn_launch_lds(eswoa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, entry, sh, cand_ptr, len_init, cand,
+                                           bounds, start_pos, pop, max_iter, sd, best_fitness, best_pos, history, dr);
+    if (rc != GNNPN_OK) return rc;
     GNNPN_CHECK_LAUNCH(entry);
     return GNNPN_OK;
 }

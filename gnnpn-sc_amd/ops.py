@@ -130,10 +130,15 @@ class TilePlan:
         y = torch.empty((self.n_rows, C), dtype=F32, device=x.device)
         check(_lib.load().gnnpn_csr_aggregate_tiled_f32(
             dev_ptr(self.header, I32, "header"), dev_ptr(self.order, I32, "order"), dev_ptr(self.selfw, F32, "selfw"),
-            dev_ptr(self.batches, U8, "batches"), dev_ptr(x, F32, "x"), C, dev_ptr(self_coef, F32, "self_coef", True),
-            dev_ptr(bias, F32, "bias", True), dev_ptr(scale, F32, "scale", True), dev_ptr(shift, F32, "shift", True), act,
+            dev_ptr(self.batches, U8, "batches"), dev_ptr(x, F32, "x"), C, *_aggregate_epilogue(self_coef, bias, scale, shift, act),
             dev_ptr(y, F32, "y"), C, self.n_rows, C, self.block_rows, stream_ptr()), "gnnpn_csr_aggregate_tiled_f32")
         return y
+
+
+def _aggregate_epilogue(self_coef, bias, scale, shift, act):
+    """The five epilogue operands every form of the aggregate takes, in the C ABI's order."""
+    return (dev_ptr(self_coef, F32, "self_coef", True), dev_ptr(bias, F32, "bias", True), dev_ptr(scale, F32, "scale", True),
+            dev_ptr(shift, F32, "shift", True), act)
 
 
 def csr_tile_plan(rowptr, col, w, block_rows):
@@ -184,18 +189,13 @@ def csr_aggregate(rowptr, col, w, x, self_coef=None, bias=None, scale=None, shif
     if form == "tiled":
         return aux.aggregate(x, self_coef, bias, scale, shift, act)
     y = torch.empty((n, C), dtype=F32, device=x.device)
+    args = (dev_ptr(rowptr, I32, "rowptr"), dev_ptr(col, I32, "col"), dev_ptr(w, F32, "w", True), dev_ptr(x, F32, "x"), C,
+            *_aggregate_epilogue(self_coef, bias, scale, shift, act), dev_ptr(y, F32, "y"), C, n, C)
     if form == "blocks":
-        check(_lib.load().gnnpn_csr_aggregate_blocks_f32(
-            dev_ptr(rowptr, I32, "rowptr"), dev_ptr(col, I32, "col"), dev_ptr(w, F32, "w", True), dev_ptr(x, F32, "x"), C,
-            dev_ptr(self_coef, F32, "self_coef", True), dev_ptr(bias, F32, "bias", True),
-            dev_ptr(scale, F32, "scale", True), dev_ptr(shift, F32, "shift", True), act, dev_ptr(y, F32, "y"), C, n, C,
-            int(block_rows), dev_ptr(aux, I32, "row_order", True), stream_ptr()), "gnnpn_csr_aggregate_blocks_f32")
-        return y
-    check(_lib.load().gnnpn_csr_aggregate_f32(
-        dev_ptr(rowptr, I32, "rowptr"), dev_ptr(col, I32, "col"), dev_ptr(w, F32, "w", True), dev_ptr(x, F32, "x"), C,
-        dev_ptr(self_coef, F32, "self_coef", True), dev_ptr(bias, F32, "bias", True),
-        dev_ptr(scale, F32, "scale", True), dev_ptr(shift, F32, "shift", True), act, dev_ptr(y, F32, "y"), C, n, C,
-        stream_ptr()), "gnnpn_csr_aggregate_f32")
+        check(_lib.load().gnnpn_csr_aggregate_blocks_f32(*args, int(block_rows), dev_ptr(aux, I32, "row_order", True), stream_ptr()),
+              "gnnpn_csr_aggregate_blocks_f32")
+    else:
+        check(_lib.load().gnnpn_csr_aggregate_f32(*args, stream_ptr()), "gnnpn_csr_aggregate_f32")
     return y
 
 

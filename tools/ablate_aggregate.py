@@ -9,33 +9,10 @@ bits: 1 no LDS reads, 2 one add instead of 2 multiplies + 2 adds per (edge, lane
 8 no result stores, 16 no stream loads.
 """
 import json, os, subprocess, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "gnnpn-sc_amd")
-OUT = os.path.join(PKG, "build", "ablate")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from patched_csrc import ROOT, PKG, OUT, patched_csrc
 VARIANTS = [0, 1, 2, 3, 4, 8, 12, 16, 19, 31]
 EXTRA = {}            # name -> -D flags of an experiment build: python tools/ablate_aggregate.py build P1=-DGNNPN_TILED_PERSISTENT=1 ...
-
-
-BASE = {"aggregate_switches.patch": "76d19b13d7", "aggregate_prefetch_wave.patch": "f5daec2"}   # the commit whose sources a frozen patch applies to (later kernels moved on)
-
-
-def patched_csrc(patch):
-    """A copy of csrc/ (+ include/) with tools/experiments/<patch> applied: the product sources carry no experiment switch, the
-    timing-only builds are compiled from this copy.  A patch listed in BASE is frozen: the files it touches are taken from that
-    commit (``git show``; needs the repository, i.e. build here, run on the GPU box)."""
-    import re, shutil
-    dst = os.path.join(OUT, "src_" + patch.replace(".patch", ""))
-    shutil.rmtree(dst, ignore_errors=True)
-    os.makedirs(os.path.join(dst, "gnnpn-sc_amd"), exist_ok=True)
-    shutil.copytree(os.path.join(PKG, "csrc"), os.path.join(dst, "gnnpn-sc_amd", "csrc"))
-    ppath = os.path.join(ROOT, "tools", "experiments", patch)
-    if patch in BASE:
-        for f in sorted(set(re.findall(r"^\+\+\+ b/(\S+)", open(ppath).read(), re.M))):
-            blob = subprocess.run(["git", "show", f"{BASE[patch]}:{f}"], check=True, cwd=ROOT, capture_output=True).stdout
-            os.makedirs(os.path.dirname(os.path.join(dst, f)), exist_ok=True)    # (a frozen patch may also touch the header, the oracle, a test)
-            open(os.path.join(dst, f), "wb").write(blob)
-    subprocess.run(["git", "apply", "--unsafe-paths", "--directory=" + dst, ppath], check=True, cwd=ROOT)
-    return os.path.join(dst, "gnnpn-sc_amd", "csrc")
 
 
 def build():

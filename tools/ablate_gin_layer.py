@@ -6,23 +6,10 @@ The switches are NOT in the product sources (round 5): tools/experiments/gin_lay
 bits: 1 no weight stream (every k-block reads the first record), 2 no matrix instructions, 4 no
 aggregate gathers, 8 no piece split in the epilogues."""
 import json, os, subprocess, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "gnnpn-sc_amd")
-OUT = os.path.join(PKG, "build", "ablate")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from patched_csrc import ROOT, PKG, OUT, patched_csrc
 VARIANTS = [0, 1, 2, 3, 4, 8, 13, 15]
 EXTRA = {}            # name -> extra -D flags (tools/ablate_gin_layer.py build NAME=-DFOO=1,-DBAR=2 ...)
-
-
-def patched_csrc(patch):
-    """A copy of csrc/ (+ include/) with tools/experiments/<patch> applied: the product sources carry no experiment switch, the
-    timing-only builds are compiled from this copy."""
-    import shutil
-    dst = os.path.join(OUT, "src_" + patch.replace(".patch", ""))
-    shutil.rmtree(dst, ignore_errors=True)
-    os.makedirs(os.path.join(dst, "gnnpn-sc_amd"), exist_ok=True)
-    shutil.copytree(os.path.join(PKG, "csrc"), os.path.join(dst, "gnnpn-sc_amd", "csrc"))
-    subprocess.run(["git", "apply", "--unsafe-paths", "--directory=" + dst, os.path.join(ROOT, "tools", "experiments", patch)], check=True, cwd=ROOT)
-    return os.path.join(dst, "gnnpn-sc_amd", "csrc")
 
 
 def build():
