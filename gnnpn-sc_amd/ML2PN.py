@@ -54,7 +54,7 @@ def check(dataset, serCategory, epoch):
 
 
 def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
-          sample_seed=None):
+          sample_seed=None, descend=None):
     """Run ML+2PN inference over ``./data/<dataset>`` on the GPU and write the two artefacts that
     ``check`` reads: the rankings of ALL problems (trainML.py:146-149 format, [P][S] ints) and the
     High-level actions of the test quarter (trainPNHigh.py:133-144 format, [T][nTest][8]).
@@ -66,7 +66,10 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     ``idx`` on stream ``seed + idx``; seed None: fresh seeds).
     ``samples`` > 1: best-of-N decoding (ML2PNPipeline.best_of): per problem the greedy answer or one of samples-1 sampled
     High decodes, whichever has the smallest R; the refinement then starts from it.  ``sample_seed``: the draws' seed
-    (batch i of the run uses replica streams of sample_seed + i); None: fresh OS entropy."""
+    (batch i of the run uses replica streams of sample_seed + i); None: fresh OS entropy.
+    ``descend``: a number of sweeps (>= 1) — then the test quarter's actions are improved by one-swap descent on the device
+    (pipeline.descend, at ``woa``'s reduct or 0) and ``./solutions/WOA/<dataset>/ML+2PN+descent.txt`` written in the same format;
+    together with ``woa`` the ES-WOA run starts from the descended composition."""
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -104,22 +107,24 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
             if lo + b >= n_train:
                 for t in range(T):
                     actions[t].append(act[b, t].tolist())
-        if woa is not None and hi > n_train:
+        if (woa is not None or descend is not None) and hi > n_train:
             test_actions.append(act[max(0, n_train - lo):])
     paths = write_artifacts(dataset, epoch, rankings, actions)
-    if woa is not None:
-        refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)), **woa)
+    if woa is not None or descend is not None:
+        refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
+                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend)
     return paths
 
 
-def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None):
+def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None):
     """ES-WOA refinement of the test quarter's actions [nTest, T, 8] on the device, written as the WOA approach's
-    ``ML+2PN+WOA.txt`` (WOA.py:286-296): quality = minCost / best fitness, problem ``idx`` on stream ``seed + idx``."""
+    ``ML+2PN+WOA.txt`` (WOA.py:286-296): quality = minCost / best fitness, problem ``idx`` on stream ``seed + idx``.
+    ``descend`` = sweeps (>= 1): one-swap descent first, written as ``ML+2PN+descent.txt``; ES-WOA (popSize > 0) then starts from it."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import DeviceBatch
+    from .pipeline import DeviceBatch, descend as descend_actions, refine
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
     first = P // 4 * 3
@@ -127,13 +132,26 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     _, pb = ld.tables_from_dataset(ds, first, first + n)
     batch = DeviceBatch.from_problems(pb, dev)
     seeds = None if seed is None else [(seed + first + i) & 0xFFFFFFFFFFFFFFFF for i in range(n)]
-    torch.cuda.synchronize(dev)
-    t0 = time.time()
-    res = pipe.refine(svc, batch, {"actions": torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float64)).to(dev)},
-                      popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=ds["minCostList"][first:first + n])
-    quality = res["quality"].cpu().tolist()
-    per_problem = (time.time() - t0) / max(n, 1)
-    return write_ml2pn_woa(dataset, quality, per_problem, first)
+    out = {"actions": torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float64)).to(dev)}
+    min_cost = ds["minCostList"][first:first + n]
+    written = None
+    # each file books the time of its own stages: descent.txt the tables + descent, WOA.txt the tables (+ descent) + ES-WOA.  With
+    # both, descent therefore runs twice (it is deterministic and costs about a hundredth of the ES-WOA run beside it).
+    if descend is not None:
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        quality = descend_actions(svc, batch, out, max_sweeps=descend, reduct=reduct, min_cost=min_cost)["quality"].cpu().tolist()
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+descent.txt")
+    if descend is None or popSize > 0:
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        if descend is None:
+            res = pipe.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost)
+        else:
+            res = refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend)
+        quality = res["quality"].cpu().tolist()
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first)
+    return written
 
 
 def artifact_paths(dataset, epoch):

@@ -95,6 +95,8 @@ _SIGNATURES = {
     "gnnpn_eswoa_ragged_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "gnnpn_eswoa_ragged_f64": (c_int, [c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, _P, c_int32, _P,
                                        c_int64, _P, _P, _P, _P, _P, _P]),
+    "gnnpn_descend_ragged_f64": (c_int, [c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                         _P, _P, _P]),
     "gnnpn_woa_candidates_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "gnnpn_woa_candidates_count": (c_int, [c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_double,
                                            _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P]),

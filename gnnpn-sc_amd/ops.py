@@ -1182,6 +1182,38 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
           "gnnpn_eswoa_ragged_f64")
     return best_fit, best_pos, history[:, :int(max_iter)], draws, best_rows
 
+def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_slots=None, max_cand=None, wide=None):
+    """One-swap coordinate descent over the ES-WOA figure of merit, a ragged batch in ONE launch (gnnpn_descend_ragged_f64): from
+    every problem's start composition, slot by slot the best candidate of the slot's list (the lowest position among equals) is
+    taken while it strictly lowers violate + objFunc, until a sweep moves nothing or ``max_sweeps`` are done.  Operands as
+    eswoa_ragged (what woa_candidates returns; a problem whose first start_pos entry is < 0 starts from position 0 of every
+    list); ``wide``: the workgroup form for every problem (taken anyway above 64 slots, and needed where a problem's table
+    exceeds the LDS).  Returns a dict of device tensors: best_fitness [B] f64, start_fitness [B] f64, best_pos [B, max_slots] i32
+    and best_rows [B, max_slots, 4] f64 (0 past a problem's count), history [B, max_sweeps] f64 (the merit after every sweep; past
+    the last sweep the final value), sweeps [B] i32 (the last, fruitless one included), moves [B] i32."""
+    dev = cand.device
+    B = prob_ptr.numel() - 1
+    n = cand_ptr.numel() - 1
+    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0:
+        raise GnnpnError("descend_ragged: inconsistent operand sizes")
+    if max_slots is None:
+        max_slots = int((prob_ptr[1:] - prob_ptr[:-1]).max().item()) if B else 1
+    if max_cand is None:
+        max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
+    max_slots, max_cand = max(int(max_slots), 1), max(int(max_cand), 1)
+    out = {"best_fitness": torch.empty(B, dtype=F64, device=dev), "start_fitness": torch.empty(B, dtype=F64, device=dev),
+           "best_pos": torch.zeros(B, max_slots, dtype=I32, device=dev), "best_rows": torch.zeros(B, max_slots, 4, dtype=F64, device=dev),
+           "history": torch.empty(B, max(int(max_sweeps), 1), dtype=F64, device=dev), "sweeps": torch.empty(B, dtype=I32, device=dev),
+           "moves": torch.empty(B, dtype=I32, device=dev)}
+    check(_lib.load().gnnpn_descend_ragged_f64(
+        B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
+        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), int(bool(wide)),
+        dev_ptr(out["best_fitness"], F64, "best_fitness"), dev_ptr(out["start_fitness"], F64, "start_fitness"),
+        dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"), dev_ptr(out["history"], F64, "history"),
+        dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"), stream_ptr()), "gnnpn_descend_ragged_f64")
+    out["history"] = out["history"][:, :int(max_sweeps)]
+    return out
+
 # ---- REINFORCE training step of the High-level pointer network (csrc/train.hip; include/gnnpn_hip.h) -----------------
 
 def gemm_split(M, N, K):

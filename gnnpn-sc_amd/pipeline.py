@@ -131,8 +131,37 @@ def warn_partitioned_device(device, precision):
                       RuntimeWarning, stacklevel=3)
 
 
+def _quality(res, min_cost, dev):
+    """quality = min_cost / best_fitness (WOA.py:286-287), added to ``res`` where ``min_cost`` [B] is given."""
+    if min_cost is not None:
+        mc = min_cost if isinstance(min_cost, torch.Tensor) else torch.as_tensor(np.asarray(min_cost, dtype=np.float64))
+        res["quality"] = mc.to(device=dev, dtype=torch.float64) / res["best_fitness"]
+    return res
+
+
+def _descend_tables(tabs, max_sweeps):
+    res = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
+                             max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+    res["n_slots"] = tabs["n_slots"]
+    return res
+
+
 @torch.no_grad()
-def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=()):
+def descend(services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patches=()):
+    """One-swap descent of ``out["actions"]`` on the device: the candidate lists of every problem as ``refine`` builds them
+    (gnnpn_woa_candidates_count / _fill), then per problem, slot by slot, the best candidate of the slot's list while it
+    strictly lowers violate + objFunc, until a sweep moves nothing or ``max_sweeps`` are done (gnnpn_descend_ragged_f64; all
+    problems in one launch, deterministic: no seeds).  A problem the host path raises on raises GnnpnError naming it.
+    ``ML2PNPipeline.descend`` is this, as a method.  Returns ops.descend_ragged's dict (best_fitness, start_fitness, best_pos,
+    best_rows, history, sweeps, moves) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness)."""
+    actions = out["actions"]
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    return _quality(_descend_tables(tabs, max_sweeps), min_cost, actions.device)
+
+
+@torch.no_grad()
+def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=(), descend=0):
     """The third stage: ES-WOA refinement of ``out["actions"]`` (what ``run`` returned, or any mapping with an actions
     tensor [B,T,8], float32 or float64) on the device — the candidate lists of every problem built from ``services`` /
     ``batch`` (gnnpn_woa_candidates_count / _fill: loadDataOther + WOA._prepare, bit for bit) and the search of every problem
@@ -140,7 +169,9 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
     fine_tune); ``min_cost`` [B]: adds quality = min_cost / best_fitness (WOA.py:286-287); ``patches``: WOA._prepare's.
     A problem the host path raises on raises GnnpnError naming it.  ``ML2PNPipeline.refine`` is this, as a method.
     Returns device tensors: best_fitness [B] f64, best_rows [B, max_slots, 4] f64, n_slots [B] i32, best_pos
-    [B, max_slots] i32 (negative: Python list positions), history [B, MAX_Iter] f64, draws [B] i64 (and quality [B] f64)."""
+    [B, max_slots] i32 (negative: Python list positions), history [B, MAX_Iter] f64, draws [B] i64 (and quality [B] f64).
+    ``descend`` = k > 0: the tables are built once, one-swap descent runs up to k sweeps on them (``descend`` above) and ES-WOA
+    starts from descent's best_pos in place of start_pos; the result gains ``descent`` (the descent's dict)."""
     actions = out["actions"]
     dev = actions.device
     B = batch.n_problems
@@ -151,14 +182,19 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
     if not isinstance(seeds, torch.Tensor):
         seeds = torch.from_numpy(np.asarray(seeds, dtype=np.uint64).reshape(B).view(np.int64).copy())
     seeds = seeds.to(device=dev, dtype=torch.int64).contiguous()
+    start_pos, descent = tabs["start_pos"], None
+    if descend:
+        descent = _quality(_descend_tables(tabs, int(descend)), min_cost, dev)
+        # a problem's slots are rows prob_ptr[p] .. of the flat tables and the first n_slots[p] entries of its best_pos row
+        slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
+        start_pos = descent["best_pos"][slots].contiguous()
     fit, pos, hist, draws, rows = ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"],
-                                                   tabs["bounds"], tabs["start_pos"], popSize, MAX_Iter, seeds,
+                                                   tabs["bounds"], start_pos, popSize, MAX_Iter, seeds,
                                                    max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
     res = {"best_fitness": fit, "best_rows": rows, "n_slots": tabs["n_slots"], "best_pos": pos, "history": hist, "draws": draws}
-    if min_cost is not None:
-        mc = min_cost if isinstance(min_cost, torch.Tensor) else torch.as_tensor(np.asarray(min_cost, dtype=np.float64))
-        res["quality"] = mc.to(device=dev, dtype=torch.float64) / fit
-    return res
+    if descent is not None:
+        res["descent"] = descent
+    return _quality(res, min_cost, dev)
 
 
 class ML2PNPipeline:
@@ -262,6 +298,11 @@ class ML2PNPipeline:
         """The third stage, ES-WOA refinement of ``out["actions"]`` on the device: module-level ``refine`` (it needs no
         network).  An extra call: ``run`` / ``capture`` are unchanged."""
         return refine(services, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, patches=patches)
+
+    def descend(self, services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patches=()):
+        """One-swap descent of ``out["actions"]`` on the device: module-level ``descend`` (it needs no network).  An extra call:
+        ``run`` / ``capture`` are unchanged."""
+        return descend(services, batch, out, max_sweeps=max_sweeps, reduct=reduct, min_cost=min_cost, patches=patches)
 
     def capture(self, services, batch, warmup=2, decode_impl=0, lds_kb=0, ws=None, paired_start=False, pool=None, write_through=False):
         """Record one whole pass over (services, batch) into a HIP graph and return a callable that

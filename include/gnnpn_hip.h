@@ -754,6 +754,31 @@ int gnnpn_eswoa_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, 
                            void* workspace, int64_t workspace_bytes, double* best_fitness, int32_t* best_pos, double* best_rows,
                            double* history, int64_t* draws, void* stream);
 
+/* One-swap coordinate descent over the ES-WOA figure of merit, a ragged batch in one launch (csrc/descend.hip).  New: no reference
+ * counterpart — the reference goes from the pointer networks' composition straight to ES-WOA; this is the deterministic stage
+ * between them.  Operands as gnnpn_eswoa_ragged_f64 (prob_ptr, cand_ptr, cand, bounds, start_pos: what gnnpn_woa_candidates_fill
+ * writes).  Per problem with T lists:
+ *   cur[j] = start_pos[j] (first start_pos entry of the problem < 0: cur[j] = 0 for all j); fit = merit(cur) -> start_fitness;
+ *   up to max_sweeps sweeps: for j = 0 .. T-1 in order, f_c = merit(cur with slot j := c) for EVERY position c of list j; c* = the
+ *   smallest f_c, the lowest position among equals; if f_c* < fit (strictly): cur[j] = c*, fit = f_c*, one more move.  history[s] =
+ *   fit after sweep s; a sweep without a move is the last (it is counted); history past the last sweep repeats the final value.
+ * merit = violate + objFunc of src/baselines/WOA.py:87-105 in numpy's float64 evaluation orders, bit for bit (as gnnpn_eswoa_f64);
+ * all comparisons are plain <, so a NaN merit never wins.  max_sweeps = 0 evaluates the start and returns it.
+ *   max_slots : the largest list count (rows of best_pos / best_rows); max_slots <= 64 and wide == 0: one wavefront per problem,
+ *               one candidate per lane, the problem's table in LDS (max_cand = its largest candidate count sizes it); else one
+ *               workgroup per problem, the table in global memory.  Both forms give the same run.
+ * Outputs: best_fitness [B], start_fitness [B], best_pos [B, max_slots] and best_rows [B, max_slots, 4] or NULL (entries past a
+ * problem's count are not written), history [B, max(max_sweeps, 1)] (every entry written: with max_sweeps = 0 its one entry is the
+ * start's merit), sweeps [B], moves [B].  A problem the launch was not sized
+ * for (no list, more lists than max_slots or 64 in the lane form, more candidates than max_cand in the lane form, entries past
+ * n_lists), with an empty list or with a start position outside its list is not searched: best_fitness and start_fitness NaN,
+ * sweeps -1, moves 0, its history row NaN, its best_pos / best_rows rows not written (ops.descend_ragged hands them in as zeros).
+ * GNNPN_E_UNSUP: the lane form's tables exceed a CU's LDS (pass wide = 1), or the workgroup form's four columns do. */
+int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                             const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                             int32_t max_sweeps, int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos,
+                             double* best_rows, double* history, int32_t* sweeps, int32_t* moves, void* stream);
+
 /* ES-WOA inputs of an ML+2PN batch built on the device (csrc/woa_prep.hip).  Replaces what src/baselines/WOA.py:194-208 and
  * :13-26, 55-69 (`WOA.start` + `ESWOA.__init__`: action rows, the pick set, rounding, the appended pick) and
  * src/loadData.py:155-276 (`addS`, `loadDataOther`: the per-task candidate lists) do on the host, with the same results

@@ -14,6 +14,11 @@
     python main.py QWS ML+2PN -1 --infer --samples=N [--seed S] [--woa]   # best-of-N decoding of the High level: per problem
                                          # the greedy answer or one of N-1 sampled decodes, the smallest R (--woa refines it)
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] [--woa]   # ... and improve the test quarter's actions by one-swap
+                                         # descent on the device (deterministic; 16 sweeps at most unless given; reduct of
+                                         # [<ds>-WOA] with --woa, else 0): ./solutions/WOA/<ds>/ML+2PN+descent.txt; with --woa
+                                         # the ES-WOA run starts from the descended composition
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -179,6 +184,12 @@ def main(argv):
         if samples is not None:                                     # best-of-N decoding of the High level
             args = argv[3:]
             best = {"samples": int(samples), "sample_seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
+        sweeps = next((a.split("=", 1)[1] if "=" in a else "16" for a in flags if a == "--descend" or a.startswith("--descend=")), None)
+        if sweeps is not None:                                      # one-swap descent of the test quarter's actions
+            if int(sweeps) < 1:
+                print("--descend=SWEEPS: at least one sweep")
+                return 1
+            best["descend"] = int(sweeps)
         ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
