@@ -685,9 +685,15 @@ __device__ __forceinline__ void split_chain(const _Float16* base, const f16x8 (&
     //   h1.w1 -> a2 | h1.w0 -> a1 | h0.w2 -> a2 | h0.w0 -> a0 | h2.w0 -> a2 | h0.w1 -> a1        (each for both tiles)
     // one per line below, every line ending in a scheduling fence.  A 16x16x32 product occupies the matrix pipe for 16
     // cycles and the SIMD's vector issue for 8 of them (MI355X_MICROARCH.md, cycle constants): the eight v_perm that expand
-    // the block's third-piece bytes are dealt two per gap to the first four gaps, and every single-buffered piece (h1, h2,
-    // the bytes) is re-requested in the gap behind its last use, >= 7 products (112 cycles) ahead of its next one; h0, used
-    // three times per block, is the one double-buffered piece.  Left alone the compiler sinks every LDS read down to its
+    // the block's third-piece bytes are dealt two per gap to the first four gaps — which FILLS those gaps (two VOP3 of 4
+    // cycles each) — and every single-buffered piece (h1, h2, the bytes) is re-requested in an otherwise EMPTY gap behind its
+    // last use (h1 behind product 5, the bytes behind product 6, h2 behind product 10), >= 6 products ahead of its next one;
+    // h0, used three times per block, is the one double-buffered piece.  A wave issues in order: an LDS read in a gap that
+    // already holds two v_perm pushes the next product back.  Round 7 measured it both ways (profiles/LOG_r07.md): h1 and
+    // the bytes used to be requested in gap 4 behind its two v_perm — moving them one and two gaps on took 270 cycles off
+    // the stamped product phase — and holding h1, h2 and the bytes TWICE to request them a whole k-block ahead returned
+    // nothing at the same positions and cost 7 % of a solo encoder launch with the requests in gaps 1-4 (or 5-8): what the
+    // phase loses is issue slots, not LDS latency.  Left alone the compiler sinks every LDS read down to its
     // first use (fewest live registers) and the wave waits out a full LDS latency several times per block — the first build
     // of this function spent 3.5 k cycles on 1.5 k cycles of MFMAs (tools/stamp_decode.py).  Measured: the bare chain runs
     // at 17.4-18.1 ticks per product (tools/probes/mfma_chain_rate.hip: registers only / with these LDS reads and v_perm);
@@ -722,13 +728,11 @@ __device__ __forceinline__ void split_chain(const _Float16* base, const f16x8 (&
         e1.z = __builtin_amdgcn_perm(0u, t.w, 0x010c000cu);
         e1.w = __builtin_amdgcn_perm(0u, t.w, 0x030c020cu);
         GNNPN_FENCE;
-        if (kk < 7) {
-            h1 = *reinterpret_cast<const f16x8*>(base + SPLIT_TILE + nx);
-            t = *reinterpret_cast<const u32x4*>(wt + 4 * 64 * (kk + 1));
-        }
         a2[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0[cur], __builtin_bit_cast(f16x8, e0), a2[0], 0, 0, 0);
+        if (kk < 7) h1 = *reinterpret_cast<const f16x8*>(base + SPLIT_TILE + nx);
         GNNPN_FENCE;
         a2[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0[cur], __builtin_bit_cast(f16x8, e1), a2[1], 0, 0, 0);
+        if (kk < 7) t = *reinterpret_cast<const u32x4*>(wt + 4 * 64 * (kk + 1));
         GNNPN_FENCE;
         if (kk < 4) a0[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0[cur], w0[0][kk], a0[0], 0, 0, 0);
         else a0b[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0[cur], w0[0][kk], a0b[0], 0, 0, 0);
