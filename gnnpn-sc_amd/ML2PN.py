@@ -54,7 +54,7 @@ def check(dataset, serCategory, epoch):
 
 
 def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
-          sample_seed=None, descend=None):
+          sample_seed=None, descend=None, all_starts=False):
     """Run ML+2PN inference over ``./data/<dataset>`` on the GPU and write the two artefacts that
     ``check`` reads: the rankings of ALL problems (trainML.py:146-149 format, [P][S] ints) and the
     High-level actions of the test quarter (trainPNHigh.py:133-144 format, [T][nTest][8]).
@@ -69,10 +69,15 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     (batch i of the run uses replica streams of sample_seed + i); None: fresh OS entropy.
     ``descend``: a number of sweeps (>= 1) — then the test quarter's actions are improved by one-swap descent on the device
     (pipeline.descend, at ``woa``'s reduct or 0) and ``./solutions/WOA/<dataset>/ML+2PN+descent.txt`` written in the same format;
-    together with ``woa`` the ES-WOA run starts from the descended composition."""
+    together with ``woa`` the ES-WOA run starts from the descended composition.
+    ``all_starts`` (with samples > 1 and descend): the test quarter's rows of EVERY replica are kept per batch and descent runs from
+    all of them (pipeline.descend_starts), the lowest local optimum per problem kept: ``ML+2PN+multistart.txt`` in place of
+    ``ML+2PN+descent.txt``; with ``woa`` ES-WOA starts from that winner.  The PNHigh artefact is the best-of winner by R either way."""
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
+    if all_starts and (samples < 2 or descend is None):
+        raise ValueError("ML2PN.infer: all_starts needs samples > 1 and descend")
     d = f"./data/{dataset}/"
     ds = {k: json.load(open(d + fn)) for k, fn in (
         ("nodefeatures", "nodefeatures.data"), ("edge_indices", "edge_indices.data"), ("labels", "labels.data"),
@@ -83,7 +88,7 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     pipe = ML2PNPipeline(net.to(dev).eval(), low.to(dev).eval(), high.to(dev).eval(), n_per, precision=precision)
     table, _ = ld.tables_from_dataset(ds, 0, 0)
     svc = DeviceServices.from_table(table, dev)
-    rankings, actions, test_actions = [], [[] for _ in range(T)], []
+    rankings, actions, test_actions, test_starts = [], [[] for _ in range(T)], [], []
     n_train = P // 4 * 3
     from . import ops
     for lo in range(0, P, batch_size):
@@ -97,8 +102,13 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
                 from .modelPN import fresh_seed
                 seed_b = fresh_seed()           # one seed per batch
             # best_of checks its own launches before it returns: a failed hand-off raises there (no repeat of the batch)
-            act = ops.run_checked(lambda attempt: pipe.best_of(svc, batch, samples, seed=seed_b, write_through=attempt > 0)["actions"]
-                                  .cpu().numpy().astype(np.float64), dev)
+            def best(attempt):
+                o = pipe.best_of(svc, batch, samples, seed=seed_b, write_through=attempt > 0, return_all=all_starts)
+                rows = o["actions_all"][..., -8:].cpu().numpy().astype(np.float64) if all_starts else None       # [b,N,T,8]
+                return o["actions"].cpu().numpy().astype(np.float64), rows
+            act, starts = ops.run_checked(best, dev)
+            if all_starts and hi > n_train:
+                test_starts.append(starts[max(0, n_train - lo):])
         else:
             act = ops.run_checked(lambda attempt: pipe.run(svc, batch, write_through=attempt > 0)["actions"].cpu().numpy().astype(np.float64),
                                   dev)                                       # [b,T,8]
@@ -112,19 +122,22 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     paths = write_artifacts(dataset, epoch, rankings, actions)
     if woa is not None or descend is not None:
         refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
-                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend)
+                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend,
+                            starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
 
-def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None):
+def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None):
     """ES-WOA refinement of the test quarter's actions [nTest, T, 8] on the device, written as the WOA approach's
     ``ML+2PN+WOA.txt`` (WOA.py:286-296): quality = minCost / best fitness, problem ``idx`` on stream ``seed + idx``.
-    ``descend`` = sweeps (>= 1): one-swap descent first, written as ``ML+2PN+descent.txt``; ES-WOA (popSize > 0) then starts from it."""
+    ``descend`` = sweeps (>= 1): one-swap descent first, written as ``ML+2PN+descent.txt``; ES-WOA (popSize > 0) then starts from it.
+    ``starts`` [nTest, N, T, 8] (with ``descend``): descent from every one of the N rows per problem, the lowest optimum kept
+    (pipeline.descend_starts), written as ``ML+2PN+multistart.txt`` instead; ES-WOA then starts from the winner's rows."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import DeviceBatch, descend as descend_actions, refine
+    from .pipeline import DeviceBatch, descend as descend_actions, descend_starts, refine
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
     first = P // 4 * 3
@@ -137,7 +150,15 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     written = None
     # each file books the time of its own stages: descent.txt the tables + descent, WOA.txt the tables (+ descent) + ES-WOA.  With
     # both, descent therefore runs twice (it is deterministic and costs about a hundredth of the ES-WOA run beside it).
-    if descend is not None:
+    if descend is not None and starts is not None:
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        multi = descend_starts(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev), max_sweeps=descend,
+                               reduct=reduct, min_cost=min_cost)
+        quality = multi["quality"].cpu().tolist()
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+multistart.txt")
+        out = {"actions": multi["actions"]}          # refine below rebuilds the winner's tables and repeats its descent
+    elif descend is not None:
         torch.cuda.synchronize(dev)
         t0 = time.time()
         quality = descend_actions(svc, batch, out, max_sweeps=descend, reduct=reduct, min_cost=min_cost)["quality"].cpu().tolist()

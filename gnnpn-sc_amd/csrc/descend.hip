@@ -379,3 +379,65 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
     GNNPN_CHECK_LAUNCH(entry);
     return GNNPN_OK;
 }
+
+// ---- selection among the replicas of a problem: one wavefront per problem -----------------------------------------------------------
+// Rows are problem-major (row b * R + r = replica r of problem b, what one gnnpn_descend_ragged_f64 launch over B * R rows wrote).
+// Lane l looks at replicas l, l + 64, ...; the key is (best_fitness, replica) under take_better's plain <, so a NaN never wins, equal
+// merits (-0.0 and 0.0 among them) go to the lowest replica, and where every row is NaN (not searched) replica 0 is the answer and its
+// NaN / -1 fields are what the caller sees.  Then the lanes copy the winner's fields; the start rows as 32-bit words, so float32 and
+// float64 actions are one build.  No atomics, nothing shared with other workgroups; loops bounded by R, max_slots, hist_ld, actions_T.
+struct SelectIo {
+    const double* fit; const double* start_fit; const int32_t* sweeps; const int32_t* moves; const int32_t* n_slots;
+    const int32_t* pos; const double* rows; const double* hist; const uint32_t* actions;
+    double* fit_o; double* start_fit_o; int32_t* sweeps_o; int32_t* moves_o; int32_t* n_slots_o;
+    int32_t* pos_o; double* rows_o; double* hist_o; uint32_t* actions_o; int32_t* start_index;
+};
+
+__global__ __launch_bounds__(64) void descend_select_kernel(int32_t R, int32_t max_slots, int32_t hist_ld, int32_t action_words, SelectIo io) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const size_t q0 = (size_t)b * R;
+    double bf = INFINITY;
+    int bc = INT_MAX;
+    for (int r = lane; r < R; r += 64) take_better(bf, bc, io.fit[q0 + r], r);
+    wave_argmin(bf, bc, lane);
+    bc = __shfl(bc, 0);
+    const int win = bc == INT_MAX ? 0 : bc;                           // every row NaN: replica 0
+    const size_t q = q0 + win;
+    if (lane == 0) {
+        io.fit_o[b] = io.fit[q];
+        io.start_fit_o[b] = io.start_fit[q];
+        io.sweeps_o[b] = io.sweeps[q];
+        io.moves_o[b] = io.moves[q];
+        io.n_slots_o[b] = io.n_slots[q];
+        io.start_index[b] = win;
+    }
+    for (int i = lane; i < max_slots; i += 64) io.pos_o[(size_t)b * max_slots + i] = io.pos[q * max_slots + i];
+    for (int i = lane; i < max_slots * 4; i += 64) io.rows_o[(size_t)b * max_slots * 4 + i] = io.rows[q * max_slots * 4 + i];
+    for (int i = lane; i < hist_ld; i += 64) io.hist_o[(size_t)b * hist_ld + i] = io.hist[q * hist_ld + i];
+    for (int i = lane; i < action_words; i += 64) io.actions_o[(size_t)b * action_words + i] = io.actions[q * action_words + i];
+}
+
+extern "C" int gnnpn_descend_select_f64(int32_t B, int32_t R, int32_t max_slots, int32_t hist_ld, int32_t actions_T, int32_t action_row_words,
+                                        const double* best_fitness, const double* start_fitness, const int32_t* sweeps, const int32_t* moves,
+                                        const int32_t* n_slots, const int32_t* best_pos, const double* best_rows, const double* history,
+                                        const void* actions, double* best_fitness_out, double* start_fitness_out, int32_t* sweeps_out,
+                                        int32_t* moves_out, int32_t* n_slots_out, int32_t* best_pos_out, double* best_rows_out,
+                                        double* history_out, void* actions_out, int32_t* start_index, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && R >= 1 && max_slots >= 1 && hist_ld >= 0 && actions_T >= 0 && action_row_words >= 1, "descend_select: bad argument");
+    GNNPN_REQUIRE((int64_t)B * R <= INT32_MAX, "descend_select: bad argument: %d problems x %d replicas exceed int32", B, R);
+    GNNPN_REQUIRE((int64_t)max_slots * 4 <= INT32_MAX && (int64_t)actions_T * action_row_words <= INT32_MAX,
+                  "descend_select: bad argument: a row of %d slots or %d x %d action words exceeds int32", max_slots, actions_T, action_row_words);
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(best_fitness && start_fitness && sweeps && moves && n_slots && best_pos && best_rows && best_fitness_out &&
+                  start_fitness_out && sweeps_out && moves_out && n_slots_out && best_pos_out && best_rows_out && start_index,
+                  "descend_select: null operand");
+    GNNPN_REQUIRE(hist_ld == 0 || (history && history_out), "descend_select: null operand (history)");
+    GNNPN_REQUIRE(actions_T == 0 || (actions && actions_out), "descend_select: null operand (actions)");
+    GNNPN_REQUIRE(actions_T == 0 || (gnnpn_aligned(actions, 4) && gnnpn_aligned(actions_out, 4)), "descend_select: misaligned actions");
+    const SelectIo io{best_fitness, start_fitness, sweeps, moves, n_slots, best_pos, best_rows, history, static_cast<const uint32_t*>(actions),
+                      best_fitness_out, start_fitness_out, sweeps_out, moves_out, n_slots_out, best_pos_out, best_rows_out, history_out,
+                      static_cast<uint32_t*>(actions_out), start_index};
+    hipLaunchKernelGGL(descend_select_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, R, max_slots, hist_ld, actions_T * action_row_words, io);
+    GNNPN_CHECK_LAUNCH("descend_select_f64");
+    return GNNPN_OK;
+}

@@ -16,6 +16,8 @@
 // Every value is written with plain stores.  A problem the host path would raise on gets a status word instead (header).
 #include "common.h"
 
+#include <climits>
+
 namespace {
 
 // Python's round(x, 5) bit for bit (CPython rounds the exact binary value, ties to even, and returns the double nearest to
@@ -55,6 +57,8 @@ constexpr int ADDS_CATEGORIES = 50;   // addS sizes its per-category lists for 5
 
 // The workspace of one call (gnnpn_woa_candidates_workspace_bytes): per NODE g (a slot is its task node) the paired row and
 // the scan's results; per problem the counts.  Front and kept lists hold positions in the category (-1: the sentinel).
+// With R replicas per problem (gnnpn_woa_candidates_replicas_*) "problem" below is a row q = b * R + r (B * R of them) and "node" a
+// (replica, node) pair r * n_nodes + g (n_nodes * R of them): the tables of a problem's replicas differ (their pick sets do).
 struct PrepWs {
     double* row;       // [N][4] rounded (and patched) action row paired with the slot's list
     int* front;        // [N][cap]
@@ -153,7 +157,7 @@ __device__ int adds_scan(const double* qos_cat, int n_srv, const double* lb, dou
 }
 
 template <class A>
-__global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* __restrict__ x, int32_t x_ld,
+__global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, int32_t R, const float* __restrict__ x, int32_t x_ld,
                                                        const int32_t* __restrict__ seg_ptr, const double* __restrict__ local_bounds,
                                                        const double* __restrict__ global_bounds, int32_t n_cat,
                                                        const int32_t* __restrict__ cat_ptr, const double* __restrict__ qos,
@@ -164,7 +168,9 @@ __global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* _
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double* sset = reinterpret_cast<double*>(lds_raw);         // [a_T][4] rounded rows (the pick set sSet)
     double* prow = sset + (size_t)a_T * 4;                     // [a_T][4] rounded rows after the patches (_prepare)
-    const int b = blockIdx.x, lane = threadIdx.x;
+    // row rq = replica rq % R of problem b = rq / R: the row's own actions, outputs and workspace; the problem's x, segment and bounds
+    const int rq = blockIdx.x, b = rq / R, lane = threadIdx.x;
+    const int wq = (rq - b * R) * N;                            // the row's nodes in the workspace: wq + g
     const unsigned long long below = (1ull << lane) - 1ull;
 
     // the seed solution's rows: category order, dummy rows (float64 sum == 3) dropped (WOA.py:194-208)
@@ -174,7 +180,7 @@ __global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* _
         double r[4] = {0.0, 0.0, 0.0, 0.0};
         bool real = false;
         if (c < a_T) {
-            const A* a = actions + ((size_t)b * a_T + c) * 8;
+            const A* a = actions + ((size_t)rq * a_T + c) * 8;
 #pragma unroll
             for (int k = 0; k < 4; ++k) r[k] = (double)a[k];
             real = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), r[2]), r[3]) != 3.0;
@@ -206,22 +212,22 @@ __global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* _
         int nk = 0;
         if (s < ns) {
             const int cat = (int)x[(size_t)g * x_ld] - 1;
-            w.cat[g] = cat;
+            w.cat[wq + g] = cat;
             if (cat < 0 || cat >= ADDS_CATEGORIES || cat >= n_cat) {
                 unsup = true;
             } else {
                 const int c0 = cat_ptr[cat];
                 nk = adds_scan(qos + (size_t)c0 * 4, cat_ptr[cat + 1] - c0, local_bounds + ((size_t)b * n_cat + cat) * 4, reduct,
-                               sset, n_rows, w.front + (size_t)g * cap, w.kept + (size_t)g * cap);
+                               sset, n_rows, w.front + (size_t)(wq + g) * cap, w.kept + (size_t)(wq + g) * cap);
                 if (nk < 0) {
                     index_error = true;
                     nk = 0;
                 }
             }
-            w.n_kept[g] = nk;
+            w.n_kept[wq + g] = nk;
         }
         const unsigned long long m = __ballot(nk > 0);
-        if (s < ns) w.rank[g] = nk > 0 ? n_lists + __popcll(m & below) : -1;
+        if (s < ns) w.rank[wq + g] = nk > 0 ? n_lists + __popcll(m & below) : -1;
         n_lists += __popcll(m);
     }
     unsup = __ballot(unsup) != 0ull;
@@ -238,17 +244,17 @@ __global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* _
     for (int s0 = 0; s0 < ns && st == GNNPN_WOA_OK; s0 += 64) {
         const int s = s0 + lane;
         const int g = n0 + 1 + s;
-        const int l = s < ns ? w.rank[g] : -1;
+        const int l = s < ns ? w.rank[wq + g] : -1;
         int len = 0;
         if (l >= 0) {
-            const int nk = w.n_kept[g];
-            const double* qc = qos + (size_t)cat_ptr[w.cat[g]] * 4;
+            const int nk = w.n_kept[wq + g];
+            const double* qc = qos + (size_t)cat_ptr[w.cat[wq + g]] * 4;
             len = nk;
             int start = -1;
             if (seeded) {
                 const double* key = prow + (size_t)l * 4;
                 for (int i = 0; i < nk && start < 0; ++i) {
-                    const double* q = qc + (size_t)w.kept[(size_t)g * cap + i] * 4;
+                    const double* q = qc + (size_t)w.kept[(size_t)(wq + g) * cap + i] * 4;
                     double v[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) v[c] = round5(q[c]);
@@ -259,25 +265,25 @@ __global__ __launch_bounds__(64) void woa_count_kernel(int32_t N, const float* _
                     len = nk + 1;
                 }
 #pragma unroll
-                for (int c = 0; c < 4; ++c) w.row[(size_t)g * 4 + c] = key[c];
+                for (int c = 0; c < 4; ++c) w.row[(size_t)(wq + g) * 4 + c] = key[c];
             }
-            w.n_len[g] = len;
-            w.start[g] = start;
+            w.n_len[wq + g] = len;
+            w.start[wq + g] = start;
         }
         int total;
         const int off = wave_excl_scan(len, lane, &total);
-        if (l >= 0) w.off[g] = n_cand + off;
+        if (l >= 0) w.off[wq + g] = n_cand + off;
         n_cand += total;
     }
     if (lane == 0) {
         const bool ok = st == GNNPN_WOA_OK;
-        w.p_lists[b] = ok ? n_lists : 0;
-        w.p_cand[b] = ok ? n_cand : 0;
-        w.p_seeded[b] = seeded ? 1 : 0;
-        n_slots[b] = ok ? n_lists : 0;
-        status[b] = st;
+        w.p_lists[rq] = ok ? n_lists : 0;
+        w.p_cand[rq] = ok ? n_cand : 0;
+        w.p_seeded[rq] = seeded ? 1 : 0;
+        n_slots[rq] = ok ? n_lists : 0;
+        status[rq] = st;
     }
-    if (lane < 4) bounds[(size_t)b * 4 + lane] = global_bounds[(size_t)b * 4 + lane];   // constraintsList (loadData.py:268-273)
+    if (lane < 4) bounds[(size_t)rq * 4 + lane] = global_bounds[(size_t)b * 4 + lane];   // constraintsList (loadData.py:268-273)
 }
 
 // exclusive scans over the problems; totals = {lists, candidates, max lists of a problem, max candidates of a problem,
@@ -328,31 +334,32 @@ __global__ __launch_bounds__(SCAN_THREADS) void woa_scan_kernel(int32_t B, PrepW
     }
 }
 
-__global__ __launch_bounds__(64) void woa_fill_kernel(int32_t B, const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ cat_ptr,
+__global__ __launch_bounds__(64) void woa_fill_kernel(int32_t B, int32_t N, int32_t R, const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ cat_ptr,
                                                       const double* __restrict__ qos, int32_t cap, PrepWs w,
                                                       const int32_t* __restrict__ status, const int32_t* __restrict__ prob_ptr,
                                                       int32_t n_lists, int32_t n_cand, int32_t* __restrict__ cand_ptr,
                                                       int32_t* __restrict__ len_init, double* __restrict__ cand,
                                                       int32_t* __restrict__ start_pos) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (b == B - 1 && lane == 0 && prob_ptr[B] == n_lists) cand_ptr[n_lists] = w.cand_off[B];
-    if (status[b] != GNNPN_WOA_OK) return;
+    const int rq = blockIdx.x, b = rq / R, lane = threadIdx.x;   // B rows here: row rq of problem b, as in woa_count_kernel
+    const int wq = (rq - b * R) * N;
+    if (rq == B - 1 && lane == 0 && prob_ptr[B] == n_lists) cand_ptr[n_lists] = w.cand_off[B];
+    if (status[rq] != GNNPN_WOA_OK) return;
     const int n0 = seg_ptr[b], n1 = seg_ptr[b + 1];
     const int ns = n1 - n0 > 1 ? n1 - n0 - 1 : 0;             // a bad segment has a non-zero status: not reached
-    const bool seeded = w.p_seeded[b] != 0;
+    const bool seeded = w.p_seeded[rq] != 0;
     for (int s = lane; s < ns; s += 64) {
         const int g = n0 + 1 + s;
-        const int l = w.rank[g];
+        const int l = w.rank[wq + g];
         if (l < 0) continue;
-        const int j = prob_ptr[b] + l, off = w.cand_off[b] + w.off[g];
-        const int nk = w.n_kept[g], len = w.n_len[g];
+        const int j = prob_ptr[rq] + l, off = w.cand_off[rq] + w.off[wq + g];
+        const int nk = w.n_kept[wq + g], len = w.n_len[wq + g];
         if (j >= n_lists || off + len > n_cand) continue;      // never for the totals this call was sized by
         cand_ptr[j] = off;
         len_init[j] = nk;
-        start_pos[j] = seeded ? w.start[g] : -1;
-        const double* qc = qos + (size_t)cat_ptr[w.cat[g]] * 4;
+        start_pos[j] = seeded ? w.start[wq + g] : -1;
+        const double* qc = qos + (size_t)cat_ptr[w.cat[wq + g]] * 4;
         for (int i = 0; i < nk; ++i) {
-            const double* q = qc + (size_t)w.kept[(size_t)g * cap + i] * 4;
+            const double* q = qc + (size_t)w.kept[(size_t)(wq + g) * cap + i] * 4;
             double* o = cand + (size_t)(off + i) * 4;
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = seeded ? round5(q[c]) : q[c];
@@ -360,7 +367,7 @@ __global__ __launch_bounds__(64) void woa_fill_kernel(int32_t B, const int32_t* 
         if (len > nk) {
             double* o = cand + (size_t)(off + nk) * 4;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) o[c] = w.row[(size_t)g * 4 + c];
+            for (int c = 0; c < 4; ++c) o[c] = w.row[(size_t)(wq + g) * 4 + c];
         }
     }
 }
@@ -372,11 +379,89 @@ __global__ void round5_kernel(const double* __restrict__ x, double* __restrict__
 
 size_t count_lds_bytes(int a_T) { return (size_t)a_T * 8 * sizeof(double); }
 
+// B problems x R replicas: the kernels count rows and (replica, node) pairs in int32
+bool rows_fit(int64_t B, int64_t R, int64_t n_nodes) { return B * R <= INT32_MAX && n_nodes * R <= INT32_MAX; }
+
+// One launcher for the per-problem entries (R = 1) and the per-replica ones: B * R rows, the workspace of B * R rows over
+// n_nodes * R (replica, node) pairs.  `who` names the entry in the messages.
+int count_launch(const char* who, int32_t B, int32_t R, int32_t n_nodes, const float* x, int32_t x_ld, const int32_t* seg_ptr,
+                 const double* local_bounds, const double* global_bounds, int32_t n_cat, const int32_t* cat_ptr, const double* qos,
+                 const void* actions, int32_t actions_f64, int32_t actions_T, double reduct, const double* patches, int32_t n_patches,
+                 int32_t max_cat_size, void* workspace, int64_t workspace_bytes, int32_t* prob_ptr, int32_t* n_slots, double* bounds,
+                 int32_t* status, int32_t* totals, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && R >= 1 && n_nodes >= 0 && x_ld >= 1 && n_cat >= 1 && actions_T >= 1 && n_patches >= 0 && max_cat_size >= 0 &&
+                  (actions_f64 == 0 || actions_f64 == 1), "%s: bad argument", who);
+    GNNPN_REQUIRE(rows_fit(B, R, n_nodes), "%s: bad argument: %d problems / %d nodes x %d replicas exceed int32", who, B, n_nodes, R);
+    GNNPN_REQUIRE(prob_ptr && totals && cat_ptr && qos, "%s: null operand", who);
+    GNNPN_REQUIRE(B == 0 || (x && seg_ptr && local_bounds && global_bounds && actions && n_slots && bounds && status),
+                  "%s: null operand", who);
+    GNNPN_REQUIRE(n_patches == 0 || patches, "%s: null patches", who);
+    const int32_t rows = B * R;
+    const int64_t need = prep_ws_bytes(rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    GNNPN_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %lld B, %lld B needed", who, (long long)workspace_bytes,
+                  (long long)need);
+    GNNPN_REQUIRE(gnnpn_aligned(workspace, 8), "%s: misaligned workspace", who);
+    const size_t lds = count_lds_bytes(actions_T);
+    if (lds > 64 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d action rows per problem (at most 1024)", who, actions_T);
+    const PrepWs w = prep_ws(workspace, rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    hipStream_t s = (hipStream_t)stream;
+    if (rows > 0) {
+        if (actions_f64)
+            hipLaunchKernelGGL(woa_count_kernel<double>, dim3(rows), dim3(64), lds, s, n_nodes, R, x, x_ld, seg_ptr, local_bounds,
+                               global_bounds, n_cat, cat_ptr, qos, static_cast<const double*>(actions), actions_T, reduct, patches,
+                               n_patches, max_cat_size + 1, w, n_slots, bounds, status);
+        else
+            hipLaunchKernelGGL(woa_count_kernel<float>, dim3(rows), dim3(64), lds, s, n_nodes, R, x, x_ld, seg_ptr, local_bounds,
+                               global_bounds, n_cat, cat_ptr, qos, static_cast<const float*>(actions), actions_T, reduct, patches,
+                               n_patches, max_cat_size + 1, w, n_slots, bounds, status);
+        GNNPN_CHECK_LAUNCH(who);
+    }
+    hipLaunchKernelGGL(woa_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, rows, w, status, prob_ptr, totals);
+    GNNPN_CHECK_LAUNCH(who);
+    return GNNPN_OK;
+}
+
+int fill_launch(const char* who, int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr, const double* qos,
+                int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status, const int32_t* prob_ptr,
+                int32_t n_lists, int32_t n_cand, int32_t* cand_ptr, int32_t* len_init, double* cand, int32_t* start_pos, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && R >= 1 && n_nodes >= 0 && max_cat_size >= 0 && n_lists >= 0 && n_cand >= 0, "%s: bad argument", who);
+    GNNPN_REQUIRE(rows_fit(B, R, n_nodes), "%s: bad argument: %d problems / %d nodes x %d replicas exceed int32", who, B, n_nodes, R);
+    GNNPN_REQUIRE(cand_ptr, "%s: null operand", who);
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(seg_ptr && cat_ptr && qos && status && prob_ptr && (n_lists == 0 || (len_init && start_pos)) && (n_cand == 0 || cand),
+                  "%s: null operand", who);
+    const int32_t rows = B * R;
+    const int64_t need = prep_ws_bytes(rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    GNNPN_REQUIRE(workspace && workspace_bytes >= need && gnnpn_aligned(workspace, 8), "%s: workspace of %lld B, %lld B needed", who,
+                  (long long)workspace_bytes, (long long)need);
+    const PrepWs w = prep_ws(const_cast<void*>(workspace), rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    hipLaunchKernelGGL(woa_fill_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, rows, n_nodes, R, seg_ptr, cat_ptr, qos,
+                       max_cat_size + 1, w, status, prob_ptr, n_lists, n_cand, cand_ptr, len_init, cand, start_pos);
+    GNNPN_CHECK_LAUNCH(who);
+    return GNNPN_OK;
+}
+
 }  // namespace
 
+extern "C" int64_t gnnpn_woa_candidates_replicas_workspace_bytes(int32_t B, int32_t R, int32_t n_nodes, int32_t max_cat_size) {
+    if (B < 0 || R < 1 || n_nodes < 0 || max_cat_size < 0 || !rows_fit(B, R, n_nodes)) return -1;
+    return prep_ws_bytes((int64_t)B * R, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+}
+
 extern "C" int64_t gnnpn_woa_candidates_workspace_bytes(int32_t B, int32_t n_nodes, int32_t max_cat_size) {
-    if (B < 0 || n_nodes < 0 || max_cat_size < 0) return -1;
-    return prep_ws_bytes(B, n_nodes, (int64_t)max_cat_size + 1);
+    return gnnpn_woa_candidates_replicas_workspace_bytes(B, 1, n_nodes, max_cat_size);
+}
+
+extern "C" int gnnpn_woa_candidates_replicas_count(int32_t B, int32_t R, int32_t n_nodes, const float* x, int32_t x_ld,
+                                                   const int32_t* seg_ptr, const double* local_bounds, const double* global_bounds,
+                                                   int32_t n_cat, const int32_t* cat_ptr, const double* qos, const void* actions,
+                                                   int32_t actions_f64, int32_t actions_T, double reduct, const double* patches,
+                                                   int32_t n_patches, int32_t max_cat_size, void* workspace, int64_t workspace_bytes,
+                                                   int32_t* prob_ptr, int32_t* n_slots, double* bounds, int32_t* status, int32_t* totals,
+                                                   void* stream) {
+    return count_launch("woa_candidates_replicas_count", B, R, n_nodes, x, x_ld, seg_ptr, local_bounds, global_bounds, n_cat, cat_ptr, qos,
+                        actions, actions_f64, actions_T, reduct, patches, n_patches, max_cat_size, workspace, workspace_bytes, prob_ptr,
+                        n_slots, bounds, status, totals, stream);
 }
 
 extern "C" int gnnpn_woa_candidates_count(int32_t B, int32_t n_nodes, const float* x, int32_t x_ld, const int32_t* seg_ptr,
@@ -385,53 +470,25 @@ extern "C" int gnnpn_woa_candidates_count(int32_t B, int32_t n_nodes, const floa
                                           int32_t actions_T, double reduct, const double* patches, int32_t n_patches,
                                           int32_t max_cat_size, void* workspace, int64_t workspace_bytes, int32_t* prob_ptr,
                                           int32_t* n_slots, double* bounds, int32_t* status, int32_t* totals, void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_nodes >= 0 && x_ld >= 1 && n_cat >= 1 && actions_T >= 1 && n_patches >= 0 && max_cat_size >= 0 &&
-                  (actions_f64 == 0 || actions_f64 == 1), "woa_candidates_count: bad argument");
-    GNNPN_REQUIRE(prob_ptr && totals && cat_ptr && qos, "woa_candidates_count: null operand");
-    GNNPN_REQUIRE(B == 0 || (x && seg_ptr && local_bounds && global_bounds && actions && n_slots && bounds && status),
-                  "woa_candidates_count: null operand");
-    GNNPN_REQUIRE(n_patches == 0 || patches, "woa_candidates_count: null patches");
-    const int64_t need = gnnpn_woa_candidates_workspace_bytes(B, n_nodes, max_cat_size);
-    GNNPN_REQUIRE(workspace && workspace_bytes >= need, "woa_candidates_count: workspace of %lld B, %lld B needed",
-                  (long long)workspace_bytes, (long long)need);
-    GNNPN_REQUIRE(gnnpn_aligned(workspace, 8), "woa_candidates_count: misaligned workspace");
-    const size_t lds = count_lds_bytes(actions_T);
-    if (lds > 64 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "woa_candidates_count: %d action rows per problem (at most 1024)", actions_T);
-    const PrepWs w = prep_ws(workspace, B, n_nodes, (int64_t)max_cat_size + 1);
-    hipStream_t s = (hipStream_t)stream;
-    if (B > 0) {
-        if (actions_f64)
-            hipLaunchKernelGGL(woa_count_kernel<double>, dim3(B), dim3(64), lds, s, n_nodes, x, x_ld, seg_ptr, local_bounds,
-                               global_bounds, n_cat, cat_ptr, qos, static_cast<const double*>(actions), actions_T, reduct, patches,
-                               n_patches, max_cat_size + 1, w, n_slots, bounds, status);
-        else
-            hipLaunchKernelGGL(woa_count_kernel<float>, dim3(B), dim3(64), lds, s, n_nodes, x, x_ld, seg_ptr, local_bounds,
-                               global_bounds, n_cat, cat_ptr, qos, static_cast<const float*>(actions), actions_T, reduct, patches,
-                               n_patches, max_cat_size + 1, w, n_slots, bounds, status);
-        GNNPN_CHECK_LAUNCH("woa_candidates_count");
-    }
-    hipLaunchKernelGGL(woa_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, B, w, status, prob_ptr, totals);
-    GNNPN_CHECK_LAUNCH("woa_candidates_count (scan)");
-    return GNNPN_OK;
+    return count_launch("woa_candidates_count", B, 1, n_nodes, x, x_ld, seg_ptr, local_bounds, global_bounds, n_cat, cat_ptr, qos, actions,
+                        actions_f64, actions_T, reduct, patches, n_patches, max_cat_size, workspace, workspace_bytes, prob_ptr, n_slots,
+                        bounds, status, totals, stream);
+}
+
+extern "C" int gnnpn_woa_candidates_replicas_fill(int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr,
+                                                  const double* qos, int32_t max_cat_size, const void* workspace, int64_t workspace_bytes,
+                                                  const int32_t* status, const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand,
+                                                  int32_t* cand_ptr, int32_t* len_init, double* cand, int32_t* start_pos, void* stream) {
+    return fill_launch("woa_candidates_replicas_fill", B, R, n_nodes, seg_ptr, cat_ptr, qos, max_cat_size, workspace, workspace_bytes, status,
+                       prob_ptr, n_lists, n_cand, cand_ptr, len_init, cand, start_pos, stream);
 }
 
 extern "C" int gnnpn_woa_candidates_fill(int32_t B, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr, const double* qos,
                                          int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status,
                                          const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* cand_ptr,
                                          int32_t* len_init, double* cand, int32_t* start_pos, void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_nodes >= 0 && max_cat_size >= 0 && n_lists >= 0 && n_cand >= 0, "woa_candidates_fill: bad argument");
-    GNNPN_REQUIRE(cand_ptr, "woa_candidates_fill: null operand");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(seg_ptr && cat_ptr && qos && status && prob_ptr && (n_lists == 0 || (len_init && start_pos)) && (n_cand == 0 || cand),
-                  "woa_candidates_fill: null operand");
-    const int64_t need = gnnpn_woa_candidates_workspace_bytes(B, n_nodes, max_cat_size);
-    GNNPN_REQUIRE(workspace && workspace_bytes >= need && gnnpn_aligned(workspace, 8), "woa_candidates_fill: workspace of %lld B, %lld B needed",
-                  (long long)workspace_bytes, (long long)need);
-    const PrepWs w = prep_ws(const_cast<void*>(workspace), B, n_nodes, (int64_t)max_cat_size + 1);
-    hipLaunchKernelGGL(woa_fill_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, seg_ptr, cat_ptr, qos, max_cat_size + 1, w, status,
-                       prob_ptr, n_lists, n_cand, cand_ptr, len_init, cand, start_pos);
-    GNNPN_CHECK_LAUNCH("woa_candidates_fill");
-    return GNNPN_OK;
+    return fill_launch("woa_candidates_fill", B, 1, n_nodes, seg_ptr, cat_ptr, qos, max_cat_size, workspace, workspace_bytes, status, prob_ptr,
+                       n_lists, n_cand, cand_ptr, len_init, cand, start_pos, stream);
 }
 
 extern "C" int gnnpn_debug_round5_f64(const double* x, double* y, int64_t n, void* stream) {

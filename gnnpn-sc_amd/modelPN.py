@@ -456,7 +456,7 @@ def fresh_seed():
 
 
 def two_level_best_of(low, high, inputs, samples, seed=None, precision=None, fold=None, decode_impl=0, lds_kb=0, write_through=False,
-                      ws=None):
+                      ws=None, return_all=False):
     """Best-of-N decoding of the two-level scheme: replica 0 is two_level_greedy's answer, replicas 1..N-1 draw the High
     level's picks from its window softmax (the sampling policy REINFORCE trains, trainPNHigh.py:83-84) against the same greedy
     Low level; per problem the replica with the smallest R (round(violate + objFunc, 5), modelPN.py:61) is returned, the
@@ -468,6 +468,8 @@ def two_level_best_of(low, high, inputs, samples, seed=None, precision=None, fol
     sampled decode of these problems with that sample_seed does.  seed None: fresh OS entropy.
     Returns two_level_greedy's keys (the winners' idx_high, R, actions, action_probs; idx_low / win_low / win_high_raw of the
     greedy pass) plus sample_index [B] i32 (the winning replica), R_all [B,N] and idx_all [B,N,T] (every replica's High picks).
+    ``return_all``: also actions_all [B,N,T,8|9], every replica's action rows, replica 0 the greedy ones (the starts of
+    pipeline.descend_starts); False: today's result, key for key.
     The encoder state is never replicated.  The cooperative launches are checked (status words, proof of work) before
     anything is returned: a failed hand-off raises GnnpnError."""
     samples = int(samples)
@@ -520,6 +522,9 @@ def two_level_best_of(low, high, inputs, samples, seed=None, precision=None, fol
     else:
         out["R_all"] = torch.cat([g["R"].unsqueeze(1), sam["R"]], 1)
         out["idx_all"] = torch.cat([g["idx_high"].unsqueeze(1), sam["idx"]], 1)
+    if return_all:
+        g_rows = g["actions"].unsqueeze(1)
+        out["actions_all"] = g_rows.clone() if sam is None else torch.cat([g_rows, sam["actions"]], 1)
     return out
 
 

@@ -1082,9 +1082,86 @@ _WOA_STATUS = {_lib.WOA_ROWS_MISMATCH: "as many seed rows as non-empty candidate
                _lib.E_UNSUP: "a task category outside 0..49 or outside the table (GNNPN_E_UNSUP: addS raises IndexError)"}
 
 
-def woa_status_error(status, first):
-    """The error a problem's status word of gnnpn_woa_candidates_count stands for."""
-    return GnnpnError(f"woa_candidates: problem {first}: status {status}: {_WOA_STATUS.get(status, 'unknown status')}")
+def woa_status_error(status, first, replicas=None):
+    """The error a problem's status word of gnnpn_woa_candidates_count stands for (``replicas``: ``first`` is a row of
+    gnnpn_woa_candidates_replicas_count, named as its problem and replica)."""
+    if replicas is None:
+        return GnnpnError(f"woa_candidates: problem {first}: status {status}: {_WOA_STATUS.get(status, 'unknown status')}")
+    return GnnpnError(f"woa_candidates_replicas: problem {first // replicas} replica {first % replicas}: status {status}: "
+                      f"{_WOA_STATUS.get(status, 'unknown status')}")
+
+
+def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches, check_status):
+    """woa_candidates (``replicas`` None: the per-problem entries) and woa_candidates_replicas (``replicas`` True: the per-replica
+    ones over B * R rows, R read from the actions)."""
+    lib = _lib.load()
+    dev = x.device
+    B = seg_ptr.numel() - 1
+    if replicas is None:
+        if actions.dim() != 3 or actions.shape[0] != B or actions.shape[2] != 8:
+            raise GnnpnError(f"{who}: actions [B={B}, T, 8] expected, got {tuple(actions.shape)}")
+        R, aT = 1, actions.shape[1]
+    else:
+        if actions.dim() != 4 or actions.shape[0] != B or actions.shape[1] < 1 or actions.shape[3] != 8:
+            raise GnnpnError(f"{who}: actions [B={B}, R >= 1, T, 8] expected, got {tuple(actions.shape)}")
+        R, aT = actions.shape[1], actions.shape[2]
+    if actions.dtype not in (F32, F64):
+        raise GnnpnError(f"{who}: actions must be float32 or float64, got {actions.dtype}")
+    if x.dim() != 2 or local_bounds.dim() != 3 or local_bounds.shape[0] != B or local_bounds.shape[1] != cat_ptr.numel() - 1:
+        raise GnnpnError(f"{who}: inconsistent shapes (x [N,7], local_bounds [B, T, 4] with T = len(cat_ptr) - 1)")
+    for name, t in (("cat_ptr", cat_ptr), ("qos", qos), ("x", x), ("seg_ptr", seg_ptr), ("local_bounds", local_bounds),
+                    ("global_bounds", global_bounds), ("actions", actions)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GnnpnError(f"{who}: {name}: expected a CUDA tensor (the hot path has no CPU implementation)")
+    patches = list(patches)
+    for want, col, _val in patches:
+        if len(want) != 4 or not 0 <= int(col) < 4:
+            raise GnnpnError(f"{who}: a patch is (4 values, column 0..3, value)")
+    pt = torch.tensor([list(map(float, w)) + [float(c), float(v)] for w, c, v in patches] or [[0.0] * 6], dtype=F64).to(dev)
+    N, n_cat = x.shape[0], cat_ptr.numel() - 1
+    max_cat = int((cat_ptr[1:] - cat_ptr[:-1]).max().item()) if n_cat else 0
+    lead = (B, N) if replicas is None else (B, R, N)
+    count, fill = ((lib.gnnpn_woa_candidates_count, lib.gnnpn_woa_candidates_fill) if replicas is None else
+                   (lib.gnnpn_woa_candidates_replicas_count, lib.gnnpn_woa_candidates_replicas_fill))
+    entry = "gnnpn_woa_candidates" if replicas is None else "gnnpn_woa_candidates_replicas"
+    nbytes = int(lib.gnnpn_woa_candidates_workspace_bytes(B, N, max_cat) if replicas is None else
+                 lib.gnnpn_woa_candidates_replicas_workspace_bytes(B, R, N, max_cat))
+    if nbytes < 0:
+        raise GnnpnError(f"{who}: {B} problems / {N} nodes x {R} replicas exceed int32")
+    Q = B * R
+    ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.int64, device=dev)
+    prob_ptr = torch.empty(Q + 1, dtype=I32, device=dev)
+    n_slots = torch.empty(Q, dtype=I32, device=dev)
+    bounds = torch.empty(Q, 4, dtype=F64, device=dev)
+    status = torch.empty(Q, dtype=I32, device=dev)
+    totals = torch.empty(6, dtype=I32, device=dev)
+    check(count(*lead, dev_ptr(x, F32, "x"), x.shape[1], dev_ptr(seg_ptr, I32, "seg_ptr"),
+                dev_ptr(local_bounds, F64, "local_bounds"), dev_ptr(global_bounds, F64, "global_bounds"),
+                n_cat, dev_ptr(cat_ptr, I32, "cat_ptr"), dev_ptr(qos, F64, "qos"),
+                dev_ptr(actions, actions.dtype, "actions"), int(actions.dtype == F64), aT, float(reduct),
+                dev_ptr(pt, F64, "patches"), len(patches), max_cat, dev_ptr(ws, torch.int64, "workspace"),
+                ws.numel() * 8, dev_ptr(prob_ptr, I32, "prob_ptr"), dev_ptr(n_slots, I32, "n_slots"),
+                dev_ptr(bounds, F64, "bounds"), dev_ptr(status, I32, "status"),
+                dev_ptr(totals, I32, "totals"), stream_ptr()), entry + "_count")
+    n_lists, n_cand, max_slots, max_cand, n_bad, first_bad = totals.tolist()        # the one copy of the totals
+    if n_bad and check_status:
+        raise woa_status_error(int(status[first_bad].item()), first_bad, None if replicas is None else R)
+    cand_ptr = torch.empty(n_lists + 1, dtype=I32, device=dev)
+    len_init = torch.empty(n_lists, dtype=I32, device=dev)
+    start_pos = torch.empty(n_lists, dtype=I32, device=dev)
+    cand = torch.empty(n_cand, 4, dtype=F64, device=dev)
+    if B == 0:
+        cand_ptr.zero_()
+    check(fill(*lead, dev_ptr(seg_ptr, I32, "seg_ptr"), dev_ptr(cat_ptr, I32, "cat_ptr"),
+               dev_ptr(qos, F64, "qos"), max_cat, dev_ptr(ws, torch.int64, "workspace"), ws.numel() * 8,
+               dev_ptr(status, I32, "status"), dev_ptr(prob_ptr, I32, "prob_ptr"), n_lists, n_cand,
+               dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
+               dev_ptr(cand, F64, "cand"), dev_ptr(start_pos, I32, "start_pos"), stream_ptr()), entry + "_fill")
+    tabs = {"prob_ptr": prob_ptr, "n_slots": n_slots, "cand_ptr": cand_ptr, "len_init": len_init, "cand": cand,
+            "start_pos": start_pos, "bounds": bounds, "status": status, "max_slots": max_slots, "max_cand": max_cand}
+    if replicas is not None:
+        tabs["replicas"] = R
+    return tabs
 
 
 def woa_candidates(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct=0, patches=(), check_status=True):
@@ -1095,58 +1172,18 @@ def woa_candidates(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, action
     totals.  A problem the host path raises on raises GnnpnError naming it (``check_status=False``: returned in ``status``).
     Returns a dict: prob_ptr [B+1], n_slots [B], cand_ptr [n+1], len_init [n], cand [m,4] f64, start_pos [n], bounds [B,4],
     status [B] (device tensors) and max_slots, max_cand (ints)."""
-    lib = _lib.load()
-    dev = x.device
-    B = seg_ptr.numel() - 1
-    if actions.dim() != 3 or actions.shape[0] != B or actions.shape[2] != 8:
-        raise GnnpnError(f"woa_candidates: actions [B={B}, T, 8] expected, got {tuple(actions.shape)}")
-    if actions.dtype not in (F32, F64):
-        raise GnnpnError(f"woa_candidates: actions must be float32 or float64, got {actions.dtype}")
-    if x.dim() != 2 or local_bounds.dim() != 3 or local_bounds.shape[0] != B or local_bounds.shape[1] != cat_ptr.numel() - 1:
-        raise GnnpnError("woa_candidates: inconsistent shapes (x [N,7], local_bounds [B, T, 4] with T = len(cat_ptr) - 1)")
-    for name, t in (("cat_ptr", cat_ptr), ("qos", qos), ("x", x), ("seg_ptr", seg_ptr), ("local_bounds", local_bounds),
-                    ("global_bounds", global_bounds), ("actions", actions)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise GnnpnError(f"woa_candidates: {name}: expected a CUDA tensor (the hot path has no CPU implementation)")
-    patches = list(patches)
-    for want, col, _val in patches:
-        if len(want) != 4 or not 0 <= int(col) < 4:
-            raise GnnpnError("woa_candidates: a patch is (4 values, column 0..3, value)")
-    pt = torch.tensor([list(map(float, w)) + [float(c), float(v)] for w, c, v in patches] or [[0.0] * 6], dtype=F64).to(dev)
-    N, n_cat, aT = x.shape[0], cat_ptr.numel() - 1, actions.shape[1]
-    max_cat = int((cat_ptr[1:] - cat_ptr[:-1]).max().item()) if n_cat else 0
-    nbytes = int(lib.gnnpn_woa_candidates_workspace_bytes(B, N, max_cat))
-    ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.int64, device=dev)
-    prob_ptr = torch.empty(B + 1, dtype=I32, device=dev)
-    n_slots = torch.empty(B, dtype=I32, device=dev)
-    bounds = torch.empty(B, 4, dtype=F64, device=dev)
-    status = torch.empty(B, dtype=I32, device=dev)
-    totals = torch.empty(6, dtype=I32, device=dev)
-    check(lib.gnnpn_woa_candidates_count(B, N, dev_ptr(x, F32, "x"), x.shape[1], dev_ptr(seg_ptr, I32, "seg_ptr"),
-                                         dev_ptr(local_bounds, F64, "local_bounds"), dev_ptr(global_bounds, F64, "global_bounds"),
-                                         n_cat, dev_ptr(cat_ptr, I32, "cat_ptr"), dev_ptr(qos, F64, "qos"),
-                                         dev_ptr(actions, actions.dtype, "actions"), int(actions.dtype == F64), aT, float(reduct),
-                                         dev_ptr(pt, F64, "patches"), len(patches), max_cat, dev_ptr(ws, torch.int64, "workspace"),
-                                         ws.numel() * 8, dev_ptr(prob_ptr, I32, "prob_ptr"), dev_ptr(n_slots, I32, "n_slots"),
-                                         dev_ptr(bounds, F64, "bounds"), dev_ptr(status, I32, "status"),
-                                         dev_ptr(totals, I32, "totals"), stream_ptr()), "gnnpn_woa_candidates_count")
-    n_lists, n_cand, max_slots, max_cand, n_bad, first_bad = totals.tolist()        # the one copy of the totals
-    if n_bad and check_status:
-        raise woa_status_error(int(status[first_bad].item()), first_bad)
-    cand_ptr = torch.empty(n_lists + 1, dtype=I32, device=dev)
-    len_init = torch.empty(n_lists, dtype=I32, device=dev)
-    start_pos = torch.empty(n_lists, dtype=I32, device=dev)
-    cand = torch.empty(n_cand, 4, dtype=F64, device=dev)
-    if B == 0:
-        cand_ptr.zero_()
-    check(lib.gnnpn_woa_candidates_fill(B, N, dev_ptr(seg_ptr, I32, "seg_ptr"), dev_ptr(cat_ptr, I32, "cat_ptr"),
-                                        dev_ptr(qos, F64, "qos"), max_cat, dev_ptr(ws, torch.int64, "workspace"), ws.numel() * 8,
-                                        dev_ptr(status, I32, "status"), dev_ptr(prob_ptr, I32, "prob_ptr"), n_lists, n_cand,
-                                        dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
-                                        dev_ptr(cand, F64, "cand"), dev_ptr(start_pos, I32, "start_pos"), stream_ptr()),
-          "gnnpn_woa_candidates_fill")
-    return {"prob_ptr": prob_ptr, "n_slots": n_slots, "cand_ptr": cand_ptr, "len_init": len_init, "cand": cand,
-            "start_pos": start_pos, "bounds": bounds, "status": status, "max_slots": max_slots, "max_cand": max_cand}
+    return _woa_tables("woa_candidates", None, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches,
+                       check_status)
+
+
+def woa_candidates_replicas(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions_all, reduct=0, patches=(), check_status=True):
+    """woa_candidates for R start compositions per problem (gnnpn_woa_candidates_replicas_count / _fill): actions_all
+    [B, R, T', 8] f32 or f64; row q = b * R + r of every output is replica r of problem b with the tables woa_candidates builds
+    for actions_all[:, r] — the batch is read by indirection, nothing of it is copied per replica.  A row the host path raises on
+    raises GnnpnError naming its problem and replica (``check_status=False``: returned in ``status``).  Returns woa_candidates'
+    dict over the B * R rows (prob_ptr [B*R+1], n_slots, status [B*R], bounds [B*R,4], ...) plus ``replicas`` = R."""
+    return _woa_tables("woa_candidates_replicas", True, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions_all, reduct,
+                       patches, check_status)
 
 
 def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, max_slots=None, max_cand=None,
@@ -1212,6 +1249,44 @@ def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, m
         dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"), dev_ptr(out["history"], F64, "history"),
         dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"), stream_ptr()), "gnnpn_descend_ragged_f64")
     out["history"] = out["history"][:, :int(max_sweeps)]
+    return out
+
+
+def descend_select(res, actions_all, n_slots):
+    """Per problem, the replica whose descent ended lowest (gnnpn_descend_select_f64).  ``res``: descend_ragged's dict over B * R
+    rows, row b * R + r = replica r of problem b; actions_all [B, R, T', 8] f32 or f64: the rows the replicas started from;
+    n_slots [B * R] i32 (woa_candidates_replicas').  The key is (best_fitness, replica) under plain <: a NaN never wins, equal
+    merits (-0.0 and 0.0 too) go to the lowest replica, and where every row of a problem is NaN replica 0 is returned with its
+    NaN / -1 fields.  Returns descend_ragged's keys for the B winners plus start_index [B] i32 (the winning replica), actions
+    [B, T', 8] (its start rows, actions_all's dtype) and n_slots [B] i32."""
+    if not isinstance(actions_all, torch.Tensor) or actions_all.dim() != 4 or actions_all.shape[3] != 8 or actions_all.shape[1] < 1:
+        raise GnnpnError(f"descend_select: actions_all [B, R >= 1, T, 8] expected, got {tuple(getattr(actions_all, 'shape', ()))}")
+    if actions_all.dtype not in (F32, F64):
+        raise GnnpnError(f"descend_select: actions_all must be float32 or float64, got {actions_all.dtype}")
+    B, R, aT, _ = actions_all.shape
+    fit, pos, rows = res["best_fitness"], res["best_pos"], res["best_rows"]
+    hist = res["history"].contiguous()
+    if fit.numel() != B * R or pos.dim() != 2 or pos.shape[0] != B * R or rows.shape != (B * R, pos.shape[1], 4) or \
+            hist.shape[0] != B * R or n_slots.numel() != B * R:
+        raise GnnpnError(f"descend_select: {B} x {R} rows expected in every field of res and in n_slots")
+    dev = fit.device
+    max_slots, hist_ld = pos.shape[1], hist.shape[1]
+    out = {"best_fitness": torch.empty(B, dtype=F64, device=dev), "start_fitness": torch.empty(B, dtype=F64, device=dev),
+           "best_pos": torch.empty(B, max_slots, dtype=I32, device=dev), "best_rows": torch.empty(B, max_slots, 4, dtype=F64, device=dev),
+           "history": torch.empty(B, hist_ld, dtype=F64, device=dev), "sweeps": torch.empty(B, dtype=I32, device=dev),
+           "moves": torch.empty(B, dtype=I32, device=dev), "start_index": torch.empty(B, dtype=I32, device=dev),
+           "actions": torch.empty(B, aT, 8, dtype=actions_all.dtype, device=dev), "n_slots": torch.empty(B, dtype=I32, device=dev)}
+    adt = actions_all.dtype
+    check(_lib.load().gnnpn_descend_select_f64(
+        B, R, max_slots, hist_ld, aT, 8 * actions_all.element_size() // 4,
+        dev_ptr(fit, F64, "best_fitness"), dev_ptr(res["start_fitness"], F64, "start_fitness"), dev_ptr(res["sweeps"], I32, "sweeps"),
+        dev_ptr(res["moves"], I32, "moves"), dev_ptr(n_slots, I32, "n_slots"), dev_ptr(pos, I32, "best_pos"),
+        dev_ptr(rows, F64, "best_rows"), dev_ptr(hist, F64, "history"), dev_ptr(actions_all, adt, "actions_all"),
+        dev_ptr(out["best_fitness"], F64, "best_fitness"), dev_ptr(out["start_fitness"], F64, "start_fitness"),
+        dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"), dev_ptr(out["n_slots"], I32, "n_slots"),
+        dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"), dev_ptr(out["history"], F64, "history"),
+        dev_ptr(out["actions"], adt, "actions"), dev_ptr(out["start_index"], I32, "start_index"), stream_ptr()),
+        "gnnpn_descend_select_f64")
     return out
 
 # ---- REINFORCE training step of the High-level pointer network (csrc/train.hip; include/gnnpn_hip.h) -----------------

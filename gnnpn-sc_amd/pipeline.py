@@ -161,6 +161,33 @@ def descend(services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patche
 
 
 @torch.no_grad()
+def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
+    """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
+    [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
+    the last 8 columns are used.  Three stages, all B * N (problem, replica) rows in each launch: the candidate tables of every
+    row (gnnpn_woa_candidates_replicas_count / _fill — per replica, because with reduct != 0 the lists depend on the pick set and
+    a foreign pick is appended per replica), one gnnpn_descend_ragged_f64 over the rows, and the selection
+    (gnnpn_descend_select_f64: the smallest best_fitness, the lowest replica among equals, a NaN never).  Deterministic: no seeds.
+    A row the host path raises on raises GnnpnError naming problem and replica.  ``ML2PNPipeline.descend_starts`` is this, as a
+    method.  Returns ``descend``'s keys for the winners plus start_index [B] i32, actions [B, T', 8] (the winner's start rows:
+    ``refine(services, batch, res, ..., descend=k)`` rebuilds its tables and repeats its descent before ES-WOA), fitness_all and
+    start_fitness_all [B, N] f64, sweeps_all and moves_all [B, N] i32 (and quality [B] f64 = min_cost / best_fitness)."""
+    all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
+    if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
+        raise ops.GnnpnError(f"descend_starts: starts [B, N, T, 8|9] expected, got {tuple(getattr(all_rows, 'shape', ()))}")
+    all_rows = all_rows[..., -8:].contiguous()
+    B, N = all_rows.shape[:2]
+    tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                                       all_rows, reduct=reduct, patches=patches)
+    per_row = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
+                                 max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+    res = ops.descend_select(per_row, all_rows, tabs["n_slots"])
+    res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
+               sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
+    return _quality(res, min_cost, all_rows.device)
+
+
+@torch.no_grad()
 def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=(), descend=0):
     """The third stage: ES-WOA refinement of ``out["actions"]`` (what ``run`` returned, or any mapping with an actions
     tensor [B,T,8], float32 or float64) on the device — the candidate lists of every problem built from ``services`` /
@@ -282,15 +309,16 @@ class ML2PNPipeline:
         return out
 
     @torch.no_grad()
-    def best_of(self, services, batch, samples, seed=None, decode_impl=0, lds_kb=0, ws=None, write_through=False):
+    def best_of(self, services, batch, samples, seed=None, decode_impl=0, lds_kb=0, ws=None, write_through=False, return_all=False):
         """One pass with best-of-``samples`` decoding of the High level (modelPN.two_level_best_of): scores -> candidates ->
         the greedy pass plus samples-1 sampled High replicas, the one with the smallest R per problem.  Returns run's keys (the
         winners) plus sample_index, R_all and idx_all.  seed None: fresh OS entropy.  A separate call: run / capture are
-        unchanged; not capturable (it checks the cooperative launches' status before it returns)."""
+        unchanged; not capturable (it checks the cooperative launches' status before it returns).  ``return_all``: also actions_all
+        [B, samples, T, 8|9], every replica's rows (replica 0 the greedy ones): the starts of ``descend_starts``."""
         scores = self.scores(services, batch)
         rows, ids = self.candidates(services, batch, scores)
         out = two_level_best_of(self.low, self.high, rows, samples, seed=seed, precision=self.precision, decode_impl=decode_impl,
-                                lds_kb=lds_kb, write_through=write_through, ws=ws)
+                                lds_kb=lds_kb, write_through=write_through, ws=ws, return_all=return_all)
         out.update(scores=scores, pn_inputs=rows, candidate_ids=ids)
         return out
 
@@ -303,6 +331,11 @@ class ML2PNPipeline:
         """One-swap descent of ``out["actions"]`` on the device: module-level ``descend`` (it needs no network).  An extra call:
         ``run`` / ``capture`` are unchanged."""
         return descend(services, batch, out, max_sweeps=max_sweeps, reduct=reduct, min_cost=min_cost, patches=patches)
+
+    def descend_starts(self, services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
+        """Multi-start descent from ``best_of(..., return_all=True)``'s replicas (or any [B, N, T, 8|9] rows): module-level
+        ``descend_starts`` (it needs no network).  An extra call: ``run`` / ``capture`` are unchanged."""
+        return descend_starts(services, batch, starts, max_sweeps=max_sweeps, reduct=reduct, min_cost=min_cost, patches=patches)
 
     def capture(self, services, batch, warmup=2, decode_impl=0, lds_kb=0, ws=None, paired_start=False, pool=None, write_through=False):
         """Record one whole pass over (services, batch) into a HIP graph and return a callable that

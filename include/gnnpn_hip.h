@@ -779,6 +779,24 @@ int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists
                              int32_t max_sweeps, int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos,
                              double* best_rows, double* history, int32_t* sweeps, int32_t* moves, void* stream);
 
+/* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
+ * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
+ * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest
+ * best_fitness.  The key is (best_fitness, replica) compared with plain <: a NaN never wins; equal merits go to the lowest replica
+ * (-0.0 and 0.0 are equal); where every row of a problem is NaN (not searched: sweeps -1) replica 0 is the answer and its NaN / -1
+ * fields are what the caller sees.  Inputs over the rows: best_fitness, start_fitness, sweeps, moves, n_slots [B*R], best_pos
+ * [B*R, max_slots], best_rows [B*R, max_slots, 4], history [B*R, hist_ld] (hist_ld = 0: none), actions [B*R, actions_T,
+ * action_row_words 32-bit words]: the start rows, copied as words (8 float32 = 8 words, 8 float64 = 16; actions_T = 0: none).
+ * Outputs: the same fields of the winner with B in place of B*R, and start_index [B], the winning replica.  One wavefront per
+ * problem, no atomics.  Errors before any launch: GNNPN_E_ARG for R < 1, negative sizes, max_slots < 1, B*R beyond int32, null
+ * or misaligned operands. */
+int gnnpn_descend_select_f64(int32_t B, int32_t R, int32_t max_slots, int32_t hist_ld, int32_t actions_T, int32_t action_row_words,
+                             const double* best_fitness, const double* start_fitness, const int32_t* sweeps, const int32_t* moves,
+                             const int32_t* n_slots, const int32_t* best_pos, const double* best_rows, const double* history,
+                             const void* actions, double* best_fitness_out, double* start_fitness_out, int32_t* sweeps_out,
+                             int32_t* moves_out, int32_t* n_slots_out, int32_t* best_pos_out, double* best_rows_out,
+                             double* history_out, void* actions_out, int32_t* start_index, void* stream);
+
 /* ES-WOA inputs of an ML+2PN batch built on the device (csrc/woa_prep.hip).  Replaces what src/baselines/WOA.py:194-208 and
  * :13-26, 55-69 (`WOA.start` + `ESWOA.__init__`: action rows, the pick set, rounding, the appended pick) and
  * src/loadData.py:155-276 (`addS`, `loadDataOther`: the per-task candidate lists) do on the host, with the same results
@@ -817,6 +835,25 @@ int gnnpn_woa_candidates_fill(int32_t B, int32_t n_nodes, const int32_t* seg_ptr
                               int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status,
                               const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* cand_ptr, int32_t* len_init,
                               double* cand, int32_t* start_pos, void* stream);
+/* The same tables for R replicas per problem — R start compositions of every problem, each with the tables WOA.start would build
+ * for it (src/baselines/WOA.py:194-208, 55-69 and src/loadData.py:155-276 once per replica: with reduct != 0 the kept lists depend
+ * on the replica's pick set, loadData.py:175,193, and a foreign pick is appended per replica, WOA.py:63-68, so tables are not
+ * shared).  Row q = b * R + r is replica r of problem b.  actions [B, R, actions_T, 8]; every per-row output (prob_ptr [B*R+1],
+ * n_slots, status [B*R], bounds [B*R,4], totals over the rows, cand_ptr, len_init, cand, start_pos) and the workspace are sized and
+ * indexed by q; every per-problem input (x, seg_ptr, local_bounds, global_bounds) is read at q / R: nothing of the batch is copied
+ * per replica.  The same kernels as the entries above, which are the R = 1 call.  GNNPN_E_ARG before any launch for R < 1, or where
+ * B * R or n_nodes * R exceeds int32 (the workspace size is -1 then). */
+int64_t gnnpn_woa_candidates_replicas_workspace_bytes(int32_t B, int32_t R, int32_t n_nodes, int32_t max_cat_size);
+int gnnpn_woa_candidates_replicas_count(int32_t B, int32_t R, int32_t n_nodes, const float* x, int32_t x_ld, const int32_t* seg_ptr,
+                                        const double* local_bounds, const double* global_bounds, int32_t n_cat, const int32_t* cat_ptr,
+                                        const double* qos, const void* actions, int32_t actions_f64, int32_t actions_T, double reduct,
+                                        const double* patches, int32_t n_patches, int32_t max_cat_size, void* workspace,
+                                        int64_t workspace_bytes, int32_t* prob_ptr, int32_t* n_slots, double* bounds, int32_t* status,
+                                        int32_t* totals, void* stream);
+int gnnpn_woa_candidates_replicas_fill(int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr,
+                                       const double* qos, int32_t max_cat_size, const void* workspace, int64_t workspace_bytes,
+                                       const int32_t* status, const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand,
+                                       int32_t* cand_ptr, int32_t* len_init, double* cand, int32_t* start_pos, void* stream);
 int gnnpn_debug_round5_f64(const double* x, double* y, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

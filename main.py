@@ -19,6 +19,13 @@
                                          # [<ds>-WOA] with --woa, else 0): ./solutions/WOA/<ds>/ML+2PN+descent.txt; with --woa
                                          # the ES-WOA run starts from the descended composition
 
+    python main.py QWS ML+2PN -1 --infer --samples=N --descend[=SWEEPS] --all-starts [--seed S] [--woa]   # multi-start descent:
+                                         # descend from EVERY one of the N best-of replicas (replica 0 the greedy answer) and keep
+                                         # the lowest local optimum per problem (ties: the lowest replica):
+                                         # ./solutions/WOA/<ds>/ML+2PN+multistart.txt in place of ML+2PN+descent.txt; with --woa
+                                         # ES-WOA starts from the winner.  Needs --samples=N (N > 1) and --descend; the PNHigh
+                                         # artefact stays the best-of winner by R
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -168,6 +175,11 @@ def main(argv):
     from gnnpn_sc_amd import ML2PN
     if "--infer" in flags:
         import json
+        samples = next((a.split("=", 1)[1] for a in flags if a.startswith("--samples=")), None)
+        sweeps = next((a.split("=", 1)[1] if "=" in a else "16" for a in flags if a == "--descend" or a.startswith("--descend=")), None)
+        if "--all-starts" in flags and (samples is None or int(samples) < 2 or sweeps is None):
+            print("--all-starts: needs --samples=N (N > 1) and --descend[=SWEEPS]")
+            return 1
         with open(f"./data/{ds}/serviceFeature.data") as f:
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
@@ -180,16 +192,16 @@ def main(argv):
                    "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]),
                    "seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
         best = {}
-        samples = next((a.split("=", 1)[1] for a in flags if a.startswith("--samples=")), None)
         if samples is not None:                                     # best-of-N decoding of the High level
             args = argv[3:]
             best = {"samples": int(samples), "sample_seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
-        sweeps = next((a.split("=", 1)[1] if "=" in a else "16" for a in flags if a == "--descend" or a.startswith("--descend=")), None)
         if sweeps is not None:                                      # one-swap descent of the test quarter's actions
             if int(sweeps) < 1:
                 print("--descend=SWEEPS: at least one sweep")
                 return 1
             best["descend"] = int(sweeps)
+        if "--all-starts" in flags:                                 # descent from every best-of-N replica, the lowest optimum kept
+            best["all_starts"] = True
         ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
