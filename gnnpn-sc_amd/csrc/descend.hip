@@ -16,28 +16,6 @@
 #include <climits>
 
 namespace {
-// np.sum's block (n <= 128) over a[0..n-1] with a[jj] replaced by v, by ONE thread: pw_leaf's order (n < 8 sequential; else eight
-// accumulators, their tree, the tail)
-__device__ double leaf_sum_swapped(const double* a, int n, int jj, double v) {
-    auto at = [&](int i) { return i == jj ? v : a[i]; };
-    if (n < 8) {
-        double s = at(0);
-        for (int i = 1; i < n; ++i) s = __dadd_rn(s, at(i));
-        return s;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = at(k);
-    const int body = n - (n % 8);
-    for (int i = 8; i < body; i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __dadd_rn(r[k], at(i + k));
-    }
-    double s = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])), __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    for (int i = body; i < n; ++i) s = __dadd_rn(s, at(i));
-    return s;
-}
-
 // What a slot's candidates share: the smallest (min1, at `owner`) and second smallest (min2) entry of column 1 and the number of
 // real services (column 0 > 0) of the current composition.  Thread-uniform: every thread scans the same LDS columns.
 struct Carried {
@@ -79,211 +57,108 @@ __device__ __forceinline__ void wave_argmin(double& f, int& c, int lane) {
     }
 }
 
-// by every thread of the problem's workgroup (tid of nt): the history row is NaN too, so no entry of it is left unwritten
-__device__ __forceinline__ void not_searched(int p, int tid, int nt, double* best_fitness, double* start_fitness, double* history,
-                                             int hist_ld, int32_t* sweeps, int32_t* moves) {
-    for (int s = tid; s < hist_ld; s += nt) history[(size_t)p * hist_ld + s] = NAN;
-    if (tid != 0) return;
-    best_fitness[p] = NAN;
-    start_fitness[p] = NAN;
-    sweeps[p] = -1;
-    moves[p] = 0;
-}
-}  // namespace
+constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halves (to within 7 terms) per level
 
-// ---- lane form: one wavefront per problem (<= 64 slots), lane = one candidate of the current slot -----------------------------------
-// LDS: the four columns of cur [4][64], bounds [4], the problem's candidate table [n_cand][4], base / len / cur [64] each.
-__global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
-                                                     const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
-                                                     int32_t max_sweeps, double* __restrict__ best_fitness,
-                                                     double* __restrict__ start_fitness, int32_t* __restrict__ best_pos_out,
-                                                     double* __restrict__ history, int32_t* __restrict__ sweeps_out,
-                                                     int32_t* __restrict__ moves_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int p = blockIdx.x, lane = threadIdx.x;
+// Where a problem's state lives: the columns of cur (L.col0, col1, L.col2, L.col3), the base / len tables and the bounds in LDS;
+// cur, in LDS or the problem's best_pos row; the candidate table's LDS copy (lane form); red / cnt / sib (workgroup form).
+struct DescendMem {
+    WideLds L;
+    double* col1;      // [T] column 1 (np.min)
+    double* sib;       // [SIB_MAX] sums of the sibling blocks on np.sum's path to the current slot
+    int* cur;          // [T]
+    double* table;     // [n_cand][4]
+};
+
+// The search, once, by the NT threads of a problem's workgroup: thread = one candidate of the current slot.  TABLE_IN_LDS: the
+// problem's candidate table is copied to M.table and cur is LDS too (else the table stays in global memory and cur IS the output
+// row).  NT = 64 is one wave whose columns are [4][64]: at most 64 slots, so np.sum is always one leaf and nothing crosses waves.
+// Above 128 slots np.sum follows numpy's recursion: only the block of at most 128 terms that holds slot j changes with the
+// candidate, so a thread sums that block with its own value in it and adds the sums of the untouched sibling blocks (`sib`, formed
+// once per slot by pw_sum) on the way up, deepest first — the same additions as the recursion (a + b rounds as b + a).
+template <int NT, bool TABLE_IN_LDS>
+__device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+                                                const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                double* __restrict__ best_fitness, double* __restrict__ start_fitness,
+                                                int32_t* __restrict__ best_pos_out, double* __restrict__ history,
+                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
+    constexpr bool WAVES = NT > 64;
+    const WideLds& L = M.L;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hist_ld = max_sweeps > 1 ? max_sweeps : 1;           // history has at least one entry per problem
     const int T = sh.count(p);
     const size_t s0 = sh.first(p);
     const bool fits = sh.fits(p, T);
     const int c0 = fits ? cand_ptr[s0] : 0, n_cand = fits ? cand_ptr[s0 + T] - c0 : 0;
-    const bool live = fits && lane < T;
-    const int my_base = live ? cand_ptr[s0 + lane] - c0 : 0;
-    const int my_len = live ? cand_ptr[s0 + lane + 1] - cand_ptr[s0 + lane] : 1;
-    const int my_pos = live && start_pos[s0] >= 0 ? start_pos[s0 + lane] : 0;
-    // a list outside the problem's table, an empty list or a start outside its list: not searched either
-    const bool bad = my_base < 0 || my_len < 1 || my_base + my_len > n_cand || my_pos < 0 || my_pos >= my_len;
-    if (!fits || n_cand < 0 || !sh.fits_cand(n_cand) || __any(live && bad)) {      // not what the launch was sized for: no search
-        not_searched(p, lane, 64, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
+    const bool seeded = fits && start_pos[s0] >= 0;
+    // not what the launch was sized for, a list outside the table, an empty list, a start outside its list: no search.  One test
+    // after the loop, so that all these loads are in flight together.
+    int bad = !fits || n_cand < 0 || !sh.fits_cand(n_cand);
+    for (int j = tid; j < (fits ? T : 0); j += NT) {
+        const int b = cand_ptr[s0 + j] - c0, ln = cand_ptr[s0 + j + 1] - cand_ptr[s0 + j], x = seeded ? start_pos[s0 + j] : 0;
+        bad |= b < 0 || ln < 1 || b + ln > n_cand || x < 0 || x >= ln;
+        L.base[j] = b;
+        L.len[j] = ln;
+    }
+    if constexpr (WAVES) bad = __syncthreads_or(bad);
+    else bad = __any(bad);
+    if (bad) {
+        not_searched(p, tid, NT, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
         return;
     }
-    double* col = reinterpret_cast<double*>(lds_raw);                 // [4][64]: the columns of cur
-    double* bounds = col + 256;                                       // [4]
-    double* cand = bounds + 4;                                        // [n_cand][4]
-    int* base = reinterpret_cast<int*>(cand + (size_t)n_cand * 4);    // [64]
-    int* len = base + 64;                                             // [64]
-    int* cur = len + 64;                                              // [64]
-    for (int i = lane; i < n_cand * 4; i += 64) cand[i] = cand_g[(size_t)c0 * 4 + i];
-    if (lane < 4) bounds[lane] = bounds_g[(size_t)p * 4 + lane];
-    if (live) {
-        base[lane] = my_base;
-        len[lane] = my_len;
-        cur[lane] = my_pos;
+    const double* cand = cand_g + (size_t)c0 * 4;
+    if constexpr (TABLE_IN_LDS) {
+        for (int i = tid; i < n_cand * 4; i += NT) M.table[i] = cand[i];
+        cand = M.table;
+    }
+    if (tid < 4) L.bounds[tid] = bounds_g[(size_t)p * 4 + tid];
+    for (int j = tid; j < T; j += NT) {
+        const int x = seeded ? start_pos[s0 + j] : 0;
+        M.cur[j] = x;
+        if constexpr (WAVES) M.col1[j] = cand[(size_t)(L.base[j] + x) * 4 + 1];
     }
     __syncthreads();
-    double q[4] = {0.0, 0.0, 0.0, 0.0};
-    if (live) gather_row(cand, my_base, my_len, my_pos, q);
-    double fit = figure_of_merit(q, T, lane, col, bounds);            // leaves the columns of cur in col
-    if (lane == 0) start_fitness[p] = fit;
+    double fit;                                                       // the start's merit; leaves the columns of cur in LDS
+    if constexpr (WAVES) {
+        fit = wide_merit(L, M.cur, cand, T, tid);
+    } else {
+        double q[4] = {0.0, 0.0, 0.0, 0.0};
+        if (lane < T) gather_row(cand, L.base[lane], L.len[lane], M.cur[lane], q);
+        fit = figure_of_merit(q, T, lane, L.col0, L.bounds);
+    }
+    if (tid == 0) start_fitness[p] = fit;
     Carried cr;
-    cr.scan(col, col + 64, T);
+    cr.scan(L.col0, M.col1, T);
 
     int sweeps = 0, moves = 0;
     for (int s = 0; s < max_sweeps; ++s) {
         bool improved = false;
         double pre2 = 1.0, pre3 = 1.0;                                // np.cumprod of columns 2 and 3 up to slot j - 1
         for (int j = 0; j < T; ++j) {
-            const int bj = base[j], lj = len[j];
-            const double old0 = col[j];
-            double bf = INFINITY;
-            int bc = INT_MAX;
-            for (int c = lane; c < lj; c += 64) {                     // lists longer than the wave: chunks, lowest position first
-                const double* r = cand + (size_t)(bj + c) * 4;
-                const double q0 = r[0], q1 = r[1];
-                double p2 = j == 0 ? r[2] : __dmul_rn(pre2, r[2]), p3 = j == 0 ? r[3] : __dmul_rn(pre3, r[3]);
-                for (int i = j + 1; i < T; ++i) {
-                    p2 = __dmul_rn(p2, col[128 + i]);
-                    p3 = __dmul_rn(p3, col[192 + i]);
+            int off = 0, ln = T, depth = 0;                           // np.sum's leaf block of slot j
+            if constexpr (WAVES) {                                    // its path from the root: the siblings' sums, root first
+                while (ln > 128 && depth < SIB_MAX) {
+                    int n2 = ln / 2;
+                    n2 -= n2 % 8;
+                    int so, sl;
+                    if (j < off + n2) {
+                        so = off + n2; sl = ln - n2; ln = n2;
+                    } else {
+                        so = off; sl = n2; off += n2; ln -= n2;
+                    }
+                    if (wave == 0) {
+                        const double v = pw_sum(L.col0 + so, sl, lane);
+                        if (lane == 0) M.sib[depth] = v;
+                    }
+                    ++depth;
                 }
-                const double sum = leaf_sum_swapped(col, T, j, q0);
-                const double f = merit_of(sum, cr.real_with(old0, q0), cr.min_with(j, q1), p2, p3, bounds);
-                if (f < bf) {
-                    bf = f;
-                    bc = c;
-                }
+                __syncthreads();                                      // sib is written, red / cnt of slot j - 1 are read
             }
-            wave_argmin(bf, bc, lane);
-            if (bf < fit) {                                           // wave-uniform
-                if (lane < 4) col[lane * 64 + j] = cand[(size_t)(bj + bc) * 4 + lane];
-                if (lane == 0) cur[j] = bc;
-                fit = bf;
-                ++moves;
-                improved = true;
-                __syncthreads();
-                cr.scan(col, col + 64, T);
-            }
-            pre2 = j == 0 ? col[128] : __dmul_rn(pre2, col[128 + j]);
-            pre3 = j == 0 ? col[192] : __dmul_rn(pre3, col[192 + j]);
-        }
-        ++sweeps;
-        if (lane == 0) history[(size_t)p * hist_ld + s] = fit;
-        if (!improved) break;
-    }
-    for (int s = sweeps + lane; s < hist_ld; s += 64) history[(size_t)p * hist_ld + s] = fit;      // max_sweeps = 0: the start
-    if (lane < T) {
-        best_pos_out[sh.out_row(p) + lane] = cur[lane];
-        if (double* rows = sh.rows_out(p)) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) rows[(size_t)lane * 4 + c] = col[c * 64 + lane];
-        }
-    }
-    if (lane == 0) {
-        best_fitness[p] = fit;
-        sweeps_out[p] = sweeps;
-        moves_out[p] = moves;
-    }
-}
-
-// ---- workgroup form: any slot count, 256 threads per problem, thread = one candidate of the current slot ------------------------------
-// The columns of cur and the base / len tables live in LDS (WideLds, plus column 1 and the sibling sums below), cur itself is the
-// problem's best_pos row, the candidate table stays in global memory.  Above 128 slots np.sum follows numpy's recursion: only the
-// block of at most 128 terms that holds slot j changes with the candidate, so a thread sums that block with its own value in it and
-// adds the sums of the untouched sibling blocks (`sib`, formed once per slot by pw_sum) on the way up, deepest first — the same
-// additions as the recursion (a + b rounds as b + a).
-namespace {
-constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halves (to within 7 terms) per level
-}
-
-__global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
-                                                           const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
-                                                           const int32_t* __restrict__ start_pos, int32_t max_sweeps,
-                                                           double* __restrict__ best_fitness, double* __restrict__ start_fitness,
-                                                           int32_t* __restrict__ best_pos_out, double* __restrict__ history,
-                                                           int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hist_ld = max_sweeps > 1 ? max_sweeps : 1;
-    const int T = sh.count(p);
-    const size_t s0 = sh.first(p);
-    if (!sh.fits(p, T)) {                                             // not what the launch was sized for: no search
-        not_searched(p, tid, WNT, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
-        return;
-    }
-    WideLds L;
-    L.col0 = reinterpret_cast<double*>(lds_raw);
-    L.col2 = L.col0 + T;
-    L.col3 = L.col2 + T;
-    L.red = L.col3 + T;
-    L.bounds = L.red + 8;
-    double* col1 = L.bounds + 4;                                      // [T]
-    double* sib = col1 + T;                                           // [SIB_MAX]
-    L.cnt = reinterpret_cast<int*>(sib + SIB_MAX);
-    L.base = L.cnt + 4;
-    L.len = L.base + T;
-    const int c0 = cand_ptr[s0], n_cand = cand_ptr[s0 + T] - c0;
-    const double* cand = cand_g + (size_t)c0 * 4;
-    int* cur = best_pos_out + sh.out_row(p);                          // the composition being improved IS the output row
-    const bool seeded = start_pos[s0] >= 0;
-    int bad = 0;
-    for (int j = tid; j < T; j += WNT) {
-        const int b = cand_ptr[s0 + j] - c0, ln = cand_ptr[s0 + j + 1] - cand_ptr[s0 + j], x = seeded ? start_pos[s0 + j] : 0;
-        bad |= b < 0 || ln < 1 || b + ln > n_cand || x < 0 || x >= ln;
-        L.base[j] = b;
-        L.len[j] = ln;
-    }
-    if (__syncthreads_or(bad)) {                                      // a list outside the table, an empty list, a start outside its list
-        not_searched(p, tid, WNT, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
-        return;
-    }
-    for (int j = tid; j < T; j += WNT) {
-        const int x = seeded ? start_pos[s0 + j] : 0;
-        cur[j] = x;
-        col1[j] = cand[(size_t)(L.base[j] + x) * 4 + 1];
-    }
-    if (tid < 4) L.bounds[tid] = bounds_g[(size_t)p * 4 + tid];
-    __syncthreads();
-    double fit = wide_merit(L, cur, cand, T, tid);                    // leaves columns 0, 2 and 3 of cur in LDS
-    if (tid == 0) start_fitness[p] = fit;
-    Carried cr;
-    cr.scan(L.col0, col1, T);
-
-    int sweeps = 0, moves = 0;
-    for (int s = 0; s < max_sweeps; ++s) {
-        bool improved = false;
-        double pre2 = 1.0, pre3 = 1.0;
-        for (int j = 0; j < T; ++j) {
-            // np.sum's path to the block of slot j: the siblings' sums, root first
-            int off = 0, ln = T, depth = 0;
-            while (ln > 128 && depth < SIB_MAX) {
-                int n2 = ln / 2;
-                n2 -= n2 % 8;
-                int so, sl;
-                if (j < off + n2) {
-                    so = off + n2; sl = ln - n2; ln = n2;
-                } else {
-                    so = off; sl = n2; off += n2; ln -= n2;
-                }
-                if (wave == 0) {
-                    const double v = pw_sum(L.col0 + so, sl, lane);
-                    if (lane == 0) sib[depth] = v;
-                }
-                ++depth;
-            }
-            __syncthreads();
             const int bj = L.base[j], lj = L.len[j];
             const double old0 = L.col0[j];
             double bf = INFINITY;
             int bc = INT_MAX;
-            for (int c = tid; c < lj; c += WNT) {
+            for (int c = tid; c < lj; c += NT) {                      // lists longer than the workgroup: chunks, lowest position first
                 const double* r = cand + (size_t)(bj + c) * 4;
                 const double q0 = r[0], q1 = r[1];
                 double p2 = j == 0 ? r[2] : __dmul_rn(pre2, r[2]), p3 = j == 0 ? r[3] : __dmul_rn(pre3, r[3]);
@@ -291,8 +166,9 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
                     p2 = __dmul_rn(p2, L.col2[i]);
                     p3 = __dmul_rn(p3, L.col3[i]);
                 }
-                double sum = leaf_sum_swapped(L.col0 + off, ln, j - off, q0);
-                for (int d = depth - 1; d >= 0; --d) sum = __dadd_rn(sum, sib[d]);
+                double sum = pw_leaf_swapped(L.col0 + off, ln, j - off, q0);
+                if constexpr (WAVES)
+                    for (int d = depth - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
                 const double f = merit_of(sum, cr.real_with(old0, q0), cr.min_with(j, q1), p2, p3, L.bounds);
                 if (f < bf) {
                     bf = f;
@@ -300,20 +176,22 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
                 }
             }
             wave_argmin(bf, bc, lane);
-            if (lane == 0) {
-                L.red[wave] = bf;
-                L.cnt[wave] = bc;
+            if constexpr (WAVES) {
+                if (lane == 0) {
+                    L.red[wave] = bf;
+                    L.cnt[wave] = bc;
+                }
+                __syncthreads();
+                bf = L.red[0];
+                bc = L.cnt[0];
+                for (int w = 1; w < NT / 64; ++w) take_better(bf, bc, L.red[w], L.cnt[w]);
             }
-            __syncthreads();
-            bf = L.red[0];
-            bc = L.cnt[0];
-            for (int w = 1; w < WNT / 64; ++w) take_better(bf, bc, L.red[w], L.cnt[w]);
             if (bf < fit) {                                           // workgroup-uniform
                 if (tid == 0) {
                     const double* r = cand + (size_t)(bj + bc) * 4;
-                    cur[j] = bc;
+                    M.cur[j] = bc;
                     L.col0[j] = r[0];
-                    col1[j] = r[1];
+                    M.col1[j] = r[1];
                     L.col2[j] = r[2];
                     L.col3[j] = r[3];
                 }
@@ -321,7 +199,7 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
                 ++moves;
                 improved = true;
                 __syncthreads();
-                cr.scan(L.col0, col1, T);
+                cr.scan(L.col0, M.col1, T);
             }
             pre2 = j == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[j]);
             pre3 = j == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[j]);
@@ -330,11 +208,13 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
         if (tid == 0) history[(size_t)p * hist_ld + s] = fit;
         if (!improved) break;
     }
-    for (int s = sweeps + tid; s < hist_ld; s += WNT) history[(size_t)p * hist_ld + s] = fit;
-    if (double* rows = sh.rows_out(p)) {
-        for (int j = tid; j < T; j += WNT) {
+    for (int s = sweeps + tid; s < hist_ld; s += NT) history[(size_t)p * hist_ld + s] = fit;       // max_sweeps = 0: the start
+    double* rows = sh.rows_out(p);
+    for (int j = tid; j < T; j += NT) {
+        if constexpr (TABLE_IN_LDS) best_pos_out[sh.out_row(p) + j] = M.cur[j];
+        if (rows) {
             rows[(size_t)j * 4 + 0] = L.col0[j];
-            rows[(size_t)j * 4 + 1] = col1[j];
+            rows[(size_t)j * 4 + 1] = M.col1[j];
             rows[(size_t)j * 4 + 2] = L.col2[j];
             rows[(size_t)j * 4 + 3] = L.col3[j];
         }
@@ -345,8 +225,51 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
         moves_out[p] = moves;
     }
 }
+}  // namespace
 
-// LDS bytes one problem needs (host side).  Lane form: the columns + bounds + its candidate table + base / len / cur.  Workgroup
+// ---- lane form: one wavefront per problem (<= 64 slots) --------------------------------------------------------------------------------
+// LDS: the four columns of cur [4][64] (figure_of_merit's layout), bounds [4], base / len / cur [64] each, the problem's candidate
+// table [n_cand][4].
+__global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
+                                                     const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
+                                                     int32_t max_sweeps, double* __restrict__ best_fitness,
+                                                     double* __restrict__ start_fitness, int32_t* __restrict__ best_pos_out,
+                                                     double* __restrict__ history, int32_t* __restrict__ sweeps_out,
+                                                     int32_t* __restrict__ moves_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    double* col = reinterpret_cast<double*>(lds_raw);
+    int* tab = reinterpret_cast<int*>(col + 260);
+    DescendMem M;
+    M.L = WideLds{col, col + 128, col + 192, nullptr, nullptr, tab, tab + 64, col + 256};
+    M.col1 = col + 64;
+    M.sib = nullptr;
+    M.cur = tab + 128;
+    M.table = reinterpret_cast<double*>(tab + 192);
+    descend_problem<64, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness, best_pos_out, history,
+                              sweeps_out, moves_out);
+}
+
+// ---- workgroup form: any slot count, 256 threads per problem ----------------------------------------------------------------------------
+// The columns of cur and the base / len tables live in LDS (WideLds, plus column 1 and the sibling sums), cur itself is the problem's
+// best_pos row, the candidate table stays in global memory.
+__global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                           const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                           const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                           double* __restrict__ best_fitness, double* __restrict__ start_fitness,
+                                                           int32_t* __restrict__ best_pos_out, double* __restrict__ history,
+                                                           int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int T = sh.count(blockIdx.x);
+    DescendMem M;
+    M.col1 = M.L.carve(lds_raw, T, T + SIB_MAX);
+    M.sib = M.col1 + T;
+    M.cur = best_pos_out + sh.out_row(blockIdx.x);
+    M.table = nullptr;
+    descend_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness, best_pos_out,
+                                history, sweeps_out, moves_out);
+}
+
+// LDS bytes one problem needs (host side).  Lane form: the columns + bounds + base / len / cur + its candidate table.  Workgroup
 // form: four columns, red[8] + bounds[4] + sib[SIB_MAX], cnt[4] + base / len tables.
 static size_t descend_lds_bytes(int n_cand) { return (256 + 4 + (size_t)n_cand * 4) * sizeof(double) + 3 * 64 * sizeof(int); }
 static size_t descend_wide_lds_bytes(int T) { return ((size_t)4 * T + 12 + SIB_MAX) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int); }
@@ -363,22 +286,18 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
     const bool use_wide = wide || max_slots > 64;
     if (!use_wide) GNNPN_REQUIRE(max_cand >= 1, "descend_ragged: max_cand must be >= 1 for the lane form");
     const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots) : descend_lds_bytes(max_cand);
-    if (lds > 160 * 1024 - 1024) {
+    auto too_large = [&]() -> int {
         if (use_wide)
             GNNPN_FAIL(GNNPN_E_UNSUP, "descend_ragged: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", max_slots, lds);
         GNNPN_FAIL(GNNPN_E_UNSUP, "descend_ragged: %zu B of LDS per problem (%d candidates) exceed a CU; wide=1 keeps the candidate "
                    "table in global memory", lds, max_cand);
-    }
+    };
     const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, n_lists, best_rows};
-    const char* entry = use_wide ? "descend_ragged_f64 (workgroup form)" : "descend_ragged_f64";
-    const int rc = use_wide ? gnnpn_launch_lds(descend_wide_kernel, dim3(B), dim3(WNT), lds, (hipStream_t)stream, entry, sh, cand_ptr, cand,
-                                               bounds, start_pos, max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves)
-                            : gnnpn_launch_lds(descend_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, entry, sh, cand_ptr, cand,
-                                               bounds, start_pos, max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
-    if (rc != GNNPN_OK) return rc;
-    GNNPN_CHECK_LAUNCH(entry);
-    return GNNPN_OK;
+    return search_launch(lds, too_large, use_wide ? descend_wide_kernel : descend_kernel, B, use_wide ? WNT : 64, stream,
+                         use_wide ? "descend_ragged_f64 (workgroup form)" : "descend_ragged_f64", sh, cand_ptr, cand, bounds, start_pos,
+                         max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
 }
+
 
 // ---- selection among the replicas of a problem: one wavefront per problem -----------------------------------------------------------
 // Rows are problem-major (row b * R + r = replica r of problem b, what one gnnpn_descend_ragged_f64 launch over B * R rows wrote).

@@ -43,10 +43,7 @@ __global__ __launch_bounds__(64) void eswoa_kernel(Shape sh, const int32_t* __re
     const bool fits = sh.fits(p, T);
     const int c0 = fits ? cand_ptr[s0] : 0, n_cand = fits ? cand_ptr[s0 + T] - c0 : 0;
     if (!fits || !sh.fits_cand(n_cand)) {                             // not what the launch was sized for: no search
-        if (lane == 0) {
-            best_fitness[p] = NAN;
-            draws_out[p] = -1;
-        }
+        not_searched(p, lane, best_fitness, draws_out);
         return;
     }
     double* col = reinterpret_cast<double*>(lds_raw);                 // [4][64]
@@ -189,21 +186,11 @@ __global__ __launch_bounds__(WNT) void eswoa_wide_kernel(Shape sh, const int32_t
     const int T = sh.count(p);
     const size_t s0 = sh.first(p);
     if (!sh.fits(p, T)) {                                             // not what the launch was sized for: no search
-        if (tid == 0) {
-            best_fitness[p] = NAN;
-            draws_out[p] = -1;
-        }
+        not_searched(p, tid, best_fitness, draws_out);
         return;
     }
     WideLds L;
-    L.col0 = reinterpret_cast<double*>(lds_raw);
-    L.col2 = L.col0 + T;
-    L.col3 = L.col2 + T;
-    L.red = L.col3 + T;
-    L.bounds = L.red + 8;
-    L.cnt = reinterpret_cast<int*>(L.bounds + 4);
-    L.base = L.cnt + 4;
-    L.len = L.base + T;
+    L.carve(lds_raw, T);
     const int c0 = cand_ptr[s0];
     const double* cand = cand_g + (size_t)c0 * 4;
     int* pos = pos_ws + (size_t)pop * s0;                 // [pop][T]
@@ -323,31 +310,26 @@ static size_t eswoa_lds_bytes(int n_cand, int pop, int T) {
 }
 
 // The one launch of both forms (`wide`: the workgroup form, positions in `workspace`), sized for sh.stride categories per
-// problem; `who` names the entry point in the messages, `entry` in a launch error
-// (gnnpn_launch_lds, common.h).
+// problem; `who` names the entry point in the messages, `entry` in a launch error (search_launch, woa_eval.h).
 static int eswoa_launch(const char* who, const char* entry, bool wide, int32_t B, const Shape& sh, const int32_t* cand_ptr,
                         const int32_t* len_init, const double* cand, const double* bounds, const int32_t* start_pos, int32_t pop,
                         int32_t max_iter, const uint64_t* seeds, void* workspace, double* best_fitness, int32_t* best_pos,
                         double* history, int64_t* draws, void* stream) {
     const int T = sh.stride;
     const size_t lds = wide ? eswoa_wide_lds_bytes(T) : eswoa_lds_bytes(sh.max_cand, pop, T);
-    if (lds > 160 * 1024 - 1024) {
+    auto too_large = [&]() -> int {
         if (wide)
             GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %s%d categories need %zu B of LDS for the three QoS columns (a CU has 160 KB)", who,
                        sh.prob_ptr ? "" : "T=", T, lds);
         GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (population %d x %d, %d candidates) exceed a CU", who, lds, pop, T,
                    sh.max_cand);
-    }
+    };
     const auto* sd = reinterpret_cast<const unsigned long long*>(seeds);
     auto* dr = reinterpret_cast<long long*>(draws);
-    const int rc = wide ? gnnpn_launch_lds(eswoa_wide_kernel, dim3(B), dim3(WNT), lds, (hipStream_t)stream, entry, sh, cand_ptr, len_init,
-                                           cand, bounds, start_pos, pop, max_iter, sd, reinterpret_cast<int32_t*>(workspace),
-                                           best_fitness, best_pos, history, dr)
-                        : gnnpn_launch_lds(eswoa_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, entry, sh, cand_ptr, len_init, cand,
-                                           bounds, start_pos, pop, max_iter, sd, best_fitness, best_pos, history, dr);
-    if (rc != GNNPN_OK) return rc;
-    GNNPN_CHECK_LAUNCH(entry);
-    return GNNPN_OK;
+    return wide ? search_launch(lds, too_large, eswoa_wide_kernel, B, WNT, stream, entry, sh, cand_ptr, len_init, cand, bounds, start_pos,
+                                pop, max_iter, sd, reinterpret_cast<int32_t*>(workspace), best_fitness, best_pos, history, dr)
+                : search_launch(lds, too_large, eswoa_kernel, B, 64, stream, entry, sh, cand_ptr, len_init, cand, bounds, start_pos, pop,
+                                max_iter, sd, best_fitness, best_pos, history, dr);
 }
 
 extern "C" int64_t gnnpn_eswoa_wide_workspace_bytes(int32_t P, int32_t T, int32_t pop) {

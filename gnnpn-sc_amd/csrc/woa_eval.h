@@ -24,8 +24,51 @@ __device__ __forceinline__ double merit_of(double sum, int n_real, double mn, do
     return __dadd_rn((double)violate, obj);
 }
 
+// np.sum's block (pairwise_sum, n <= 128: n < 8 sequential; else eight accumulators, their tree, the tail), stated twice: by one
+// wave over a[0..n-1], the result in every lane, and (pw_leaf_swapped) by ONE thread with a[jj] replaced by v.
+__device__ double pw_leaf(const double* a, int n, int lane) {
+    double sum = 0.0;
+    if (n < 8) {
+        if (lane == 0) {
+            sum = a[0];
+            for (int i = 1; i < n; ++i) sum = __dadd_rn(sum, a[i]);
+        }
+        return wave_bcast(sum, 0);
+    }
+    double r = 0.0;
+    const int body = n - (n % 8);
+    if (lane < 8) {
+        r = a[lane];
+        for (int i = 8; i < body; i += 8) r = __dadd_rn(r, a[i + lane]);
+    }
+    const double r0 = wave_bcast(r, 0), r1 = wave_bcast(r, 1), r2 = wave_bcast(r, 2), r3 = wave_bcast(r, 3);
+    const double r4 = wave_bcast(r, 4), r5 = wave_bcast(r, 5), r6 = wave_bcast(r, 6), r7 = wave_bcast(r, 7);
+    sum = __dadd_rn(__dadd_rn(__dadd_rn(r0, r1), __dadd_rn(r2, r3)), __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
+    for (int i = body; i < n; ++i) sum = __dadd_rn(sum, a[i]);
+    return sum;
+}
+__device__ double pw_leaf_swapped(const double* a, int n, int jj, double v) {
+    auto at = [&](int i) { return i == jj ? v : a[i]; };
+    if (n < 8) {
+        double s = at(0);
+        for (int i = 1; i < n; ++i) s = __dadd_rn(s, at(i));
+        return s;
+    }
+    double r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = at(k);
+    const int body = n - (n % 8);
+    for (int i = 8; i < body; i += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = __dadd_rn(r[k], at(i + k));
+    }
+    double s = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])), __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
+    for (int i = body; i < n; ++i) s = __dadd_rn(s, at(i));
+    return s;
+}
+
 // violate + objFunc of the composition whose category-j row is (q[0..3]) in lane j (lanes >= T idle).
-// `col` = 4 x 64 doubles of LDS scratch.
+// `col` = 4 x 64 doubles of LDS scratch, which holds the composition's four columns afterwards.
 __device__ double figure_of_merit(const double (&q)[4], int T, int lane, double* col, const double* bounds) {
     if (lane < T) {
 #pragma unroll
@@ -39,26 +82,7 @@ __device__ double figure_of_merit(const double (&q)[4], int T, int lane, double*
         prod = a[0];
         for (int i = 1; i < T; ++i) prod = __dmul_rn(prod, a[i]);
     }
-    // np.sum of column 0 (pairwise_sum, n <= 128): n < 8 sequential; else 8 accumulators, tree, tail
-    double sum = 0.0;
-    if (T < 8) {
-        if (lane == 0) {
-            sum = col[0];
-            for (int i = 1; i < T; ++i) sum = __dadd_rn(sum, col[i]);
-        }
-    } else {
-        double r = 0.0;
-        const int body = T - (T % 8);
-        if (lane < 8) {
-            r = col[lane];
-            for (int i = 8; i < body; i += 8) r = __dadd_rn(r, col[i + lane]);
-        }
-        const double r0 = wave_bcast(r, 0), r1 = wave_bcast(r, 1), r2 = wave_bcast(r, 2), r3 = wave_bcast(r, 3);
-        const double r4 = wave_bcast(r, 4), r5 = wave_bcast(r, 5), r6 = wave_bcast(r, 6), r7 = wave_bcast(r, 7);
-        sum = __dadd_rn(__dadd_rn(__dadd_rn(r0, r1), __dadd_rn(r2, r3)), __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
-        for (int i = body; i < T; ++i) sum = __dadd_rn(sum, col[i]);
-    }
-    sum = wave_bcast(sum, 0);
+    const double sum = pw_leaf(col, T, lane);                         // np.sum of column 0: T <= 64 is one block
     const double prod2 = wave_bcast(prod, 0), prod3 = wave_bcast(prod, 1);
     // serviceNum and np.min(column 1): exact reductions
     const unsigned long long real = __ballot(lane < T && q[0] > 0.0);
@@ -106,28 +130,23 @@ struct Shape {
 namespace {
 constexpr int WNT = 256;
 
-// numpy's pairwise block (n <= 128) by one wave: result in every lane
-__device__ double pw_leaf(const double* a, int n, int lane) {
-    double sum = 0.0;
-    if (n < 8) {
-        if (lane == 0) {
-            sum = a[0];
-            for (int i = 1; i < n; ++i) sum = __dadd_rn(sum, a[i]);
-        }
-        return wave_bcast(sum, 0);
-    }
-    double r = 0.0;
-    const int body = n - (n % 8);
-    if (lane < 8) {
-        r = a[lane];
-        for (int i = 8; i < body; i += 8) r = __dadd_rn(r, a[i + lane]);
-    }
-    const double r0 = wave_bcast(r, 0), r1 = wave_bcast(r, 1), r2 = wave_bcast(r, 2), r3 = wave_bcast(r, 3);
-    const double r4 = wave_bcast(r, 4), r5 = wave_bcast(r, 5), r6 = wave_bcast(r, 6), r7 = wave_bcast(r, 7);
-    sum = __dadd_rn(__dadd_rn(__dadd_rn(r0, r1), __dadd_rn(r2, r3)), __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
-    for (int i = body; i < n; ++i) sum = __dadd_rn(sum, a[i]);
-    return sum;
+// What a problem that is not searched leaves behind, by every thread of its workgroup (tid of nt).  ES-WOA: nothing else is touched.
+__device__ __forceinline__ void not_searched(int p, int tid, double* best_fitness, long long* draws) {
+    if (tid != 0) return;
+    best_fitness[p] = NAN;
+    draws[p] = -1;
 }
+// Descent: the history row is NaN too, so no entry of it is left unwritten.
+__device__ __forceinline__ void not_searched(int p, int tid, int nt, double* best_fitness, double* start_fitness, double* history,
+                                             int hist_ld, int32_t* sweeps, int32_t* moves) {
+    for (int s = tid; s < hist_ld; s += nt) history[(size_t)p * hist_ld + s] = NAN;
+    if (tid != 0) return;
+    best_fitness[p] = NAN;
+    start_fitness[p] = NAN;
+    sweeps[p] = -1;
+    moves[p] = 0;
+}
+
 // np.sum of n doubles (pairwise_sum): post-order walk of the recursion with an explicit stack (depth <= log2(n / 128) + 1)
 __device__ double pw_sum(const double* a, int n, int lane) {
     int off[24], len[24], st[24];
@@ -171,6 +190,20 @@ struct WideLds {
     int* base;         // [T]
     int* len;          // [T]
     double* bounds;    // [4]
+    // The carve-up of a problem's dynamic LDS, the one statement of the layout the host's *_wide_lds_bytes size: the doubles
+    // (three columns, red, bounds, then `extra` more for the caller, returned), then the ints.
+    __device__ __forceinline__ double* carve(unsigned char* raw, int T, int extra = 0) {
+        col0 = reinterpret_cast<double*>(raw);
+        col2 = col0 + T;
+        col3 = col2 + T;
+        red = col3 + T;
+        bounds = red + 8;
+        double* more = bounds + 4;
+        cnt = reinterpret_cast<int*>(more + extra);
+        base = cnt + 4;
+        len = base + T;
+        return more;
+    }
 };
 
 // figure of merit of the composition pos[j] (j < T), every thread returns it
@@ -216,5 +249,17 @@ __device__ double wide_merit(const WideLds& L, const int* pos, const double* can
     const double f = merit_of(sum, n_real, mn, prod2, prod3, L.bounds);
     __syncthreads();                                      // the columns and red[] are free again
     return f;
+}
+
+// The one launch of a search kernel (host side): one workgroup of `nt` threads per problem with `lds` bytes of dynamic LDS.  Above
+// what a CU can give, `too_large` writes the entry point's message and returns its code; nothing is launched then.
+template <class TooLarge, typename... P, typename... A>
+int search_launch(size_t lds, TooLarge too_large, void (*kernel)(P...), int32_t B, int nt, void* stream, const char* entry,
+                  const A&... args) {
+    if (lds > 160 * 1024 - 1024) return too_large();
+    const int rc = gnnpn_launch_lds(kernel, dim3(B), dim3(nt), lds, (hipStream_t)stream, entry, args...);
+    if (rc != GNNPN_OK) return rc;
+    GNNPN_CHECK_LAUNCH(entry);
+    return GNNPN_OK;
 }
 }  // namespace

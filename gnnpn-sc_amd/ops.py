@@ -1186,6 +1186,25 @@ def woa_candidates_replicas(cat_ptr, qos, x, seg_ptr, local_bounds, global_bound
                        patches, check_status)
 
 
+def _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand):
+    """(max_slots, max_cand) of a ragged batch, both >= 1: the largest list count / candidate count of a problem, read back from
+    the device where the caller gave None."""
+    B = prob_ptr.numel() - 1
+    if max_slots is None:
+        max_slots = int((prob_ptr[1:] - prob_ptr[:-1]).max().item()) if B else 1
+    if max_cand is None:
+        max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
+    return max(int(max_slots), 1), max(int(max_cand), 1)
+
+
+def _descent_fields(B, max_slots, hist_ld, dev, rows=torch.empty):
+    """descend_ragged's seven fields for B problems; ``rows`` allocates best_pos / best_rows (zeros: 0 past a problem's count)."""
+    return {"best_fitness": torch.empty(B, dtype=F64, device=dev), "start_fitness": torch.empty(B, dtype=F64, device=dev),
+            "best_pos": rows(B, max_slots, dtype=I32, device=dev), "best_rows": rows(B, max_slots, 4, dtype=F64, device=dev),
+            "history": torch.empty(B, hist_ld, dtype=F64, device=dev), "sweeps": torch.empty(B, dtype=I32, device=dev),
+            "moves": torch.empty(B, dtype=I32, device=dev)}
+
+
 def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max_iter, seeds, max_slots=None, max_cand=None,
                  wide=None):
     """ES-WOA over a batch whose problems differ in their number of categories, in ONE launch (gnnpn_eswoa_ragged_f64).
@@ -1201,11 +1220,7 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
     I64 = torch.int64
     if n != len_init.numel() or n != start_pos.numel() or bounds.shape != (B, 4) or seeds.numel() != B:
         raise GnnpnError("eswoa_ragged: inconsistent operand sizes")
-    if max_slots is None:
-        max_slots = int((prob_ptr[1:] - prob_ptr[:-1]).max().item()) if B else 1
-    if max_cand is None:
-        max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
-    max_slots, max_cand = max(int(max_slots), 1), max(int(max_cand), 1)
+    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
     lib = _lib.load()
     nbytes = int(lib.gnnpn_eswoa_ragged_workspace_bytes(n, max_slots, int(pop), int(bool(wide))))
     best_fit, best_pos, history, draws, ws = _eswoa_buffers(B, max_slots, max_iter, nbytes, dev, fill=torch.zeros)
@@ -1233,15 +1248,8 @@ def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, m
     n = cand_ptr.numel() - 1
     if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0:
         raise GnnpnError("descend_ragged: inconsistent operand sizes")
-    if max_slots is None:
-        max_slots = int((prob_ptr[1:] - prob_ptr[:-1]).max().item()) if B else 1
-    if max_cand is None:
-        max_cand = int((cand_ptr[prob_ptr[1:].long()] - cand_ptr[prob_ptr[:-1].long()]).max().item()) if B else 1
-    max_slots, max_cand = max(int(max_slots), 1), max(int(max_cand), 1)
-    out = {"best_fitness": torch.empty(B, dtype=F64, device=dev), "start_fitness": torch.empty(B, dtype=F64, device=dev),
-           "best_pos": torch.zeros(B, max_slots, dtype=I32, device=dev), "best_rows": torch.zeros(B, max_slots, 4, dtype=F64, device=dev),
-           "history": torch.empty(B, max(int(max_sweeps), 1), dtype=F64, device=dev), "sweeps": torch.empty(B, dtype=I32, device=dev),
-           "moves": torch.empty(B, dtype=I32, device=dev)}
+    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
+    out = _descent_fields(B, max_slots, max(int(max_sweeps), 1), dev, rows=torch.zeros)
     check(_lib.load().gnnpn_descend_ragged_f64(
         B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
         dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), int(bool(wide)),
@@ -1271,10 +1279,7 @@ def descend_select(res, actions_all, n_slots):
         raise GnnpnError(f"descend_select: {B} x {R} rows expected in every field of res and in n_slots")
     dev = fit.device
     max_slots, hist_ld = pos.shape[1], hist.shape[1]
-    out = {"best_fitness": torch.empty(B, dtype=F64, device=dev), "start_fitness": torch.empty(B, dtype=F64, device=dev),
-           "best_pos": torch.empty(B, max_slots, dtype=I32, device=dev), "best_rows": torch.empty(B, max_slots, 4, dtype=F64, device=dev),
-           "history": torch.empty(B, hist_ld, dtype=F64, device=dev), "sweeps": torch.empty(B, dtype=I32, device=dev),
-           "moves": torch.empty(B, dtype=I32, device=dev), "start_index": torch.empty(B, dtype=I32, device=dev),
+    out = {**_descent_fields(B, max_slots, hist_ld, dev), "start_index": torch.empty(B, dtype=I32, device=dev),
            "actions": torch.empty(B, aT, 8, dtype=actions_all.dtype, device=dev), "n_slots": torch.empty(B, dtype=I32, device=dev)}
     adt = actions_all.dtype
     check(_lib.load().gnnpn_descend_select_f64(

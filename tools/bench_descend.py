@@ -10,7 +10,9 @@ ES-WOA alone (gnnpn_eswoa_ragged_f64 from the tables' start) and descent + ES-WO
 for the start, descent, ES-WOA and descent + ES-WOA, the mean best_fitness with descent's mean sweeps and moves.  Prints one
 JSON line.
 
-    python tools/bench_descend.py [--problems 1000] [--configs qws,normal] [--repeat 3] [--sweeps 16]
+    python tools/bench_descend.py [--problems 1000] [--configs qws,normal] [--repeat 3] [--sweeps 16] [--wide]
+
+``--wide``: the workgroup form of both searches (``wide=True`` to ops.descend_ragged and ops.eswoa_ragged).
 """
 import argparse
 import json
@@ -27,7 +29,7 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
 from bench_refine import CONFIGS, _seed_rows          # noqa: E402  (the same configurations, the same generators)
 
 
-def run_config(cfg, n_test, repeat, sweeps, dev):
+def run_config(cfg, n_test, repeat, sweeps, dev, wide=None):
     import torch
     import gnnpn_sc_amd.synth as synth
     from gnnpn_sc_amd import ops
@@ -48,11 +50,11 @@ def run_config(cfg, n_test, repeat, sweeps, dev):
 
     def descend(tabs):
         return ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], sweeps,
-                                  max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+                                  max_slots=tabs["max_slots"], max_cand=tabs["max_cand"], wide=wide)
 
     def eswoa(tabs, start_pos):
         return ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"], tabs["bounds"], start_pos,
-                                cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+                                cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"], wide=wide)
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -101,12 +103,13 @@ def main():
     ap.add_argument("--configs", default="qws,normal")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--sweeps", type=int, default=16)
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
     import torch
     dev = torch.device("cuda:0")
     out = {"metric": "descend", "configs": {}}
     for name in args.configs.split(","):
-        out["configs"][name] = run_config(CONFIGS[name], args.problems, args.repeat, args.sweeps, dev)
+        out["configs"][name] = run_config(CONFIGS[name], args.problems, args.repeat, args.sweeps, dev, wide=args.wide or None)
     print(json.dumps(out))
 
 
