@@ -102,6 +102,7 @@ extern "C" int gnnpn_lstm_encode_f32(int n_nets, const gnnpn_encode_net_t* in, i
         GNNPN_REQUIRE(e.pregates || (e.inputs && e.w_in && e.b_in),
                       "lstm_encode: net %d needs pregates or (inputs, w_in, b_in)", n);
         GNNPN_REQUIRE(gnnpn_aligned(e.whh_packed, 16), "lstm_encode: packed weights must be 16-byte aligned");
+        GNNPN_REQUIRE(gnnpn_aligned(e.enc_out, 16), "lstm_encode: enc_out must be 16-byte aligned (the cooperative form stores it 16 bytes at a time; the decoders require it too)");
         any_fold |= (e.pregates == nullptr);
         nets.pregates[n] = e.pregates;
         nets.inputs[n] = e.inputs;

@@ -1,15 +1,18 @@
 // Candidate reduction (per problem x category top-K of the feasible services) and the full
 // per-row ranking.  Integer/compare work, HBM-bound on the score rows: one wavefront per
 // (problem, category) segment, each lane scanning a strided share of the segment; the K picks are
-// K wave-wide max-reductions over 64-bit keys (score order bits : inverted id), so ties resolve to
+// K wave-wide max-reductions over 64-bit keys (order bits of the score, its zero canonicalised : inverted id), so equal scores —
+// -0.0 and +0.0 are equal, as for the stable descending sort of the oracle — resolve to
 // the lowest service id and the result does not depend on lane count or launch geometry.  The two full-ranking kernels share one
 // bitonic network (bitonic_sort_desc): on 64-bit keys, or on ids that form their keys from the score row.
 #include <vector>
 
 #include "common.h"
 
+// float_order_key puts -0 below +0; a ranking must not: score + (+0), rounded to nearest, is +0 for either zero and the score itself
+// for every other value (denormals are kept; a NaN stays a NaN and still sorts above +inf).
 __device__ __forceinline__ unsigned long long rank_key(float score, uint32_t id) {
-    return ((unsigned long long)float_order_key(score) << 32) | (0xffffffffu - id);
+    return ((unsigned long long)float_order_key(__fadd_rn(score, 0.0f)) << 32) | (0xffffffffu - id);
 }
 
 __global__ __launch_bounds__(256) void select_candidates_kernel(

@@ -226,8 +226,9 @@ int gnnpn_request_branch_f32(const float* x, int32_t nfeat, const float* table, 
 /* ---------------------------------------------------------------------------------------------
  * Candidate reduction: for every (problem b, category c) choose the n_per best-scored services
  * of that category that satisfy the problem's local bounds, best first (score descending, ties
- * by lowest service id), pad cyclically when fewer than n_per are feasible, and emit the
- * pointer-net input rows.
+ * by lowest service id; -0.0 and +0.0 are equal scores), pad cyclically when fewer than n_per are
+ * feasible, and emit the pointer-net input rows.  ld_scores: row stride of scores, >= the number of services
+ * (it also picks the launch shape: speed only, same rows); out_rows 16-byte aligned (GNNPN_E_ARG otherwise).
  *   scores        [B, S] fp32 (sigmoid scores of Net.forward)
  *   cat_ptr       [T+1]  services of category c are ids [cat_ptr[c], cat_ptr[c+1])
  *   qos           [S, 4] fp64 (q0,q1,q2=cost,q3=quality) — fp64 because the reference compares
@@ -245,7 +246,8 @@ int gnnpn_select_candidates(const float* scores, int64_t ld_scores, const int32_
                             const uint8_t* present, const double* global_bounds, float* out_rows,
                             int32_t* out_ids, int32_t B, int32_t T, int32_t n_per, void* stream);
 
-/* Full descending ranking of every score row (ties: lowest id first): ranking [B,S] int32.
+/* Full descending ranking of every score row (ties: lowest id first; -0.0 and +0.0 tie, as in a stable descending sort):
+ * ranking [B,S] int32, contiguous; ld_scores >= S is the row stride of scores.
  * S <= 32768 (one LDS bitonic sort per row: 64-bit keys up to 16384, service ids with keys formed on the fly above).
  * Replaces `_x.sort(dim=0, descending=True)` of src/models/trainML.py:62 (whose tie
  * order is undefined). */
@@ -270,7 +272,7 @@ int gnnpn_precision_at_k(const int32_t* ranking, int64_t ld_rank, const float* l
  *     projection into one [4H, 8] matrix — an exact algebraic identity, rounded differently
  *     (DESIGN.md section 6 item 7); only the cooperative form evaluates it in-kernel.
  *   whh_packed [H/4][gate][j][4] fp32  = W_hh[gate*H + j][k..k+3]   (ops.pack_lstm_weight)
- *   bhh [4H];   outputs enc_out [B, L, H], h_n / c_n [B, H]
+ *   bhh [4H];   outputs enc_out [B, L, H] (16-byte aligned, like whh_packed: GNNPN_E_ARG otherwise), h_n / c_n [B, H]
  * H must be 256 or 32 (environment.ini:55 and the unit fixtures).  `nets` is a HOST array.
  * Two implementations with bit-identical results: cooperative (H = 256 and a workspace given:
  * groups of 8 workgroups keep W_hh in registers and exchange h every step) and streaming.
