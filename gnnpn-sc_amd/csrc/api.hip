@@ -53,6 +53,28 @@ unsigned* gnnpn_cu_seat_table() {
     return table[dev];
 }
 
+// ---- failure record of the cooperative kernels (layout and writer: coop_common.h, coop_failure_record) ----
+__device__ unsigned g_dec_diag[COOP_REC_WORDS * (COOP_REC_ENTRIES + 1)];
+static_assert(sizeof(g_dec_diag) == 512 * 4, "gnnpn_decode_diag documents 512 words");
+// its device address: every cooperative launcher passes it to its kernel (nullptr: no record is kept)
+unsigned* gnnpn_decode_diag_buffer() {
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_dec_diag)) != hipSuccess) return nullptr;
+    return static_cast<unsigned*>(p);
+}
+
+extern "C" int gnnpn_decode_diag(uint32_t* out, int32_t n_words, int32_t clear) {
+    if (!out || n_words < 0 || n_words > 512) GNNPN_FAIL(GNNPN_E_ARG, "decode_diag: up to 512 words");
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec_diag), (size_t)n_words * 4) != hipSuccess)
+        GNNPN_FAIL(GNNPN_E_LAUNCH, "decode_diag: copy failed");
+    if (clear) {
+        static const unsigned zeros[512] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_dec_diag), zeros, sizeof(zeros)) != hipSuccess)
+            GNNPN_FAIL(GNNPN_E_LAUNCH, "decode_diag: clear failed");
+    }
+    return GNNPN_OK;
+}
+
 // after a launch that ended in a hand-off time-out without ever being staffed: it never left the count of launches that
 // are staffing (coop_common.h::coop_place), which would make every later launch decline badly placed seats for good
 extern "C" int gnnpn_coop_reset_staffing(void) {
@@ -73,8 +95,8 @@ extern "C" int gnnpn_coop_staffing_count(void) {
 
 extern "C" int gnnpn_set_option(const char* name, int value) {
     if (!name) GNNPN_FAIL(GNNPN_E_ARG, "set_option: null name");
-    if (!strcmp(name, "lstm_ablate")) {   // bit0 no MFMA, bit1 no transcendentals, bit2 no tag wait, bit3 no sweep, bit4 no publish, bit5 stamps
-        GNNPN_REQUIRE(value >= 0 && (value & 128) == 0, "set_option: lstm_ablate bit 7 is gnnpn_launch_opts_t.write_through now");
+    if (!strcmp(name, "lstm_ablate")) {   // a bit field of GNNPN_ABLATE_* (include/gnnpn_hip.h)
+        GNNPN_REQUIRE(value >= 0 && (value & GNNPN_ABLATE_REFUSED) == 0, "set_option: lstm_ablate bit 7 is gnnpn_launch_opts_t.write_through now");
         g_lstm_ablate = value;
         return GNNPN_OK;
     }

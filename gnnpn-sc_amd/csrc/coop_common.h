@@ -7,6 +7,19 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
+// ---- the flag word every cooperative kernel receives: the two booleans of gnnpn_launch_opts_t that reach the device.  They sit
+// in two bits no GNNPN_ABLATE_* name uses, so the encoder's diagnostic switches ride the same argument.
+enum : int {
+    COOP_FLAG_WRITE_THROUGH = 1 << 7,    // hand-off granules are written through to the device's coherence point (agent scope)
+    COOP_FLAG_PAIRED_START = 1 << 12,    // a partner launch starts together with this one: strict placement (coop_place)
+};
+static_assert(COOP_FLAG_WRITE_THROUGH == GNNPN_ABLATE_REFUSED && !((GNNPN_ABLATE_ENCODER | GNNPN_ABLATE_DEC_STAMPS | GNNPN_ABLATE_KEEP_WORKSPACE) &
+                                                                   (COOP_FLAG_WRITE_THROUGH | COOP_FLAG_PAIRED_START)),
+              "the launch flags share a word with the diagnostic bits");
+inline int coop_flags(const CoopOpts& o) { return (o.write_through ? COOP_FLAG_WRITE_THROUGH : 0) | (o.paired_start ? COOP_FLAG_PAIRED_START : 0); }
+__device__ __forceinline__ bool coop_write_through(int flags) { return (flags & COOP_FLAG_WRITE_THROUGH) != 0; }
+__device__ __forceinline__ bool coop_paired_start(int flags) { return (flags & COOP_FLAG_PAIRED_START) != 0; }
+
 // ---- granule hand-off (CDNA4 guide, Guideline 16 / R2): 8-byte {tag, value}, ONE sc1 store / load
 __device__ __forceinline__ void granule_store(u64* p, unsigned tag, float v) {
     __hip_atomic_store(p, ((u64)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
@@ -132,6 +145,48 @@ __device__ __forceinline__ unsigned xcc_id() {
     return __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xfu;   // hwreg(HW_REG_XCC_ID, 0, 4)
 }
 
+// ---- failure record (diagnosis of a timed-out sweep; written on the failure path only, read by gnnpn_decode_diag, api.hip) ----
+// Word 0 of the buffer: failures so far (all launches); then COOP_REC_WORDS words per failing wave, the first 31 of them.
+// ops.FAILURE_RECORD_WORDS mirrors the names (tests/test_host_logic.py compares them).
+enum CoopRecordWord {
+    COOP_REC_GROUP, COOP_REC_MEMBER, COOP_REC_TILE,
+    COOP_REC_K,                   // step within the tile
+    COOP_REC_WAVE,
+    COOP_REC_TAG,                 // the tag the sweep waited for
+    COOP_REC_H_MISSING_MEMBERS,   // mask of members whose h granules are missing
+    COOP_REC_P_MISSING_MEMBERS,   // mask of members whose partial dots are missing — or COOP_REC_ENCODER_MARK
+    COOP_REC_LATENT_MISSING,      // lanes whose latent logit is missing
+    COOP_REC_CLAIMS_XCD0_3, COOP_REC_CLAIMS_XCD4_7,   // seats taken per XCD, one byte each
+    COOP_REC_T_LO, COOP_REC_T_HI,                     // real-time clock — encoder entries: ARRIVALS per XCD, one byte each
+    COOP_REC_GPX, COOP_REC_WORKGROUP, COOP_REC_LAUNCH_STATUS,
+    COOP_REC_WORDS
+};
+constexpr unsigned COOP_REC_ENCODER_MARK = 0xE0C;   // in COOP_REC_P_MISSING_MEMBERS: an encoder's entry
+constexpr int COOP_REC_ENTRIES = 31;
+// One lane of the failing wave.  A writer passes what it knows and zero for the rest; `encoder` marks the entry and puts the
+// per-XCD arrival counters where the decoders put the clock.
+__device__ __forceinline__ void coop_failure_record(unsigned* diag, const unsigned* status, int gpx, int group, int member, int tile,
+                                                    int k, int wave, unsigned tag, unsigned h_miss, unsigned p_miss, unsigned l_miss,
+                                                    bool encoder = false) {
+    if (!diag) return;
+    const unsigned n = atomicAdd(diag, 1u);
+    if (n >= COOP_REC_ENTRIES) return;
+    unsigned* rec = diag + COOP_REC_WORDS * (n + 1);
+    auto bytes = [status](int offset, int first) {   // four per-XCD counters, one byte each
+        unsigned v = 0;
+        for (int x = 0; x < 4; ++x) v |= (status[offset / 4 + COOP_XCD_STRIDE * (first + x)] & 0xffu) << (8 * x);
+        return v;
+    };
+    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+    rec[COOP_REC_GROUP] = group; rec[COOP_REC_MEMBER] = member; rec[COOP_REC_TILE] = tile; rec[COOP_REC_K] = k;
+    rec[COOP_REC_WAVE] = wave; rec[COOP_REC_TAG] = tag; rec[COOP_REC_H_MISSING_MEMBERS] = h_miss;
+    rec[COOP_REC_P_MISSING_MEMBERS] = encoder ? COOP_REC_ENCODER_MARK : p_miss; rec[COOP_REC_LATENT_MISSING] = l_miss;
+    rec[COOP_REC_CLAIMS_XCD0_3] = bytes(COOP_XCDCNT_OFFSET, 0); rec[COOP_REC_CLAIMS_XCD4_7] = bytes(COOP_XCDCNT_OFFSET, 4);
+    rec[COOP_REC_T_LO] = encoder ? bytes(COOP_ARRIVE_OFFSET, 0) : (unsigned)t;
+    rec[COOP_REC_T_HI] = encoder ? bytes(COOP_ARRIVE_OFFSET, 4) : (unsigned)(t >> 32);
+    rec[COOP_REC_GPX] = gpx; rec[COOP_REC_WORKGROUP] = blockIdx.x; rec[COOP_REC_LAUNCH_STATUS] = status[0];
+}
+
 // The L2-resident publish, WRITTEN as the instruction it is (round 6): one global_store_dwordx2 without cache-policy bits — the
 // granule goes to the XCD's L2, the point the group's peers read at with sc1 loads (a group sits on one XCD by placement).  Rounds
 // 1-5 asked for it as a workgroup-scope relaxed atomic store and relied on this toolchain lowering that to exactly this instruction
@@ -167,7 +222,7 @@ namespace {   // one copy per translation unit
 __global__ __launch_bounds__(256) void coop_zero_kernel(unsigned long long* __restrict__ p, size_t n8, unsigned* __restrict__ sticky,
                                                         int word, unsigned expected, int skip_zeroing) {
     if (sticky && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(sticky + word, expected);
-    if (skip_zeroing) return;                              // test hook (lstm_ablate bit 13): the workspace stays as the test prepared it
+    if (skip_zeroing) return;                              // test hook (GNNPN_ABLATE_KEEP_WORKSPACE): the workspace stays as the test prepared it
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x)
         __hip_atomic_store(p + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -193,6 +248,7 @@ struct CoopLaunch {
     unsigned* status;   // the launch's status area: the first COOP_STATUS_BYTES of the workspace
     char* buffers;      // the exchange buffers behind it
     unsigned* seats;    // the device's canonical seat table (api.hip)
+    unsigned* diag;     // the failure record (api.hip; written on a timed-out sweep only), or nullptr
 };
 
 // What every launcher does before its kernel, in this order: the device query; groups per XCD, the refusal of a partitioned
@@ -223,11 +279,13 @@ inline int coop_begin(const char* who, int n_nets, int32_t rows, Need need, int 
     if (!workspace || workspace_bytes < bytes || !gnnpn_aligned(workspace, 256))
         GNNPN_FAIL(GNNPN_E_ARG, "%s: workspace of %lld B (256-B aligned) required", who, (long long)bytes);
     L.seats = gnnpn_cu_seat_table();
+    static unsigned* const diag = gnnpn_decode_diag_buffer();
+    L.diag = diag;
     if (!L.seats) GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: cannot allocate the seat table", who);
-    // zero the status area and every tag before each launch (tags start at 1).  Test hook (lstm_ablate bit 13, tests only): leave
+    // zero the status area and every tag before each launch (tags start at 1).  Test hook (GNNPN_ABLATE_KEEP_WORKSPACE, tests only): leave
     // the workspace as the previous launch left it — every workgroup must then notice (status code 8) instead of running on it
     const unsigned units = (unsigned)(COOP_G * n_nets * L.n_tiles);
-    if (coop_zero_workspace(workspace, (size_t)bytes, s, opts.sticky, expected_word, units, (gnnpn_option_lstm_ablate() & 0x2000) != 0) !=
+    if (coop_zero_workspace(workspace, (size_t)bytes, s, opts.sticky, expected_word, units, (gnnpn_option_lstm_ablate() & GNNPN_ABLATE_KEEP_WORKSPACE) != 0) !=
         hipSuccess)
         GNNPN_FAIL(GNNPN_E_LAUNCH, "%s: workspace memset failed", who);
     g_gnnpn_last_units = opts.sticky ? (int64_t)units : 0;
@@ -242,6 +300,10 @@ inline int coop_begin(const char* who, int n_nets, int32_t rows, Need need, int 
 struct DecodeWorkspace {
     int64_t h_bytes, p_bytes, l_bytes;
     int64_t total() const { return COOP_STATUS_BYTES + h_bytes + p_bytes + l_bytes + COOP_OVERREAD_BYTES; }
+    // the three exchange buffers inside CoopLaunch::buffers, in this order
+    u64* h(char* buffers) const { return reinterpret_cast<u64*>(buffers); }
+    u64* p(char* buffers) const { return reinterpret_cast<u64*>(buffers + h_bytes); }
+    u64* l(char* buffers) const { return reinterpret_cast<u64*>(buffers + h_bytes + p_bytes); }
 };
 inline DecodeWorkspace decode_workspace(int64_t groups, int64_t rows, int32_t T, int32_t K, int64_t xp_granules) {
     const int64_t tiles = (rows + COOP_ROWS - 1) / COOP_ROWS;
@@ -461,10 +523,54 @@ __device__ __forceinline__ bool coop_place(unsigned* status, int gpx, int* slot,
     return group >= 0;
 }
 
+// ---- one way in, one way out: what every cooperative kernel does before its first and after its last tile ----
+// The way in: take a seat (coop_place), find the seat's net and the group's index among the net's groups, clear the workgroup's
+// abort flag, and count the workgroup into COOP_PLACED_OFFSET if it hands off inside its XCD.  false: a surplus workgroup of
+// the over-subscribed launch or a spare group that takes part in no exchange — the kernel returns at once.  `place`: two ints
+// of LDS, `abort_flag`: the workgroup's flag in LDS.  Called by every thread.  (The seat comes back through the reference and
+// the verdict as the return value: returned whole by value, the three outcomes were merged into one exit and the exact-split
+// lean decoder's register allocation moved.)
+struct CoopSeat {
+    bool same_xcd;
+    int group, member, net, index_in_net;
+};
+template <int G>
+__device__ __forceinline__ bool coop_enter(unsigned* status, unsigned* sticky, unsigned* seats, int gpx, int flags, int n_nets,
+                                           int groups_per_net, int* place, int* abort_flag, CoopSeat& s) {
+    if (!coop_place<G>(status, gpx, place, s.group, s.member, seats, coop_paired_start(flags), sticky)) return false;
+    s.net = s.group / groups_per_net;
+    s.index_in_net = s.group % groups_per_net;
+    if (s.net >= n_nets) return false;
+    if (threadIdx.x == 0) *abort_flag = 0;
+    __syncthreads();
+    s.same_xcd = !coop_write_through(flags);
+    if (threadIdx.x == 0 && s.same_xcd) atomicAdd(status + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics (per XCD: its own line)
+    return true;
+}
+// The way out, by every thread of a seated workgroup: an abort is raised as `code`, the finished tiles are booked (proof of work)
+__device__ __forceinline__ void coop_leave(unsigned* status, unsigned* sticky, unsigned* seats, bool aborted, unsigned code,
+                                           int finished_word, unsigned tiles_done) {
+    if (threadIdx.x != 0) return;
+    if (aborted) coop_raise(status, sticky, code, seats);
+    coop_note_finished(sticky, finished_word, tiles_done);
+}
+
 // value of lane (l ^ 8) within each row of 16 lanes, as a DPP row rotate (no LDS round trip)
 __device__ __forceinline__ float swap8(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128 /* row_ror:8 */, 0xF, 0xF, false));
 }
+
+// value of lane (l + n) % 16 within each row of 16 lanes, n = 1, 2, 4 or 8: the max / sum over a row in four rotations, every lane
+// ending with the row's result (a rotation has a source for every lane: bound_ctrl only spares the compiler an `old = 0` move per use)
+__device__ __forceinline__ int dpp_ror16(int v, int n) {
+    switch (n) {
+        case 1: return __builtin_amdgcn_update_dpp(0, v, 0x121, 0xF, 0xF, true);
+        case 2: return __builtin_amdgcn_update_dpp(0, v, 0x122, 0xF, 0xF, true);
+        case 4: return __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, true);
+        default: return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true);
+    }
+}
+__device__ __forceinline__ float dpp_ror16(float v, int n) { return __int_as_float(dpp_ror16(__float_as_int(v), n)); }
 
 // Diagnostic stamps (diagnostic option only; never in a measured run)
 __device__ __forceinline__ u64 phase_stamp() {
@@ -483,6 +589,19 @@ __device__ __forceinline__ u64 phase_stamp() {
 // apart) are 2-way on 32 banks, which costs a ds_write_b32 nothing.
 constexpr int LDT = 260;
 __device__ __forceinline__ int ht_index(int row, int unit) { return row * LDT + (unit & 3) * 64 + (unit >> 2); }
+
+// fp32 B-fragments of one gate column (gate, unit u) for lane quarter kq, from the packed layout W[g*HD+u][4kk+kq] = Wp[((kk*4+g)*HD+u)*4+kq]
+template <int HD>
+__device__ __forceinline__ void load_whh_fragments(const float* Wp, int gate, int u, int kq, float (&w)[64]) {
+#pragma unroll
+    for (int kk = 0; kk < 64; ++kk) w[kk] = Wp[((size_t)(kk * 4 + gate) * HD + u) * 4 + kq];
+}
+// B-fragments of a folded input projection [4H, 8] for gate row `wrow` (k = 4 kk2 + kq, kk2 = 0, 1), and the row's bias
+__device__ __forceinline__ void load_folded_input(const float* w_fold, const float* b_fold, int wrow, int kq, float (&wx)[2], float& bias) {
+    wx[0] = w_fold[wrow * 8 + kq];
+    wx[1] = w_fold[wrow * 8 + 4 + kq];
+    bias = b_fold[wrow];
+}
 
 // Two k-ordered fp32 MFMA chains (one per 16-column tile) over K = 256 against A-fragments read from
 // an LDS tile `src`: row-major (row c, stride LD, element 4*kk + kq) or, KQ, the k-quarter-major h tile above.
@@ -765,6 +884,16 @@ __device__ __forceinline__ void split_chain(const _Float16* base, const f16x8 (&
 // value: a lane sends the gate pair of the rows its PARTNER finishes and receives the partner's gates of its own rows.  Same
 // arithmetic as lstm_cell_update (recurrent.h): cy = f*c + i*g ; hy = o*tanh(cy), products and sum rounded separately
 // (-ffp-contract=off).
+// gates_before_cell: the gate pre-activations it takes, from the two tiles' recurrent products `ah0` / `ah1`, the recurrent biases
+// `bh` and the input side `gx` (bias included): gates = (h.W_hh^T + b_hh) + (x.W_ih^T + b_ih), added in that order.
+__device__ __forceinline__ void gates_before_cell(const f32x4& ah0, const f32x4& ah1, const float (&bh)[2], const float (&gx)[2][4],
+                                                  f32x2 (&g0)[2], f32x2 (&g1)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        g0[q] = (f32x2{ah0[2 * q], ah0[2 * q + 1]} + pk_set(bh[0])) + f32x2{gx[0][2 * q], gx[0][2 * q + 1]};
+        g1[q] = (f32x2{ah1[2 * q], ah1[2 * q + 1]} + pk_set(bh[1])) + f32x2{gx[1][2 * q], gx[1][2 * q + 1]};
+    }
+}
 __device__ __forceinline__ void cell_update_split(const f32x2 (&g0)[2], const f32x2 (&g1)[2], bool lo_half, f32x2& cst, f32x2& h) {
     f32x2 a0[2], a1[2];
 #pragma unroll

@@ -39,51 +39,17 @@ constexpr int KMAX = 16;          // candidates per category the cooperative for
 constexpr unsigned SPIN_LIMIT = 400000;
 }  // namespace
 
-// ---- failure record (diagnosis of a timed-out sweep; written only on the failure path, read by gnnpn_decode_diag) ----
-// [0] failures so far (all launches) | per failing wave, first 31 of them, 16 words: group, member, tile, k, wave, tag,
-// mask of members whose h granules are missing, mask of members whose partial dots are missing, missing latent lanes,
-// the 8 per-XCD claim counters of the launch packed as bytes (2 words), realtime lo/hi, gpx, blockIdx.x
-__device__ unsigned g_dec_diag[512];
-__device__ __forceinline__ void decode_diag_record(int group, int member, int tile, const unsigned* err, int gpx) {
-    const unsigned n = atomicAdd(g_dec_diag, 1u);
-    if (n < 31) {
-        unsigned* r = g_dec_diag + 16 * (n + 1);
-        const unsigned* cnt = err + COOP_XCDCNT_OFFSET / 4;
-        unsigned c0 = 0, c1 = 0;
-        for (int x = 0; x < 4; ++x) {
-            c0 |= (cnt[COOP_XCD_STRIDE * x] & 0xffu) << (8 * x);
-            c1 |= (cnt[COOP_XCD_STRIDE * (4 + x)] & 0xffu) << (8 * x);
-        }
-        const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-        r[0] = group; r[1] = member; r[2] = tile; r[9] = c0; r[10] = c1; r[11] = (unsigned)t; r[12] = (unsigned)(t >> 32);
-        r[13] = gpx; r[14] = blockIdx.x; r[15] = err[0];
-    }
-}
-
-// max / sum over each row of 16 lanes by DPP rotations (every lane ends with the row's result)
-__device__ __forceinline__ int ror16(int v, int n) {
-    switch (n) {
-        // (a rotation has a source for every lane: bound_ctrl only spares the compiler an `old = 0` move per use)
-        case 1: return __builtin_amdgcn_update_dpp(0, v, 0x121, 0xF, 0xF, true);
-        case 2: return __builtin_amdgcn_update_dpp(0, v, 0x122, 0xF, 0xF, true);
-        case 4: return __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, true);
-        default: return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true);
-    }
-}
-
 // The fp32 arithmetic, one workgroup per CU (512 registers); the exact-split product and the 2-per-CU builds are those of
 // decode_lean.hip.
 // FOLDX: the folded input side (net.xw_fold); otherwise the literal two-stage one (embedding2, then W_ih).
 // SAMPLE: the build that can draw the pick from the window softmax (gnnpn_decode_net_t.sample); the greedy build carries
 // none of that code.  Only this build reads `rep` (sampled replicas, decode_shared.h: row -> problem indirection)
-// write_through: 128 — the hand-off granules are written through to the device's coherence point instead of staying in the
-// group's L2 (gnnpn_launch_opts_t.write_through).
 template <bool FOLDX, bool SAMPLE>
 __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs a, u64* __restrict__ xh,
                                                                    u64* __restrict__ xp, u64* __restrict__ xl,
                                                                    unsigned* __restrict__ err, unsigned* __restrict__ sticky,
-                                                                   int n_nets, int groups_per_net, int gpx, int write_through, unsigned* __restrict__ seats,
-                                                                   ReplicaMap rep) {
+                                                                   int n_nets, int groups_per_net, int gpx, int flags, unsigned* __restrict__ seats,
+                                                                   unsigned* __restrict__ diag, ReplicaMap rep) {
     __shared__ __attribute__((aligned(16))) float hs[ROWS * LDH16];   // fp32 tile, k-quarter-major with stride LDT (ROWS * LDT floats used)
     __shared__ float xs[FOLDX ? 1 : ROWS * LDH];
     __shared__ __attribute__((aligned(16))) float hsl[ROWS][UNITS + 4];
@@ -96,15 +62,11 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kq = lane >> 4, c = lane & 15;
     __shared__ int place[2];
-    int group, member;
-    if (!coop_place<G>(err, gpx, place, group, member, seats, false, sticky)) return;   // surplus workgroup of the over-subscribed launch (coop_common.h)
-    const int net_id = group / groups_per_net, gi = group % groups_per_net;
-    if (net_id >= n_nets) return;
+    CoopSeat seat;
+    if (!coop_enter<G>(err, sticky, seats, gpx, flags, n_nets, groups_per_net, place, &abort_flag, seat)) return;
+    const int group = seat.group, member = seat.member, net_id = seat.net, gi = seat.index_in_net;
+    const bool same_xcd = seat.same_xcd;   // h and partial-dot granules stay inside the group's XCD
     const DecodeNet& net = a.net[net_id];
-    if (tid == 0) abort_flag = 0;
-    __syncthreads();
-    const bool same_xcd = !(write_through & 128);   // h and partial-dot granules stay inside the group's XCD
-    if (tid == 0 && same_xcd) atomicAdd(err + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics: workgroups on the same-XCD fast path (per XCD: its own line)
 
     const int B = a.B, T = a.T, K = a.K, L = T * K;
     // row -> problem whose inputs the row reads: b / R for sampled replicas, the identity everywhere else (constant-folded
@@ -128,19 +90,14 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
     for (int tl = 0; tl < 2; ++tl) {
         const int gate = wrow[tl] / H, u = wrow[tl] % H;
         bh[tl] = net.bhh[wrow[tl]];
-#pragma unroll
-        for (int kk = 0; kk < 64; ++kk) wBh[tl][kk] = net.whh[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
-        if constexpr (FOLDX) {   // B-fragments of (W_ih W_e) [4H,8], its bias, and the step-0 gates W_ih.start + b_ih
-            wXf[tl][0] = net.xw_fold[wrow[tl] * 8 + kq];
-            wXf[tl][1] = net.xw_fold[wrow[tl] * 8 + 4 + kq];
-            bi[tl] = net.xb_fold[wrow[tl]];
+        load_whh_fragments<H>(net.whh, gate, u, kq, wBh[tl]);
+        if constexpr (FOLDX) {   // (W_ih W_e) [4H,8], its bias, and the step-0 gates W_ih.start + b_ih
+            load_folded_input(net.xw_fold, net.xb_fold, wrow[tl], kq, wXf[tl], bi[tl]);
             sg[tl] = net.start_fold[wrow[tl]];
         } else {
             bi[tl] = net.bih[wrow[tl]];
             wXf[tl][0] = wXf[tl][1] = sg[tl] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < 64; ++kk)
-                wBx[tl][kk] = net.wih[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
+            load_whh_fragments<H>(net.wih, gate, u, kq, wBx[tl]);
         }
     }
     // unfolded path, in-kernel embedding2 of the picked row (net.embedded == nullptr): column tid of emb_w
@@ -265,8 +222,8 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
                     unsigned long long key = ((unsigned long long)hi << 32) | (unsigned)(15 - r);
 #pragma unroll
                     for (int n = 1; n <= 8; n <<= 1) {
-                        const unsigned olo = (unsigned)ror16((int)(unsigned)key, n);
-                        const unsigned ohi = (unsigned)ror16((int)(unsigned)(key >> 32), n);
+                        const unsigned olo = (unsigned)dpp_ror16((int)(unsigned)key, n);
+                        const unsigned ohi = (unsigned)dpp_ror16((int)(unsigned)(key >> 32), n);
                         const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
                         key = o > key ? o : key;
                     }
@@ -278,7 +235,7 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
                     float e = live ? expf(__fsub_rn(v, best)) : 0.0f;
                     const float e_own = e;
 #pragma unroll
-                    for (int n = 8; n >= 1; n >>= 1) e = __fadd_rn(e, __int_as_float(ror16(__float_as_int(e), n)));
+                    for (int n = 8; n >= 1; n >>= 1) e = __fadd_rn(e, dpp_ror16(e, n));
                     int pick_r = best_r;
                     float pick_p = 1.0f / e;
                     if constexpr (SAMPLE) {
@@ -422,11 +379,7 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
             u64* out_h = xh_g + (step & 1) * (ROWS * H);
             {   // one cell update per lane for the two rows it finishes (coop_common.h: cell_update_split)
                 f32x2 g0[2], g1[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    g0[q] = (f32x2{ah0[2 * q], ah0[2 * q + 1]} + pk_set(bh[0])) + f32x2{gx[0][2 * q], gx[0][2 * q + 1]};
-                    g1[q] = (f32x2{ah1[2 * q], ah1[2 * q + 1]} + pk_set(bh[1])) + f32x2{gx[1][2 * q], gx[1][2 * q + 1]};
-                }
+                gates_before_cell(ah0, ah1, bh, gx, g0, g1);
                 cell_update_split(g0, g1, c < 8, cst, hl);
             }
             {
@@ -465,15 +418,12 @@ __global__ __launch_bounds__(256, 1) void pointer_decode_coop_kernel(DecodeArgs 
             ++step;
         }
         if (abort_flag) {
-            if (tid == 0) decode_diag_record(group, member, tile, err, gpx);
+            if (tid == 0) coop_failure_record(diag, err, gpx, group, member, tile, 0, 0, 0u, 0u, 0u, 0u);   // which step and whose granules: not kept by this sweep
             break;
         }
         ++tiles_done;
     }
-    if (tid == 0) {
-        if (abort_flag) coop_raise(err, sticky, 2u, seats);
-        coop_note_finished(sticky, GNNPN_STATUS_DEC_FINISHED, tiles_done);
-    }
+    coop_leave(err, sticky, seats, abort_flag, 2u, GNNPN_STATUS_DEC_FINISHED, tiles_done);
 }
 
 // this file's workspace (coop_common.h: decode_workspace): the partial dots of the K candidates of every row from every member
@@ -489,25 +439,6 @@ extern "C" int64_t gnnpn_pointer_decode_workspace_bytes(int32_t B, int32_t T, in
     const int64_t a8 = gnnpn_decode_coop_workspace_need(B, T, n_per);
     const int64_t lean = gnnpn_decode_lean_workspace_bytes(B, T, n_per);
     return a8 > lean ? a8 : lean;
-}
-
-// device address of the failure record, for the kernels of other translation units (decode_lean.hip)
-unsigned* gnnpn_decode_diag_buffer() {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_dec_diag)) != hipSuccess) return nullptr;
-    return static_cast<unsigned*>(p);
-}
-
-extern "C" int gnnpn_decode_diag(uint32_t* out, int32_t n_words, int32_t clear) {
-    if (!out || n_words < 0 || n_words > 512) GNNPN_FAIL(GNNPN_E_ARG, "decode_diag: up to 512 words");
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec_diag), (size_t)n_words * 4) != hipSuccess)
-        GNNPN_FAIL(GNNPN_E_LAUNCH, "decode_diag: copy failed");
-    if (clear) {
-        static const unsigned zeros[512] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_dec_diag), zeros, sizeof(zeros)) != hipSuccess)
-            GNNPN_FAIL(GNNPN_E_LAUNCH, "decode_diag: clear failed");
-    }
-    return GNNPN_OK;
 }
 
 bool gnnpn_decode_coop_supported(int32_t H_, int32_t n_per) { return H_ == H && n_per <= KMAX; }
@@ -537,14 +468,11 @@ int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, 
     if (const int rc = coop_begin("pointer_decode", n_nets, args.B, need, GNNPN_STATUS_DEC_EXPECTED, opts, workspace, workspace_bytes, s, c))
         return rc;
     const DecodeWorkspace w = coop_workspace(c.groups, args.B, args.T, args.K);
-    u64* p_h = reinterpret_cast<u64*>(c.buffers);
-    u64* p_p = reinterpret_cast<u64*>(c.buffers + w.h_bytes);
-    u64* p_l = reinterpret_cast<u64*>(c.buffers + w.h_bytes + w.p_bytes);
-    const int wt = opts.write_through ? 128 : 0;
+    const int flags = coop_flags(opts) & ~COOP_FLAG_PAIRED_START;   // these builds have never placed strictly (opts.paired_start is not for them)
 #define GNNPN_DEC8(FOLD_, SAMPLE_)                                                                                                  \
     hipLaunchKernelGGL((pointer_decode_coop_kernel<FOLD_, SAMPLE_>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),                      \
-                       gnnpn_lds_padding((const void*)pointer_decode_coop_kernel<FOLD_, SAMPLE_>, opts.lds_kb), s, args, p_h, p_p, p_l, \
-                       c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, wt, c.seats, rep)
+                       gnnpn_lds_padding((const void*)pointer_decode_coop_kernel<FOLD_, SAMPLE_>, opts.lds_kb), s, args, w.h(c.buffers), w.p(c.buffers), w.l(c.buffers), \
+                       c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, flags, c.seats, c.diag, rep)
     if (any_sample) GNNPN_DEC8(true, true);       // folded input side, every pick drawn from the window softmax
     else GNNPN_DEC8(false, false);                // the literal two-stage input side (embedding2, then W_ih), greedy
 #undef GNNPN_DEC8

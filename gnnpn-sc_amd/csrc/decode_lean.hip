@@ -43,14 +43,6 @@ constexpr int AUX_SC1 = 16;       // cache-policy bit sc1: agent scope (a load r
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }
-__device__ __forceinline__ float dpp_ror(float v, int n) {
-    switch (n) {
-        case 1: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, true));
-        case 2: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xF, 0xF, true));
-        case 4: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, true));
-        default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));
-    }
-}
 __device__ __forceinline__ void store_granule(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, u64 g, bool same_xcd) {
     const u32x2 v = {(unsigned)g, (unsigned)(g >> 32)};
     // one 8-byte store per granule.  Same XCD: no sc bits — the store lands in the group's L2, the coherence point of an
@@ -58,33 +50,15 @@ __device__ __forceinline__ void store_granule(__amdgpu_buffer_rsrc_t r, unsigned
     if (same_xcd) __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
     else __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, AUX_SC1);
 }
-// failure record of a timed-out sweep (read by gnnpn_decode_diag; layout: decode_coop.hip) — failure path only
-__device__ __forceinline__ void record_failure(unsigned* diag, const unsigned* err, int group, int member, int tile, int k, int wave,
-                                               unsigned tag, unsigned h_miss, unsigned p_miss, unsigned l_miss, int gpx) {
-    if ((threadIdx.x & 63) != 0 || !diag) return;
-    const unsigned n = atomicAdd(diag, 1u);
-    if (n >= 31) return;
-    unsigned* rec = diag + 16 * (n + 1);
-    const unsigned* cnt = err + COOP_XCDCNT_OFFSET / 4;
-    unsigned c0 = 0, c1 = 0;
-    for (int x = 0; x < 4; ++x) {
-        c0 |= (cnt[COOP_XCD_STRIDE * x] & 0xffu) << (8 * x);
-        c1 |= (cnt[COOP_XCD_STRIDE * (4 + x)] & 0xffu) << (8 * x);
-    }
-    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-    rec[0] = group; rec[1] = member; rec[2] = tile; rec[3] = k; rec[4] = wave; rec[5] = tag;
-    rec[6] = h_miss; rec[7] = p_miss; rec[8] = l_miss; rec[9] = c0; rec[10] = c1;
-    rec[11] = (unsigned)t; rec[12] = (unsigned)(t >> 32); rec[13] = gpx; rec[14] = blockIdx.x; rec[15] = err[0];
-}
 }  // namespace
 
 // EVH: lanes per (row, candidate) in the partial dots: 2 (n_per <= 8: 16 floats of the slice each) or 1 (n_per <= 16)
-// DIAG: the diagnostic build with phase stamps (tools/stamp_decode.py; lstm_ablate bit 11) — timing only, never a measured run
+// DIAG: the diagnostic build with phase stamps (tools/stamp_decode.py; GNNPN_ABLATE_DEC_STAMPS) — timing only, never a measured run
 template <bool SPLIT, int OCC, int EVH, bool DIAG = false>
 __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArgs a, u64* xh, u64* xp,
                                                                      u64* xl, unsigned* __restrict__ err,
                                                                      unsigned* __restrict__ sticky, int n_nets, int groups_per_net,
-                                                                     int gpx, int write_through, unsigned* __restrict__ seats,
+                                                                     int gpx, int flags, unsigned* __restrict__ seats,
                                                                      unsigned* __restrict__ diag) {
     __shared__ __attribute__((aligned(16))) float hs[SPLIT ? 3 * SPLIT_TILE / 2 : ROWS * LDT];   // fp32 tile (k-quarter-major) | three fp16 piece tiles
     __shared__ __attribute__((aligned(16))) unsigned wts[SPLIT ? SPLIT_WT_DWORDS : 4];
@@ -96,19 +70,14 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = lane >> 4, c = lane & 15;
-    int group, member;
-    if (!coop_place<G>(err, gpx, place, group, member, seats, (write_through & 2) != 0, sticky)) return;   // surplus workgroup of the over-subscribed launch (bit 1: opts.paired_start)
-    // seat numbers come out of LDS, i.e. in vector registers: say that they are uniform — every base address, resource and
+    CoopSeat seat;
+    if (!coop_enter<G>(err, sticky, seats, gpx, flags, n_nets, groups_per_net, place, &abort_flag, seat)) return;
+    // the seat comes out of LDS, i.e. in vector registers: say that it is uniform — every base address, resource and
     // scalar offset below then lives in SGPRs (a resource the compiler cannot prove uniform costs a waterfall loop per access)
-    group = __builtin_amdgcn_readfirstlane(group);
-    member = __builtin_amdgcn_readfirstlane(member);
-    const int net_id = group / groups_per_net, gi = group % groups_per_net;
-    if (net_id >= n_nets) return;
+    const int group = __builtin_amdgcn_readfirstlane(seat.group), member = __builtin_amdgcn_readfirstlane(seat.member);
+    const int net_id = __builtin_amdgcn_readfirstlane(seat.net), gi = __builtin_amdgcn_readfirstlane(seat.index_in_net);
+    const bool same_xcd = seat.same_xcd;
     const DecodeNet& net = a.net[net_id];
-    if (tid == 0) abort_flag = 0;
-    __syncthreads();
-    const bool same_xcd = !(write_through & 1);
-    if (tid == 0 && same_xcd) atomicAdd(err + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics: workgroups on the same-XCD fast path (per XCD: its own line)
 
     const int B = a.B, T = a.T, K = a.K, L = T * K;
     const bool latent_in_launch = net.latent_from >= 0;
@@ -119,7 +88,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
 
     // ---- weights of this lane's two gate columns: tile 0 = [i | f], tile 1 = [g | o], 8 units per wave
     const int unit = member * UNITS + wave * 8 + (c & 7);
-    const int wrow0 = (0 + (c >> 3)) * H + unit, wrow1 = (2 + (c >> 3)) * H + unit;
+    const int wrow[2] = {(0 + (c >> 3)) * H + unit, (2 + (c >> 3)) * H + unit};
     float wBh[SPLIT ? 1 : 2][SPLIT ? 1 : 64];
     f16x8 wH16[SPLIT ? 2 : 1][8], wL16[SPLIT ? 2 : 1][8];
     float winv[2] = {1.0f, 1.0f};
@@ -131,18 +100,15 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
     }
 #pragma unroll
     for (int tl = 0; tl < 2; ++tl) {
-        const int wrow = tl ? wrow1 : wrow0, gate = wrow / H, u = wrow % H;
-        bh[tl] = net.bhh[wrow];
+        const int gate = wrow[tl] / H, u = wrow[tl] % H;
+        bh[tl] = net.bhh[wrow[tl]];
         if constexpr (SPLIT) {
             if (!Wsplit) winv[tl] = split_weights<H>(net.whh, gate, u, kq, wH16[tl], wL16[tl], wt_lane + 2 * tl);
         } else {
-#pragma unroll
-            for (int kk = 0; kk < 64; ++kk) wBh[tl][kk] = net.whh[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
+            load_whh_fragments<H>(net.whh, gate, u, kq, wBh[tl]);
         }
-        wXf[tl][0] = net.xw_fold[wrow * 8 + kq];        // B-fragments of (W_ih W_e) [4H,8], its bias, and the step-0 gates
-        wXf[tl][1] = net.xw_fold[wrow * 8 + 4 + kq];
-        bi[tl] = net.xb_fold[wrow];
-        sg[tl] = net.start_fold[wrow];
+        load_folded_input(net.xw_fold, net.xb_fold, wrow[tl], kq, wXf[tl], bi[tl]);   // (W_ih W_e) [4H,8] and its bias ...
+        sg[tl] = net.start_fold[wrow[tl]];                                             // ... and the step-0 gates
     }
 
     // ---- per-lane constants of the step loop (everything else of an address is uniform: resource + scalar offset)
@@ -276,7 +242,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
                             for (int q = 0; q < 4; ++q)
                                 if ((bm >> (16 * q)) & 0xffffull) h_miss |= 1u << (4 * (j & 1) + q);
                         }
-                        record_failure(diag, err, group, member, tile, k, wave, tag, h_miss, 0u, 0u, gpx);
+                        if (lane == 0) coop_failure_record(diag, err, gpx, group, member, tile, k, wave, tag, h_miss, 0u, 0u);
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
@@ -353,7 +319,8 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
                         if (__ballot(live && vp[j].y != tag)) p_miss |= 1u << (2 * j);
                         if (__ballot(live && vp[j].w != tag)) p_miss |= 1u << (2 * j + 1);
                     }
-                    record_failure(diag, err, group, member, tile, k, wave, tag, 0u, p_miss, (unsigned)__popcll(__ballot(live && latent_in_launch && vl.y != 1u)), gpx);
+                    const unsigned l_miss = (unsigned)__popcll(__ballot(live && latent_in_launch && vl.y != 1u));
+                    if (lane == 0) coop_failure_record(diag, err, gpx, group, member, tile, k, wave, tag, 0u, p_miss, l_miss);
                 }
 
                 // ---- logits and first-max argmax: lane (rq, r) = (row 4 wave + rq, candidate r)
@@ -376,10 +343,10 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
                     }
                     v = (has_lat && live) ? __fadd_rn(v, lv) : v;
                     float m = live ? v : -INFINITY;
-                    m = fmaxf(m, dpp_ror(m, 8));
-                    m = fmaxf(m, dpp_ror(m, 4));
-                    m = fmaxf(m, dpp_ror(m, 2));
-                    m = fmaxf(m, dpp_ror(m, 1));
+                    m = fmaxf(m, dpp_ror16(m, 8));
+                    m = fmaxf(m, dpp_ror16(m, 4));
+                    m = fmaxf(m, dpp_ror16(m, 2));
+                    m = fmaxf(m, dpp_ror16(m, 1));
                     // torch.max returns the FIRST maximum: the lowest candidate whose logit equals the row maximum
                     const unsigned hit = (unsigned)(__ballot(live && v == m) >> (16 * rq)) & 0xffffu;
                     const int pick_r = hit ? __ffs(hit) - 1 : 0;
@@ -429,11 +396,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
             }
             {   // one cell update per lane for the two rows it finishes (coop_common.h: cell_update_split)
                 f32x2 g0[2], g1[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    g0[q] = (f32x2{ah[0][2 * q], ah[0][2 * q + 1]} + pk_set(bh[0])) + f32x2{gx[0][2 * q], gx[0][2 * q + 1]};
-                    g1[q] = (f32x2{ah[1][2 * q], ah[1][2 * q + 1]} + pk_set(bh[1])) + f32x2{gx[1][2 * q], gx[1][2 * q + 1]};
-                }
+                gates_before_cell(ah[0], ah[1], bh, gx, g0, g1);
                 cell_update_split(g0, g1, c < 8, cst, hl);
             }
             {
@@ -498,10 +461,7 @@ __global__ __launch_bounds__(256, OCC) void pointer_decode_lean_kernel(DecodeArg
         if (abort_flag) break;
         ++tiles_done;
     }
-    if (tid == 0) {
-        if (abort_flag) coop_raise(err, sticky, 2u, seats);
-        coop_note_finished(sticky, GNNPN_STATUS_DEC_FINISHED, tiles_done);
-    }
+    coop_leave(err, sticky, seats, abort_flag, 2u, GNNPN_STATUS_DEC_FINISHED, tiles_done);
 }
 
 // pick_prob[b][t] = softmax of the step's window logits (+ the latent logits) at the pick = 1 / sum_j exp(v_j - v_pick):
@@ -565,22 +525,17 @@ int gnnpn_launch_decode_lean(const DecodeArgs& args, int n_nets, int precision, 
         GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: a tile of 16 problems must stay below 4 GB of encoder output");
     const bool split = precision == GNNPN_PREC_SPLIT;
     const bool wide = args.K > 8;
-    const bool stamps = (gnnpn_option_lstm_ablate() & 0x800) != 0;   // phase stamps (1-per-CU builds, n_per <= 8): a decoder-only bit
+    const bool stamps = (gnnpn_option_lstm_ablate() & GNNPN_ABLATE_DEC_STAMPS) != 0;   // phase stamps (1-per-CU builds, n_per <= 8): a decoder-only bit
     if (stamps && wide) GNNPN_FAIL(GNNPN_E_UNSUP, "pointer_decode: the stamped build exists for n_per <= 8");
     CoopLaunch c;
     const auto need = [&](int groups) { return lean_workspace(groups, args.B, args.T, args.K).total(); };
     if (const int rc = coop_begin("pointer_decode", n_nets, args.B, need, GNNPN_STATUS_DEC_EXPECTED, opts, workspace, workspace_bytes, s, c))
         return rc;
     const DecodeWorkspace w = lean_workspace(c.groups, args.B, args.T, args.K);
-    u64* p_h = reinterpret_cast<u64*>(c.buffers);
-    u64* p_p = reinterpret_cast<u64*>(c.buffers + w.h_bytes);
-    u64* p_l = reinterpret_cast<u64*>(c.buffers + w.h_bytes + w.p_bytes);
-    static unsigned* p_diag = gnnpn_decode_diag_buffer();   // failure record (written on a timed-out sweep only)
-    const int wt = (opts.write_through ? 1 : 0) | (opts.paired_start ? 2 : 0);
 #define GNNPN_LEAN(SPLIT_, OCC_, EVH_, ...)                                                                                           \
     hipLaunchKernelGGL((pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),       \
                        gnnpn_lds_padding((const void*)pointer_decode_lean_kernel<SPLIT_, OCC_, EVH_, ##__VA_ARGS__>, opts.lds_kb), s, args, \
-                       p_h, p_p, p_l, c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, wt, c.seats, p_diag)
+                       w.h(c.buffers), w.p(c.buffers), w.l(c.buffers), c.status, opts.sticky, n_nets, c.groups_per_net, c.gpx, coop_flags(opts), c.seats, c.diag)
     if (stamps) {
         if (split) GNNPN_LEAN(true, 1, 2, true);
         else GNNPN_LEAN(false, 1, 2, true);

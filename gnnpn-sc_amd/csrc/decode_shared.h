@@ -132,4 +132,3 @@ int gnnpn_launch_decode_coop(const DecodeArgs& args, int n_nets, int precision, 
 int gnnpn_launch_decode_lean(const DecodeArgs& args, int n_nets, int precision, bool shared_cu, const CoopOpts& opts,
                              void* workspace, int64_t workspace_bytes, hipStream_t s);
 int64_t gnnpn_decode_lean_workspace_bytes(int32_t B, int32_t T, int32_t n_per);
-unsigned* gnnpn_decode_diag_buffer();   // decode_coop.hip: device address of the failure record (gnnpn_decode_diag), or nullptr

@@ -21,7 +21,6 @@
 #include "recurrent.h"
 #include "lstm_shared.h"
 #include "coop_common.h"
-#include "decode_shared.h"   // gnnpn_decode_diag_buffer: the failure record both recurrent kernels write
 
 namespace {
 constexpr int H = COOP_H;
@@ -102,9 +101,9 @@ template <int PREC, bool PRE, bool DIAG>
 __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets, u64* __restrict__ xchg,
                                                                   unsigned* __restrict__ err, unsigned* __restrict__ sticky,
                                                                   int32_t B, int32_t L, int n_nets, int groups_per_net,
-                                                                  int gpx, int ablate_arg, unsigned* __restrict__ seats,
+                                                                  int gpx, int flags, unsigned* __restrict__ seats,
                                                                   unsigned* __restrict__ diag) {
-    const int ablate = DIAG ? (ablate_arg & ~0x1000) : (ablate_arg & 128);   // bit 7 = gnnpn_launch_opts_t.write_through (a tested mode)
+    const int ablate = DIAG ? (flags & GNNPN_ABLATE_ENCODER) : 0;   // the diagnostic switches ride the flag word (coop_common.h)
     constexpr bool F16 = PREC != 0, SPLIT = PREC == 2;
     constexpr int HS_FLOATS = PREC == 2 ? 3 * SPLIT_TILE / 2 : ROWS * LDH16;
     __shared__ __attribute__((aligned(16))) float hs[HS_FLOATS];      // fp32 tile (k-quarter-major, stride LDT) | fp16 tile | three fp16 piece tiles (stride LDH16 halfs)
@@ -115,17 +114,13 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
     const int kq = lane >> 4, c = lane & 15;
     // placement by claim (coop_common.h): one member per CU, a group's members on one XCD
     __shared__ int place[2];
-    int group, member;
     u64 p_entry = 0, p_placed = 0, p_weights = 0;          // diagnostic build: stamps of the launch's fixed part (prof[7..9] below)
     if constexpr (DIAG) p_entry = phase_stamp();
-    if (!coop_place<G>(err, gpx, place, group, member, seats, (ablate_arg & 0x1000) != 0, sticky)) return;   // surplus workgroup of the over-subscribed launch (bit 12: opts.paired_start)
+    CoopSeat seat;
+    if (!coop_enter<G>(err, sticky, seats, gpx, flags, n_nets, groups_per_net, place, &abort_flag, seat)) return;
     if constexpr (DIAG) p_placed = phase_stamp();
-    const int net = group / groups_per_net, gi = group % groups_per_net;
-    if (net >= n_nets) return;                            // spare group: takes part in no exchange
-    if (threadIdx.x == 0) abort_flag = 0;
-    __syncthreads();
-    const bool same_xcd = !(ablate & 128);
-    if (threadIdx.x == 0 && same_xcd) atomicAdd(err + COOP_PLACED_OFFSET / 4 + COOP_XCD_STRIDE * xcc_id(), 1u);   // statistics: workgroups on the fast path (per XCD: its own line)
+    const int group = seat.group, member = seat.member, net = seat.net, gi = seat.index_in_net;
+    const bool same_xcd = seat.same_xcd;
 
     const float* __restrict__ pre = PRE ? nets.pregates[net] : nullptr;
     const float* __restrict__ xin = nets.inputs[net];     // used when pre == nullptr (F = 8)
@@ -161,16 +156,8 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
                 for (int j = 0; j < 8; ++j)
                     wB16[tl][kk][j] = (_Float16)Wp[((size_t)((8 * kk + 2 * kq + (j >> 2)) * 4 + gate) * H + u) * 4 + (j & 3)];
         }
-        if constexpr (!PRE) {   // B-fragments of the folded input projection: w_in[wrow][4*kk2 + kq], kk2 = 0,1
-            wX[tl][0] = nets.w_in[net][wrow[tl] * 8 + kq];
-            wX[tl][1] = nets.w_in[net][wrow[tl] * 8 + 4 + kq];
-            bx[tl] = nets.b_in[net][wrow[tl]];
-        }
-        if constexpr (!F16) {
-#pragma unroll
-            for (int kk = 0; kk < 64; ++kk)   // packed layout: W[g*H+u][4kk+kq] = Wp[((kk*4+g)*H+u)*4+kq]
-                wB[tl][kk] = Wp[((size_t)(kk * 4 + gate) * H + u) * 4 + kq];
-        }
+        if constexpr (!PRE) load_folded_input(nets.w_in[net], nets.b_in[net], wrow[tl], kq, wX[tl], bx[tl]);
+        if constexpr (!F16) load_whh_fragments<H>(Wp, gate, u, kq, wB[tl]);
     }
 
     if constexpr (DIAG) {
@@ -220,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
 #endif
         if constexpr (SPLIT && !DIAG) asm volatile(".p2align 6\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(GNNPN_ENC_PAD_NOPS) : "memory");
         for (int t = 0; t < L; ++t, ++step) {
-            const bool stamps = ablate & 32;
+            const bool stamps = ablate & GNNPN_ABLATE_ENC_STAMPS;
             u64 s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
             if (stamps) s0 = phase_stamp();
 #pragma unroll
@@ -246,29 +233,12 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
             if (t == 0) {
                 for (int i = threadIdx.x; i < HS_FLOATS; i += 256) hs[i] = 0.0f;
                 if (!first_tile) ok = sweep_quarter<PREC>(xg + ((step - 1) & 1) * (ROWS * H), step, hs, wave, lane, false);
-            } else if (!(ablate & 8)) {
-                ok = sweep_quarter<PREC>(xg + ((step - 1) & 1) * (ROWS * H), step, hs, wave, lane, true, ablate & 4);
+            } else if (!(ablate & GNNPN_ABLATE_NO_SWEEP)) {
+                ok = sweep_quarter<PREC>(xg + ((step - 1) & 1) * (ROWS * H), step, hs, wave, lane, true, ablate & GNNPN_ABLATE_NO_TAG_WAIT);
             }
             if (!ok) abort_flag = 1;
-            if constexpr (DIAG) {   // failure record of the diagnostic build (shared with the decoder's, gnnpn_decode_diag; p_missing =
-                if (!ok && lane == 0 && diag) {   // 0xE0C marks an encoder entry): seats taken and workgroups ARRIVED per XCD so far
-                    const unsigned n = atomicAdd(diag, 1u);
-                    if (n < 31) {
-                        unsigned* rec = diag + 16 * (n + 1);
-                        const unsigned* cnt = err + COOP_XCDCNT_OFFSET / 4;
-                        const unsigned* arr = err + COOP_ARRIVE_OFFSET / 4;
-                        unsigned c0 = 0, c1 = 0, a0 = 0, a1 = 0;
-                        for (int x = 0; x < 4; ++x) {
-                            c0 |= (cnt[COOP_XCD_STRIDE * x] & 0xffu) << (8 * x);
-                            c1 |= (cnt[COOP_XCD_STRIDE * (4 + x)] & 0xffu) << (8 * x);
-                            a0 |= (arr[COOP_XCD_STRIDE * x] & 0xffu) << (8 * x);
-                            a1 |= (arr[COOP_XCD_STRIDE * (4 + x)] & 0xffu) << (8 * x);
-                        }
-                        rec[0] = group; rec[1] = member; rec[2] = tile; rec[3] = t; rec[4] = wave; rec[5] = step;
-                        rec[6] = 0; rec[7] = 0xE0Cu; rec[8] = 0; rec[9] = c0; rec[10] = c1; rec[11] = a0; rec[12] = a1;
-                        rec[13] = gpx; rec[14] = blockIdx.x; rec[15] = err[0];
-                    }
-                }
+            if constexpr (DIAG) {   // failure record of the diagnostic build: an encoder entry (coop_common.h)
+                if (!ok && lane == 0) coop_failure_record(diag, err, gpx, group, member, tile, t, wave, step, 0u, 0u, 0u, true);
             }
             if (stamps) s1 = phase_stamp();
             __syncthreads();
@@ -297,14 +267,14 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
                     }
                 }
             } else {
-                if (t > 0 && !(ablate & 1)) mfma_chain_pair<LDT, 16, true>(hs, c, kq, wB[0], wB[F16 ? 0 : 1], acc0, acc1);
+                if (t > 0 && !(ablate & GNNPN_ABLATE_NO_MFMA)) mfma_chain_pair<LDT, 16, true>(hs, c, kq, wB[0], wB[F16 ? 0 : 1], acc0, acc1);
             }
-            if (t + 1 < L && !(ablate & 0x400)) load_input(t + 1, pg_next, ax_next);
+            if (t + 1 < L && !(ablate & GNNPN_ABLATE_NO_INPUT_PREFETCH)) load_input(t + 1, pg_next, ax_next);
             // Issued BEHIND the MFMA stream (they would otherwise sit in front of it: measured 1.3k cycles per
             // step): the next step's input loads, and enc_out of the PREVIOUS step — after the hand-off wait
             // (stores retire in issue order with the sweep's loads, so storing before the sweep would lengthen
             // it), as whole 128-B lines (one per problem row) out of the LDS staging tile.
-            if (t > 0 && threadIdx.x < ROWS * 8 && !(ablate & 0x200)) {
+            if (t > 0 && threadIdx.x < ROWS * 8 && !(ablate & GNNPN_ABLATE_NO_ENC_OUT)) {
                 const int row = threadIdx.x >> 3, q = threadIdx.x & 7;
                 if (b0 + row < B)
                     *reinterpret_cast<float4*>(enc + ((int64_t)(b0 + row) * L + (t - 1)) * H + member * UNITS + 4 * q) =
@@ -330,11 +300,7 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
             {
                 // gates = (h.W_hh^T + b_hh) + (x.W_ih^T + b_ih); lanes c<8 hold (i,g), c>=8 hold (f,o)
                 f32x2 g0[2], g1[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    g0[q] = (f32x2{acc0[2 * q], acc0[2 * q + 1]} + pk_set(bh[0])) + f32x2{pg[0][2 * q], pg[0][2 * q + 1]};
-                    g1[q] = (f32x2{acc1[2 * q], acc1[2 * q + 1]} + pk_set(bh[1])) + f32x2{pg[1][2 * q], pg[1][2 * q + 1]};
-                }
+                gates_before_cell(acc0, acc1, bh, pg, g0, g1);
                 cell_update_split(g0, g1, c < 8, cst, hlast);
             }
             {
@@ -343,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
                 if constexpr (SPLIT) {
                     split_granule_store(dst, step + 1, hlast.x, same_xcd);
                     split_granule_store(dst + H, step + 1, hlast.y, same_xcd);
-                } else if (!(ablate & 16)) {
+                } else if (!(ablate & GNNPN_ABLATE_NO_PUBLISH)) {
                     if (same_xcd) {
                         granule_store_l2(dst, step + 1, hlast.x);
                         granule_store_l2(dst + H, step + 1, hlast.y);
@@ -394,10 +360,7 @@ __global__ __launch_bounds__(256, 2) void lstm_encode_coop_kernel(LstmNets nets,
         first_tile = false;
         ++tiles_done;
     }
-    if (threadIdx.x == 0) {
-        if (abort_flag) coop_raise(err, sticky, 1u, seats);
-        coop_note_finished(sticky, GNNPN_STATUS_ENC_FINISHED, tiles_done);
-    }
+    coop_leave(err, sticky, seats, abort_flag, 1u, GNNPN_STATUS_ENC_FINISHED, tiles_done);
 }
 
 
@@ -455,21 +418,20 @@ int gnnpn_launch_encode_coop(const LstmNets& nets, int n_nets, int32_t B, int32_
         if ((nets.pregates[n] != nullptr) != pre)
             GNNPN_FAIL(GNNPN_E_ARG, "lstm_encode: all nets of a call must use the same input-side form");
     const int prec = precision;   // GNNPN_PREC_*: 0 fp32, 1 fp16 operands, 2 fp16-split operands
-    const int abl = (gnnpn_option_lstm_ablate() & ~(0x800 | 0x1000 | 0x2000)) | (opts.write_through ? 128 : 0);   // bit 11 belongs to the decoder (phase stamps), 13 to the launch (coop_begin)
-    const bool diag = (abl & ~128) != 0;   // diagnostic build (folded form; fp32 with every switch, exact split with the phase stamps)
-    if (diag && (prec == 1 || pre || (prec == 2 && (abl & ~(128 | 32)) != 0)))
+    const int abl = gnnpn_option_lstm_ablate() & GNNPN_ABLATE_ENCODER;
+    const bool diag = abl != 0;   // diagnostic build (folded form; fp32 with every switch, exact split with the phase stamps)
+    if (diag && (prec == 1 || pre || (prec == 2 && (abl & ~GNNPN_ABLATE_ENC_STAMPS) != 0)))
         GNNPN_FAIL(GNNPN_E_UNSUP, "lstm_encode: diagnostics are built for the folded form (fp32: all switches; split: stamps only)");
     CoopLaunch c;
     if (const int rc = coop_begin("lstm_encode", n_nets, B, encode_workspace_bytes, GNNPN_STATUS_ENC_EXPECTED, opts, workspace,
                                   workspace_bytes, s, c))
         return rc;
     u64* p_x = reinterpret_cast<u64*>(c.buffers);
-    const int abl_arg = abl | (opts.paired_start ? 0x1000 : 0);   // bit 12 rides the kernel argument only (placement, coop_place)
-    static unsigned* p_diag = gnnpn_decode_diag_buffer();   // failure record (diagnostic build, timed-out sweep only)
+    const int flags = coop_flags(opts) | abl;
 #define GNNPN_ENC(PREC_, PRE_, DIAG_)                                                                                        \
     hipLaunchKernelGGL((lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>), dim3(COOP_OVERSUB * c.groups * G), dim3(256),             \
                        gnnpn_lds_padding((const void*)lstm_encode_coop_kernel<PREC_, PRE_, DIAG_>, opts.lds_kb), s, nets, p_x, \
-                       c.status, opts.sticky, B, L, n_nets, c.groups_per_net, c.gpx, abl_arg, c.seats, p_diag)
+                       c.status, opts.sticky, B, L, n_nets, c.groups_per_net, c.gpx, flags, c.seats, c.diag)
     if (diag) {
         if (prec == 2) GNNPN_ENC(2, false, true);
         else GNNPN_ENC(0, false, true);

@@ -439,6 +439,29 @@ COOP_PLACED_OFFSET = 14336   # seated workgroups on the same-XCD hand-off, per X
 COOP_TAKEN_OFFSET = 10240    # seat flags, 64 words per XCD
 
 
+# The bits of the "lstm_ablate" diagnostics option (set_option), as include/gnnpn_hip.h names them (tests/test_host_logic.py compares).
+GNNPN_ABLATE_NO_MFMA = 0x1
+GNNPN_ABLATE_NO_TRANSCENDENTALS = 0x2
+GNNPN_ABLATE_NO_TAG_WAIT = 0x4
+GNNPN_ABLATE_NO_SWEEP = 0x8
+GNNPN_ABLATE_NO_PUBLISH = 0x10
+GNNPN_ABLATE_ENC_STAMPS = 0x20          # encoder phase stamps
+GNNPN_ABLATE_REFUSED = 0x80             # was the write-through hand-off: the ``write_through`` argument now
+GNNPN_ABLATE_NO_ENC_OUT = 0x200
+GNNPN_ABLATE_NO_INPUT_PREFETCH = 0x400
+GNNPN_ABLATE_DEC_STAMPS = 0x800         # decoder phase stamps
+GNNPN_ABLATE_KEEP_WORKSPACE = 0x2000    # tests only: a launch does not zero its workspace
+GNNPN_ABLATE_ENCODER = 0x63f            # the encoder's bits together
+
+# The 16 words of a failure-record entry, in the order of csrc/coop_common.h's COOP_REC_* indices (tests/test_host_logic.py compares);
+# an encoder's entry carries FAILURE_RECORD_ENCODER_MARK in "p_missing_members" and per-XCD arrival counters where the decoders
+# put the clock.
+FAILURE_RECORD_WORDS = ("group", "member", "tile", "k", "wave", "tag", "h_missing_members", "p_missing_members", "latent_missing",
+                        "claims_xcd0_3", "claims_xcd4_7", "t_lo", "t_hi", "gpx", "workgroup", "launch_status")
+FAILURE_RECORD_ENCODER_MARK = 0xE0C
+_ENCODER_RECORD_WORDS = tuple({"t_lo": "arrivals_xcd0_3", "t_hi": "arrivals_xcd4_7"}.get(n, n) for n in FAILURE_RECORD_WORDS)
+
+
 def coop_per_xcd(words, offset):
     """The eight per-XCD counters at byte ``offset`` of a status area, from its 32-bit ``words`` (a list or an int32 tensor)."""
     w = offset // 4
@@ -622,14 +645,19 @@ def graph_replay(graph, all_ws):
 
 
 def decode_failure_record(clear=True):
-    """gnnpn_decode_diag as a list of dicts (one per timed-out decoder sweep, the first 31) — diagnosis only."""
+    """gnnpn_decode_diag as a list of dicts (one per timed-out sweep of a cooperative kernel, the first 31) — diagnosis only."""
     import ctypes
     buf = (ctypes.c_uint32 * 512)()
     _lib.check(_lib.load().gnnpn_decode_diag(ctypes.cast(buf, ctypes.c_void_p), 512, 1 if clear else 0), "gnnpn_decode_diag")
-    names = ("group", "member", "tile", "k", "wave", "tag", "h_missing_members", "p_missing_members", "latent_missing",
-             "claims_xcd0_3", "claims_xcd4_7", "t_lo", "t_hi", "gpx", "workgroup", "launch_status")
-    n = int(buf[0])
-    return {"failures": n, "records": [dict(zip(names, [int(v) for v in buf[16 * (i + 1):16 * (i + 2)]])) for i in range(min(n, 31))]}
+    return parse_failure_record([int(v) for v in buf])
+
+
+def parse_failure_record(words):
+    """The words of gnnpn_decode_diag -> {"failures": n, "records": [one dict per entry]}, every entry under its writer's word names."""
+    n, w, mark = int(words[0]), len(FAILURE_RECORD_WORDS), FAILURE_RECORD_WORDS.index("p_missing_members")
+    entries = [words[w * (i + 1):w * (i + 2)] for i in range(min(n, 31))]
+    return {"failures": n, "records": [dict(zip(_ENCODER_RECORD_WORDS if e[mark] == FAILURE_RECORD_ENCODER_MARK else FAILURE_RECORD_WORDS, e))
+                                       for e in entries]}
 
 
 _default_ws = {}

@@ -401,17 +401,33 @@ int gnnpn_lds_footprint_kb(int kb);
 int64_t gnnpn_last_launch_units(void);
 
 /* Diagnostics switch (process-wide; tools/ only):
- *   "lstm_ablate"    phase stamps / ablations of the cooperative kernels; results are WRONG when non-zero.
+ *   "lstm_ablate"    phase stamps / ablations of the cooperative kernels, a bit field of GNNPN_ABLATE_* (below); results are
+ *                    WRONG when an ablation bit is set.
  * Implementation choice and placement control are per-call arguments (gnnpn_launch_opts_t), not options.
  * Unknown names / out-of-range values: GNNPN_E_ARG. */
 int gnnpn_set_option(const char* name, int value);
+/* The bits of "lstm_ablate".  The encoder bits select the encoder's diagnostic build (folded input side; fp32: every switch,
+ * exact split: the stamps only); gnnpn_sc_amd/ops.py carries the same names (tests/test_host_logic.py compares the two). */
+#define GNNPN_ABLATE_NO_MFMA 0x1             /* encoder: no recurrent product */
+#define GNNPN_ABLATE_NO_TRANSCENDENTALS 0x2  /* encoder: reserved (the cell update has no switch any more) */
+#define GNNPN_ABLATE_NO_TAG_WAIT 0x4         /* encoder: one sweep pass, whatever the tags say */
+#define GNNPN_ABLATE_NO_SWEEP 0x8            /* encoder: no hand-off sweep */
+#define GNNPN_ABLATE_NO_PUBLISH 0x10         /* encoder: no publish of h (fp32) */
+#define GNNPN_ABLATE_ENC_STAMPS 0x20         /* encoder: phase stamps (tools/stamp_encode.py) */
+#define GNNPN_ABLATE_REFUSED 0x80            /* was the write-through hand-off: gnnpn_launch_opts_t.write_through; GNNPN_E_ARG */
+#define GNNPN_ABLATE_NO_ENC_OUT 0x200        /* encoder: no enc_out stores inside the step loop */
+#define GNNPN_ABLATE_NO_INPUT_PREFETCH 0x400 /* encoder: no input loads for the next step */
+#define GNNPN_ABLATE_DEC_STAMPS 0x800        /* decoder: phase stamps (tools/stamp_decode.py; 1-per-CU builds, n_per <= 8) */
+#define GNNPN_ABLATE_KEEP_WORKSPACE 0x2000   /* tests only: the launch does not zero its workspace; every workgroup must notice (code 8) */
+#define GNNPN_ABLATE_ENCODER 0x63f           /* the encoder's bits together */
 
 /* Failure record of the cooperative decoder (diagnosis only; host call, synchronises the device): copies the first
  * n_words (<= 512) uint32 of the record to the HOST buffer `out`, optionally clearing it.  out[0] = timed-out sweeps
  * since the last clear; then 16 words per failing wave (the first 31): group, member, tile, step k, wave, expected tag,
  * mask of members whose h granules were missing, mask of members whose partial dots were missing, missing latent
  * lanes, the launch's eight per-XCD claim counters (one byte each, two words), device realtime (lo, hi), groups per
- * XCD, workgroup id, the launch's status word. */
+ * XCD, workgroup id, the launch's status word.  A writer leaves what it does not know at zero.  An entry of the encoder's
+ * diagnostic build carries 0xE0C in the partial-dot word and the eight per-XCD ARRIVAL counters in place of the realtime. */
 int gnnpn_decode_diag(uint32_t* out, int32_t n_words, int32_t clear);
 /* Housekeeping after a cooperative launch reported a hand-off time-out (sticky status != 0): clears the per-device count of
  * launches that are still staffing (such a launch may never have left it); synchronises the device. */

@@ -445,7 +445,7 @@ def test_lstm_encode_cooperative_build(dev, precision, pre, diag):
     three-piece operands) are held to the fp32 yardstick (factor 4, floor 2e-6).  "f16" rounds W_hh and h to fp16 by design
     (unit roundoff 2^-11 per operand): it is held to 10 x 2^-11 = 4.9e-3 absolute — the bar the project set for this option
     (5e-3 against the fp32 path) read against float64 — and must differ from the fp32 build (else the option did nothing).
-    The stamped builds (timing diagnostics: lstm_ablate bit 5, folded input side only) give results like any other build."""
+    The stamped builds (timing diagnostics: GNNPN_ABLATE_ENC_STAMPS, folded input side only) give results like any other build."""
     from pn_inputs import pn_inputs
     ops = _ops()
     H, B, T, K = 256, 37, 6, 3
@@ -457,7 +457,7 @@ def test_lstm_encode_cooperative_build(dev, precision, pre, diag):
     assert ops.coop_supported(H)                                      # the default form at H = 256: nothing is forced
     try:
         if diag:
-            ops.set_option("lstm_ablate", 32)                        # the only way into the stamped builds (tools/ablate_encode.py)
+            ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_ENC_STAMPS)   # the only way into the stamped builds (tools/ablate_encode.py)
         enc, h_n, c_n = twice(lambda: ops.lstm_encode(args, precision=precision))
         ops.check_status(dev)
     finally:
@@ -481,7 +481,7 @@ def test_lstm_encode_cooperative_build(dev, precision, pre, diag):
 
 # ---- the cooperative decoders: pointer_decode_lean_kernel<SPLIT, OCC, EVH, DIAG>, pointer_decode_coop_kernel<FOLD, SAMPLE> ----------
 # build -> (precision, decode_impl, K, fold, stamps, sampled).  decode_lean.hip: OCC = 2 is the 256-register build for two
-# workgroups per CU (impl 4), EVH = 1 the wide windows (n_per 9..16), DIAG the phase-stamp build (lstm_ablate bit 11, n_per <= 8).
+# workgroups per CU (impl 4), EVH = 1 the wide windows (n_per 9..16), DIAG the phase-stamp build (GNNPN_ABLATE_DEC_STAMPS, n_per <= 8).
 # decode_coop.hip: <false,false> the literal two-stage input side (fold off), <true,true> every High pick drawn.
 DECODE_COOP = {
     "lean<false,1,1,false>": ("f32", 2, 10, True, False, False), "lean<false,1,2,false>": ("f32", 2, 3, True, False, False),
@@ -515,7 +515,7 @@ def test_pointer_decode_cooperative_build(dev, build):
     xd = x.to(dev)
     try:
         if stamps:
-            ops.set_option("lstm_ablate", 0x800)
+            ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_DEC_STAMPS)
         out = twice(lambda: two_level_greedy(low, high, xd, fold=fold, precision=precision, decode_impl=impl, sample_high_seed=seed))
         ops.check_status(dev)
     finally:

@@ -591,7 +591,7 @@ def test_split_precision_needs_the_cooperative_form(dev):
 
 def test_a_launch_on_a_dirty_workspace_is_loud(dev):
     """coop_place's check that the status area was clean when the launch began (status code 8): with the per-launch zeroing
-    switched off (test hook: lstm_ablate bit 13) a second encoder launch on the same workspace finds the first one's seat and
+    switched off (test hook: GNNPN_ABLATE_KEEP_WORKSPACE) a second encoder launch on the same workspace finds the first one's seat and
     arrival counters — every workgroup would leave as surplus and the outputs would be garbage with nothing timing out; instead the
     launch's own word and the sticky word carry code 8 and ops.check_status raises.  (Seen for real: DESIGN.md section 4.4; profiles/LOG_r01_r04.md section 13.3.)"""
     from gnnpn_sc_amd import custom_ops, ops
@@ -603,7 +603,7 @@ def test_a_launch_on_a_dirty_workspace_is_loud(dev):
     enc0 = custom_ops.lstm_encode([args], ws=ws)[0][0].clone()
     ws.check()
     try:
-        ops.set_option("lstm_ablate", 0x2000)
+        ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_KEEP_WORKSPACE)
         custom_ops.lstm_encode([args], ws=ws)
         torch.cuda.synchronize()
         assert int(ws._encode[:4].view(torch.int32).item()) & 8 and int(ws.status[0].item()) & 8
@@ -681,14 +681,14 @@ def test_poisoned_status_area_ends_loud_or_correct(dev, which, kind):
     assert ws.last_progress[which]["expected"] == ops.Workspaces.coop_units(2, B)
     buf = ws._encode if which == "encoder" else ws._decode
     try:
-        # the workspaces as a per-launch zeroing would leave them, then the poison; the test hook (lstm_ablate bit 13) makes the
+        # the workspaces as a per-launch zeroing would leave them, then the poison; the test hook (GNNPN_ABLATE_KEEP_WORKSPACE) makes the
         # launches skip their own zeroing (the decode call's encoder launch included: its workspace is clean)
         ws._encode.zero_()
         if ws._decode is not None:
             ws._decode.zero_()
         buf[:ops.COOP_STATUS_BYTES].view(torch.int32).copy_(_poison(kind, ops.COOP_STATUS_BYTES // 4, gen))
         torch.cuda.synchronize()
-        ops.set_option("lstm_ablate", 0x2000)
+        ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_KEEP_WORKSPACE)
         got = launch()
         torch.cuda.synchronize()
         ops.set_option("lstm_ablate", 0)
@@ -716,7 +716,7 @@ def test_a_launch_that_does_nothing_is_a_shortfall(dev):
     custom_ops.lstm_encode(args, ws=ws)
     ws.check()
     try:
-        ops.set_option("lstm_ablate", 0x2000)
+        ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_KEEP_WORKSPACE)
         custom_ops.lstm_encode(args, ws=ws)         # on the counters the first launch left behind
         word, prog = ws._read()
         assert prog["encoder"]["expected"] == 2 * ops.Workspaces.coop_units(2, 256) == prog["encoder"]["host_expected"]

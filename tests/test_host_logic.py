@@ -572,3 +572,36 @@ def test_status_area_layout_matches_coop_common():
         assert int(header[name]) == getattr(ops, name), name
     assert ops.coop_per_xcd(list(range(ops.COOP_STATUS_BYTES // 4)), ops.COOP_ARRIVE_OFFSET) == \
         [ops.COOP_ARRIVE_OFFSET // 4 + ops.COOP_XCD_STRIDE * x for x in range(8)]
+
+
+def test_ablate_bits_match_the_header():
+    """ops' names for the bits of the "lstm_ablate" option are the GNNPN_ABLATE_* values of include/gnnpn_hip.h, name for name."""
+    import re
+    from gnnpn_sc_amd import ops
+    with open(os.path.join(ROOT, "include", "gnnpn_hip.h")) as f:
+        header = {n: int(v, 0) for n, v in re.findall(r"^#define (GNNPN_ABLATE_\w+) (0x[0-9a-fA-F]+|\d+)\b", f.read(), re.M)}
+    mine = {n: getattr(ops, n) for n in dir(ops) if n.startswith("GNNPN_ABLATE_")}
+    assert len(header) >= 12 and header == mine
+    assert header["GNNPN_ABLATE_REFUSED"] == 0x80 and header["GNNPN_ABLATE_KEEP_WORKSPACE"] == 0x2000      # the values are ABI
+    encoder = [v for n, v in header.items() if n.startswith(("GNNPN_ABLATE_NO_", "GNNPN_ABLATE_ENC_"))]
+    assert header["GNNPN_ABLATE_ENCODER"] == sum(encoder) and len(set(encoder)) == len(encoder)
+
+
+def test_failure_record_words_match_coop_common():
+    """ops.FAILURE_RECORD_WORDS names the words of a failure-record entry as csrc/coop_common.h's COOP_REC_* indices order them, and an
+    entry that carries the encoder's mark is read under the encoder's names (arrival counters where the decoders put the clock)."""
+    import re
+    from gnnpn_sc_amd import ops
+    with open(os.path.join(ROOT, "gnnpn-sc_amd", "csrc", "coop_common.h")) as f:
+        text = f.read()
+    body = re.search(r"enum CoopRecordWord \{(.*?)\};", text, re.S).group(1)
+    names = re.findall(r"\bCOOP_REC_(\w+)", re.sub(r"//[^\n]*", "", body))
+    assert names[-1] == "WORDS" and tuple(n.lower() for n in names[:-1]) == ops.FAILURE_RECORD_WORDS and len(names) - 1 == 16
+    assert int(re.search(r"COOP_REC_ENCODER_MARK = (0x[0-9A-Fa-f]+);", text).group(1), 16) == ops.FAILURE_RECORD_ENCODER_MARK
+    words = [2] + [0] * 15 + list(range(100, 116)) + list(range(200, 216)) + [0] * (512 - 48)      # entry i at word 16 (i + 1)
+    words[32 + ops.FAILURE_RECORD_WORDS.index("p_missing_members")] = ops.FAILURE_RECORD_ENCODER_MARK
+    rec = ops.parse_failure_record(words)
+    assert rec["failures"] == 2 and len(rec["records"]) == 2
+    assert rec["records"][0] == dict(zip(ops.FAILURE_RECORD_WORDS, range(100, 116)))
+    enc = rec["records"][1]
+    assert enc["arrivals_xcd0_3"] == 211 and enc["arrivals_xcd4_7"] == 212 and "t_lo" not in enc and enc["claims_xcd0_3"] == 209

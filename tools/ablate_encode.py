@@ -12,6 +12,8 @@ for n in range(2):
                  "b_in": ((torch.rand(4 * H, generator=g) * 2 - 1) * 0.3).to(dev),
                  "whh": ops.pack_lstm_weight((torch.rand(4 * H, H, generator=g) * 2 - 1) / 16).to(dev),
                  "bhh": ((torch.rand(4 * H, generator=g) * 2 - 1) / 16).to(dev)})
+MFMA, TRANSC, SWEEP, PUBLISH = (ops.GNNPN_ABLATE_NO_MFMA, ops.GNNPN_ABLATE_NO_TRANSCENDENTALS, ops.GNNPN_ABLATE_NO_SWEEP,
+                                ops.GNNPN_ABLATE_NO_PUBLISH)
 def timeit(label, abl):
     ops.set_option("lstm_ablate", abl)
     for _ in range(3): ops.lstm_encode(nets)
@@ -23,25 +25,25 @@ def timeit(label, abl):
     ms = e0.elapsed_time(e1) / 10
     print(f"{label:40s} ablate={abl:2d}  {ms:.3f} ms  {ms * 1e3 / L:.2f} us/step", flush=True)
 timeit("full", 0)
-timeit("diagnostic build, stamps on", 32)
+timeit("diagnostic build, stamps on", ops.GNNPN_ABLATE_ENC_STAMPS)
 timeit("full", 0)
-timeit("diagnostic build, stamps on", 32)
-timeit("no enc_out flush", 0x200)
-timeit("no input prefetch", 0x400)
-timeit("neither", 0x600)
-timeit("no MFMA", 1)
-timeit("no transcendentals", 2)
-timeit("no MFMA, no transcendentals", 3)
-timeit("no tag wait (one pass)", 4)
-timeit("no sweep at all", 8)
-timeit("no sweep, no publish", 24)
-timeit("no sweep/publish/MFMA", 25)
-timeit("no sweep/publish/MFMA/transc", 27)
-timeit("no sweep/publish/transc", 26)
+timeit("diagnostic build, stamps on", ops.GNNPN_ABLATE_ENC_STAMPS)
+timeit("no enc_out flush", ops.GNNPN_ABLATE_NO_ENC_OUT)
+timeit("no input prefetch", ops.GNNPN_ABLATE_NO_INPUT_PREFETCH)
+timeit("neither", ops.GNNPN_ABLATE_NO_ENC_OUT | ops.GNNPN_ABLATE_NO_INPUT_PREFETCH)
+timeit("no MFMA", MFMA)
+timeit("no transcendentals", TRANSC)
+timeit("no MFMA, no transcendentals", MFMA | TRANSC)
+timeit("no tag wait (one pass)", ops.GNNPN_ABLATE_NO_TAG_WAIT)
+timeit("no sweep at all", SWEEP)
+timeit("no sweep, no publish", SWEEP | PUBLISH)
+timeit("no sweep/publish/MFMA", SWEEP | PUBLISH | MFMA)
+timeit("no sweep/publish/MFMA/transc", SWEEP | PUBLISH | MFMA | TRANSC)
+timeit("no sweep/publish/transc", SWEEP | PUBLISH | TRANSC)
 ops.set_option("lstm_ablate", 0)
 
-# phase stamps (diagnostic build path: lstm_ablate bit 5)
-ops.set_option("lstm_ablate", 32)
+# phase stamps (diagnostic build path: GNNPN_ABLATE_ENC_STAMPS)
+ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_ENC_STAMPS)
 ops.lstm_encode(nets); torch.cuda.synchronize()
 ws = ops.workspaces(dev).encode()
 prof = ws[32:32 + 56].view(torch.int64).cpu().tolist()

@@ -11,8 +11,10 @@ table = synth.make_service_table(w["T"], w["S"], seed=0, degree=32)
 net, low, high = bench.build_models(w["T"], w["S"], w["K"], dev, w["n_gcn"])
 svc = DeviceServices.from_table(table, dev)
 batch = DeviceBatch.from_problems(synth.make_problem_batch(table, w["B"], seed=1, tasks_per_problem=w["n_t"]), dev)
-for label, abl in (("production build", 0), ("no MFMA", 1), ("no transcendentals", 2),
-                   ("no tag wait", 4), ("no sweep", 8), ("no sweep, no publish", 24), ("no enc_out flush, no input prefetch", 0x600)):
+for label, abl in (("production build", 0), ("no MFMA", ops.GNNPN_ABLATE_NO_MFMA), ("no transcendentals", ops.GNNPN_ABLATE_NO_TRANSCENDENTALS),
+                   ("no tag wait", ops.GNNPN_ABLATE_NO_TAG_WAIT), ("no sweep", ops.GNNPN_ABLATE_NO_SWEEP),
+                   ("no sweep, no publish", ops.GNNPN_ABLATE_NO_SWEEP | ops.GNNPN_ABLATE_NO_PUBLISH),
+                   ("no enc_out flush, no input prefetch", ops.GNNPN_ABLATE_NO_ENC_OUT | ops.GNNPN_ABLATE_NO_INPUT_PREFETCH)):
     ops.set_option("lstm_ablate", abl)
     pipe = ML2PNPipeline(net, low, high, w["K"])
     runner = PipelinedRunner(pipe, svc, batch, slots=2)

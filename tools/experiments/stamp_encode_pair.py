@@ -8,7 +8,7 @@ x = torch.rand(B, L, 8, generator=g).to(dev)
 nets = [{"inputs": x, "w_in": ((torch.rand(4 * H, 8, generator=g) * 2 - 1) * 0.3).to(dev), "b_in": ((torch.rand(4 * H, generator=g) * 2 - 1) * 0.3).to(dev),
          "whh": ops.pack_lstm_weight((torch.rand(4 * H, H, generator=g) * 2 - 1) / 16).to(dev), "bhh": ((torch.rand(4 * H, generator=g) * 2 - 1) / 16).to(dev)} for _ in range(2)]
 for _ in range(3): ops.lstm_encode(nets, precision="split", impl=5)
-ops.set_option("lstm_ablate", 32)
+ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_ENC_STAMPS)
 ops.lstm_encode(nets, precision="split", impl=5); torch.cuda.synchronize()
 ws = ops.workspaces(dev).encode()
 prof = ws[32:32 + 48].view(torch.int64).cpu().tolist()

@@ -19,7 +19,7 @@ for prec in ("split+presplit", "split", "f32"):
         for d in nets: d.pop("whh_split", None)
     prec = prec.split("+")[0]
     for _ in range(3): ops.lstm_encode(nets, precision=prec)
-    ops.set_option("lstm_ablate", 32)
+    ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_ENC_STAMPS)
     for rep in range(2):
         ops.lstm_encode(nets, precision=prec); torch.cuda.synchronize()
         ws = ops.workspaces(dev).encode()

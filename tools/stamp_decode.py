@@ -10,7 +10,7 @@ net, low, high = build_models(T, 2507, K, dev)
 g = torch.Generator().manual_seed(0)
 x = torch.rand(B, T * K, 8, generator=g).to(dev)
 for _ in range(3): two_level_greedy(low, high, x)
-ops.set_option("lstm_ablate", 0x800)
+ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_DEC_STAMPS)
 two_level_greedy(low, high, x); torch.cuda.synchronize()
 ws = ops.workspaces(dev).decode(B, T, K)
 prof = ws[32:32 + 64].view(torch.int64).cpu().tolist()

@@ -22,7 +22,7 @@ for prec in ("f32", "split"):
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 3
     print(prec, f"B={B} L={L}: {ms:.3f} ms per launch (production build), {ms / L * 1e3:.3f} us per step", flush=True)
-    ops.set_option("lstm_ablate", 32)
+    ops.set_option("lstm_ablate", ops.GNNPN_ABLATE_ENC_STAMPS)
     ops.lstm_encode(nets, precision=prec); torch.cuda.synchronize()
     ws = ops.workspaces(dev).encode()
     prof = ws[32:32 + 80].view(torch.int64).cpu().tolist()
