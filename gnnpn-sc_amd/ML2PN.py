@@ -54,7 +54,7 @@ def check(dataset, serCategory, epoch):
 
 
 def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
-          sample_seed=None, descend=None, all_starts=False):
+          sample_seed=None, descend=None, all_starts=False, pair_rounds=None):
     """Run ML+2PN inference over ``./data/<dataset>`` on the GPU and write the two artefacts that
     ``check`` reads: the rankings of ALL problems (trainML.py:146-149 format, [P][S] ints) and the
     High-level actions of the test quarter (trainPNHigh.py:133-144 format, [T][nTest][8]).
@@ -72,12 +72,17 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     together with ``woa`` the ES-WOA run starts from the descended composition.
     ``all_starts`` (with samples > 1 and descend): the test quarter's rows of EVERY replica are kept per batch and descent runs from
     all of them (pipeline.descend_starts), the lowest local optimum per problem kept: ``ML+2PN+multistart.txt`` in place of
-    ``ML+2PN+descent.txt``; with ``woa`` ES-WOA starts from that winner.  The PNHigh artefact is the best-of winner by R either way."""
+    ``ML+2PN+descent.txt``; with ``woa`` ES-WOA starts from that winner.  The PNHigh artefact is the best-of winner by R either way.
+    ``pair_rounds`` (>= 1, with descend): pair-swap descent with that many rounds allowed in place of the one-swap descent
+    (pipeline.descend_pairs / descend_starts_pairs): ``ML+2PN+pairs.txt`` (``ML+2PN+multistart+pairs.txt`` with all_starts) in
+    place of the descent artefact, its format plus the per-problem rounds, pair_moves and converged; ES-WOA starts from its result."""
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
     if all_starts and (samples < 2 or descend is None):
         raise ValueError("ML2PN.infer: all_starts needs samples > 1 and descend")
+    if pair_rounds is not None and (descend is None or pair_rounds < 1):
+        raise ValueError("ML2PN.infer: pair_rounds needs descend and at least one round")
     d = f"./data/{dataset}/"
     ds = {k: json.load(open(d + fn)) for k, fn in (
         ("nodefeatures", "nodefeatures.data"), ("edge_indices", "edge_indices.data"), ("labels", "labels.data"),
@@ -122,22 +127,26 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     paths = write_artifacts(dataset, epoch, rankings, actions)
     if woa is not None or descend is not None:
         refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
-                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend,
+                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
 
-def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None):
+def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None,
+                        pair_rounds=None):
     """ES-WOA refinement of the test quarter's actions [nTest, T, 8] on the device, written as the WOA approach's
     ``ML+2PN+WOA.txt`` (WOA.py:286-296): quality = minCost / best fitness, problem ``idx`` on stream ``seed + idx``.
     ``descend`` = sweeps (>= 1): one-swap descent first, written as ``ML+2PN+descent.txt``; ES-WOA (popSize > 0) then starts from it.
     ``starts`` [nTest, N, T, 8] (with ``descend``): descent from every one of the N rows per problem, the lowest optimum kept
-    (pipeline.descend_starts), written as ``ML+2PN+multistart.txt`` instead; ES-WOA then starts from the winner's rows."""
+    (pipeline.descend_starts), written as ``ML+2PN+multistart.txt`` instead; ES-WOA then starts from the winner's rows.
+    ``pair_rounds`` (>= 1, with ``descend``): pair-swap descent in place of the one-swap descent in each of these, written as
+    ``ML+2PN+pairs.txt`` / ``ML+2PN+multistart+pairs.txt`` with the per-problem rounds, pair_moves and converged beside the four keys."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import DeviceBatch, descend as descend_actions, descend_starts, refine
+    from .pipeline import DeviceBatch, descend as descend_actions, descend_pairs, descend_starts, descend_starts_pairs, refine
+    counters = lambda r: {k: r[k].cpu().tolist() for k in ("rounds", "pair_moves", "converged")}      # noqa: E731
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
     first = P // 4 * 3
@@ -153,11 +162,22 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     if descend is not None and starts is not None:
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        multi = descend_starts(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev), max_sweeps=descend,
-                               reduct=reduct, min_cost=min_cost)
+        rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
+        if pair_rounds is None:
+            multi = descend_starts(svc, batch, rows, max_sweeps=descend, reduct=reduct, min_cost=min_cost)
+        else:
+            multi = descend_starts_pairs(svc, batch, rows, max_sweeps=descend, pair_rounds=pair_rounds, reduct=reduct, min_cost=min_cost)
         quality = multi["quality"].cpu().tolist()
-        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+multistart.txt")
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first,
+                                  name="ML+2PN+multistart.txt" if pair_rounds is None else "ML+2PN+multistart+pairs.txt",
+                                  extra=None if pair_rounds is None else counters(multi))
         out = {"actions": multi["actions"]}          # refine below rebuilds the winner's tables and repeats its descent
+    elif descend is not None and pair_rounds is not None:
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        res = descend_pairs(svc, batch, out, max_sweeps=descend, max_rounds=pair_rounds, reduct=reduct, min_cost=min_cost)
+        quality = res["quality"].cpu().tolist()
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+pairs.txt", extra=counters(res))
     elif descend is not None:
         torch.cuda.synchronize(dev)
         t0 = time.time()
@@ -169,7 +189,8 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
         if descend is None:
             res = pipe.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost)
         else:
-            res = refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend)
+            res = refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend,
+                         pair_rounds=pair_rounds or 0)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first)
     return written

@@ -165,10 +165,11 @@ class WOA:
         return out
 
 
-def write_ml2pn_woa(dataset, quality, per_problem, first, times=0, name="ML+2PN+WOA.txt"):
+def write_ml2pn_woa(dataset, quality, per_problem, first, times=0, name="ML+2PN+WOA.txt", extra=None):
     """The progress lines and ``./solutions/WOA/<dataset>/ML+2PN+WOA.txt`` of the ML2PNWOATest mode (WOA.py:286-296) for the
     qualities of test problems ``first``, ``first + 1`` ...; ``per_problem``: the time booked to each.  ``name``: another file
-    name in that directory for the same format (the descent stage writes ``ML+2PN+descent.txt``)."""
+    name in that directory for the same format (the descent stage writes ``ML+2PN+descent.txt``); ``extra``: further per-problem
+    lists written after the four keys (the pair-swap descent's counters)."""
     import json
     out = {"quality": [], "time": [], "averageQ": 0, "averageT": 0}
     for i, q in enumerate(quality):                                                            # :286-292
@@ -178,6 +179,7 @@ def write_ml2pn_woa(dataset, quality, per_problem, first, times=0, name="ML+2PN+
         out["averageT"] = sum(out["time"]) / (times + 1)
         print(first + i, out["averageQ"], out["averageT"])
         times += 1
+    out.update(extra or {})
     os.makedirs(f"./solutions/WOA/{dataset}/", exist_ok=True)
     with open(f"./solutions/WOA/{dataset}//{name}", "w") as f:                                # :294-296
         json.dump(out, f)

@@ -11,34 +11,52 @@
 // count of real services are carried wave-uniformly across j; a lane multiplies its own row onto the prefix and continues both
 // chains through cur[j+1 .. T-1] (every lane reads the same LDS address: broadcasts), and forms np.sum of column 0 in numpy's
 // order with element j replaced.  No atomics, no waits on other workgroups; every loop is bounded by max_sweeps, T or a list length.
+//
+// Pair-swap descent (descend_pairs_kernel) goes on from the one-swap optimum: a swap that breaks a product bound costs +1 and is
+// never taken alone, even where a second swap restores the bound.  A pair sweep tries, for every two slots, every pair of their
+// candidates (one pair per lane, the same carried prefix, two rows replaced), and the one-swap sweeps run again after a sweep that
+// moved — the same sweeps, not a second statement of them (tests/pair_descent_reference.py is its Python restatement).
 #include "woa_eval.h"
 
 #include <climits>
 
 namespace {
-// What a slot's candidates share: the smallest (min1, at `owner`) and second smallest (min2) entry of column 1 and the number of
-// real services (column 0 > 0) of the current composition.  Thread-uniform: every thread scans the same LDS columns.
+// What a slot's candidates share: the smallest (min1, at `owner`), second smallest (min2, at `owner2`) and third smallest (min3)
+// entry of column 1 and the number of real services (column 0 > 0) of the current composition.  Thread-uniform: every thread scans
+// the same LDS columns.  The one-swap sweeps use min1 / min2 / owner; the pair sweep takes two slots out and needs all five.
 struct Carried {
-    double min1, min2;
-    int owner, n_real;
+    double min1, min2, min3;
+    int owner, owner2, n_real;
     __device__ void scan(const double* col0, const double* col1, int T) {
-        min1 = min2 = INFINITY;
-        owner = -1;
+        min1 = min2 = min3 = INFINITY;
+        owner = owner2 = -1;
         n_real = 0;
         for (int i = 0; i < T; ++i) {
             const double v = col1[i];
             if (v < min1) {
+                min3 = min2;
                 min2 = min1;
+                owner2 = owner;
                 min1 = v;
                 owner = i;
             } else if (v < min2) {
+                min3 = min2;
                 min2 = v;
+                owner2 = i;
+            } else if (v < min3) {
+                min3 = v;
             }
             n_real += col0[i] > 0.0;
         }
     }
     __device__ __forceinline__ double min_with(int j, double q1) const { return fmin(owner == j ? min2 : min1, q1); }
     __device__ __forceinline__ int real_with(double old0, double q0) const { return n_real - (old0 > 0.0) + (q0 > 0.0); }
+    // np.min of column 1 without slots i != j: the smallest entry neither of them owns (callers fmin their two new entries onto it)
+    __device__ __forceinline__ double min_without(int i, int j) const {
+        const double m1 = min1, m2 = min2, m3 = min3;                 // read first: the choice is among values, not addresses
+        const bool out1 = owner == i || owner == j, out2 = owner2 == i || owner2 == j;
+        return out1 ? (out2 ? m3 : m2) : m1;
+    }
 };
 
 // (value, position) order: the smaller merit, the lower position among equals.  A NaN merit never enters (callers keep +inf for it).
@@ -69,23 +87,43 @@ struct DescendMem {
     double* table;     // [n_cand][4]
 };
 
-// The search, once, by the NT threads of a problem's workgroup: thread = one candidate of the current slot.  TABLE_IN_LDS: the
-// problem's candidate table is copied to M.table and cur is LDS too (else the table stays in global memory and cur IS the output
-// row).  NT = 64 is one wave whose columns are [4][64]: at most 64 slots, so np.sum is always one leaf and nothing crosses waves.
-// Above 128 slots np.sum follows numpy's recursion: only the block of at most 128 terms that holds slot j changes with the
-// candidate, so a thread sums that block with its own value in it and adds the sums of the untouched sibling blocks (`sib`, formed
-// once per slot by pw_sum) on the way up, deepest first — the same additions as the recursion (a + b rounds as b + a).
+// The lane form's carve-up (descend_lds_bytes sizes it): the four columns of cur [4][64] (figure_of_merit's layout), bounds [4],
+// base / len / cur [64] each, the problem's candidate table [n_cand][4].
+__device__ __forceinline__ DescendMem lane_mem(unsigned char* lds_raw) {
+    double* col = reinterpret_cast<double*>(lds_raw);
+    int* tab = reinterpret_cast<int*>(col + 260);
+    DescendMem M;
+    M.L = WideLds{col, col + 128, col + 192, nullptr, nullptr, tab, tab + 64, col + 256};
+    M.col1 = col + 64;
+    M.sib = nullptr;
+    M.cur = tab + 128;
+    M.table = reinterpret_cast<double*>(tab + 192);
+    return M;
+}
+
+// A problem's search state between the three parts below, thread-uniform: its slot count, its candidate table (LDS or global), the
+// current composition's merit and what its slots' candidates share.  The composition itself is M.cur and the columns in LDS.
+struct DescendState {
+    int T;
+    const double* cand;
+    double fit;
+    Carried cr;
+};
+
+// The search in three parts, each by the NT threads of a problem's workgroup — load and validate, one-swap sweeps from the state in
+// LDS, write the outputs — which descend_problem (both one-swap kernels) and descend_pairs_kernel call.  TABLE_IN_LDS: the problem's
+// candidate table is copied to M.table and cur is LDS too (else the table stays in global memory and cur IS the output row).
+// NT = 64 is one wave whose columns are [4][64]: at most 64 slots, so np.sum is always one leaf and nothing crosses waves.
+
+// Part 1: validates the problem's lists and start, fills the LDS tables, forms the start's merit (-> start_fitness) and `Carried`.
+// False: the problem is not searched and nothing but L.base / L.len was touched; the caller writes what such a problem leaves.
 template <int NT, bool TABLE_IN_LDS>
-__device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
-                                                const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
-                                                const int32_t* __restrict__ start_pos, int32_t max_sweeps,
-                                                double* __restrict__ best_fitness, double* __restrict__ start_fitness,
-                                                int32_t* __restrict__ best_pos_out, double* __restrict__ history,
-                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
+__device__ __forceinline__ bool descend_load(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+                                             const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                             const int32_t* __restrict__ start_pos, double* __restrict__ start_fitness, DescendState& S) {
     constexpr bool WAVES = NT > 64;
     const WideLds& L = M.L;
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hist_ld = max_sweeps > 1 ? max_sweeps : 1;           // history has at least one entry per problem
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int T = sh.count(p);
     const size_t s0 = sh.first(p);
     const bool fits = sh.fits(p, T);
@@ -102,10 +140,7 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
     }
     if constexpr (WAVES) bad = __syncthreads_or(bad);
     else bad = __any(bad);
-    if (bad) {
-        not_searched(p, tid, NT, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
-        return;
-    }
+    if (bad) return false;
     const double* cand = cand_g + (size_t)c0 * 4;
     if constexpr (TABLE_IN_LDS) {
         for (int i = tid; i < n_cand * 4; i += NT) M.table[i] = cand[i];
@@ -127,10 +162,28 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
         fit = figure_of_merit(q, T, lane, L.col0, L.bounds);
     }
     if (tid == 0) start_fitness[p] = fit;
-    Carried cr;
-    cr.scan(L.col0, M.col1, T);
+    S.T = T;
+    S.cand = cand;
+    S.fit = fit;
+    S.cr.scan(L.col0, M.col1, T);
+    return true;
+}
 
-    int sweeps = 0, moves = 0;
+// Part 2: up to max_sweeps one-swap sweeps from the state in LDS, thread = one candidate of the current slot; adds to `sweeps` and
+// `moves`, `settled` = the last sweep moved nothing (unchanged where max_sweeps = 0); hist (or NULL) takes the merit after every sweep.
+// Above 128 slots np.sum follows numpy's recursion: only the block of at most 128 terms that holds slot j changes with the
+// candidate, so a thread sums that block with its own value in it and adds the sums of the untouched sibling blocks (`sib`, formed
+// once per slot by pw_sum) on the way up, deepest first — the same additions as the recursion (a + b rounds as b + a).
+template <int NT>
+__device__ __forceinline__ void one_swap_sweeps(const DescendMem& M, DescendState& S, int32_t max_sweeps, double* __restrict__ hist,
+                                                int& sweeps, int& moves, bool& settled) {
+    constexpr bool WAVES = NT > 64;
+    const WideLds& L = M.L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = S.T;
+    const double* cand = S.cand;
+    double fit = S.fit;
+    Carried cr = S.cr;
     for (int s = 0; s < max_sweeps; ++s) {
         bool improved = false;
         double pre2 = 1.0, pre3 = 1.0;                                // np.cumprod of columns 2 and 3 up to slot j - 1
@@ -205,10 +258,20 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
             pre3 = j == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[j]);
         }
         ++sweeps;
-        if (tid == 0) history[(size_t)p * hist_ld + s] = fit;
+        settled = !improved;
+        if (hist && tid == 0) hist[s] = fit;
         if (!improved) break;
     }
-    for (int s = sweeps + tid; s < hist_ld; s += NT) history[(size_t)p * hist_ld + s] = fit;       // max_sweeps = 0: the start
+    S.fit = fit;
+    S.cr = cr;
+}
+
+// Part 3: the composition in LDS and its merit to best_pos / best_rows / best_fitness.
+template <int NT, bool TABLE_IN_LDS>
+__device__ __forceinline__ void descend_store(const DescendMem& M, const Shape& sh, const DescendState& S,
+                                              double* __restrict__ best_fitness, int32_t* __restrict__ best_pos_out) {
+    const WideLds& L = M.L;
+    const int p = blockIdx.x, tid = threadIdx.x, T = S.T;
     double* rows = sh.rows_out(p);
     for (int j = tid; j < T; j += NT) {
         if constexpr (TABLE_IN_LDS) best_pos_out[sh.out_row(p) + j] = M.cur[j];
@@ -219,11 +282,100 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
             rows[(size_t)j * 4 + 3] = L.col3[j];
         }
     }
+    if (tid == 0) best_fitness[p] = S.fit;
+}
+
+// One-swap descent: the three parts, the history tail and the counters.
+template <int NT, bool TABLE_IN_LDS>
+__device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+                                                const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                double* __restrict__ best_fitness, double* __restrict__ start_fitness,
+                                                int32_t* __restrict__ best_pos_out, double* __restrict__ history,
+                                                int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int hist_ld = max_sweeps > 1 ? max_sweeps : 1;           // history has at least one entry per problem
+    DescendState S;
+    if (!descend_load<NT, TABLE_IN_LDS>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, start_fitness, S)) {
+        not_searched(p, tid, NT, best_fitness, start_fitness, history, hist_ld, sweeps_out, moves_out);
+        return;
+    }
+    int sweeps = 0, moves = 0;
+    bool settled = false;
+    double* hist = history + (size_t)p * hist_ld;
+    one_swap_sweeps<NT>(M, S, max_sweeps, hist, sweeps, moves, settled);
+    for (int s = sweeps + tid; s < hist_ld; s += NT) hist[s] = S.fit;                               // max_sweeps = 0: the start
+    descend_store<NT, TABLE_IN_LDS>(M, sh, S, best_fitness, best_pos_out);
     if (tid == 0) {
-        best_fitness[p] = fit;
         sweeps_out[p] = sweeps;
         moves_out[p] = moves;
     }
+}
+
+// One pair sweep from the state in LDS by ONE wave (lane form): for every slot pair i < j in order, lanes stride over k = a * len_j + b
+// — the composition with slots i and j replaced by candidates a and b of their lists, current members included — lowest k first,
+// each keeping its best under strict <; the wave's argmin is by (value, k); the pair is taken if it is strictly below the current
+// merit.  A lane continues the carried prefix pre2 / pre3 (np.cumprod up to slot i - 1) with row a, cur[i+1 .. j-1], row b,
+// cur[j+1 .. T-1], one __dmul_rn each: numpy's order.  Returns the number of pairs taken.  Bounded by T and list lengths.
+__device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S) {
+    const WideLds& L = M.L;
+    const int lane = threadIdx.x, T = S.T;
+    const double* cand = S.cand;
+    int taken = 0;
+    double pre2 = 1.0, pre3 = 1.0;
+    for (int i = 0; i < T; ++i) {
+        const int bi = L.base[i], li = L.len[i];
+        for (int j = i + 1; j < T; ++j) {
+            const int bj = L.base[j], lj = L.len[j], n = li * lj;
+            const double rest_min = S.cr.min_without(i, j);
+            const int rest_real = S.cr.n_real - (L.col0[i] > 0.0) - (L.col0[j] > 0.0);
+            double bf = INFINITY;
+            int bk = INT_MAX;
+            for (int k = lane; k < n; k += 64) {                       // products beyond a wave: chunks, lowest k first
+                const int a = k / lj, b = k - a * lj;
+                const double* ra = cand + (size_t)(bi + a) * 4;
+                const double* rb = cand + (size_t)(bj + b) * 4;
+                const double a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
+                double p2 = i == 0 ? ra[2] : __dmul_rn(pre2, ra[2]), p3 = i == 0 ? ra[3] : __dmul_rn(pre3, ra[3]);
+                for (int m = i + 1; m < j; ++m) {
+                    p2 = __dmul_rn(p2, L.col2[m]);
+                    p3 = __dmul_rn(p3, L.col3[m]);
+                }
+                p2 = __dmul_rn(p2, rb[2]);
+                p3 = __dmul_rn(p3, rb[3]);
+                for (int m = j + 1; m < T; ++m) {
+                    p2 = __dmul_rn(p2, L.col2[m]);
+                    p3 = __dmul_rn(p3, L.col3[m]);
+                }
+                const double sum = pw_leaf_swapped(L.col0, T, i, a0, j, b0);
+                const int n_real = rest_real + (a0 > 0.0) + (b0 > 0.0);
+                const double f = merit_of(sum, n_real, fmin(fmin(rest_min, a1), b1), p2, p3, L.bounds);
+                if (f < bf) {
+                    bf = f;
+                    bk = k;
+                }
+            }
+            wave_argmin(bf, bk, lane);
+            if (bf < S.fit) {                                          // wave-uniform
+                if (lane == 0) {
+                    const int a = bk / lj, b = bk - a * lj;
+                    const double* ra = cand + (size_t)(bi + a) * 4;
+                    const double* rb = cand + (size_t)(bj + b) * 4;
+                    M.cur[i] = a;
+                    M.cur[j] = b;
+                    L.col0[i] = ra[0]; M.col1[i] = ra[1]; L.col2[i] = ra[2]; L.col3[i] = ra[3];
+                    L.col0[j] = rb[0]; M.col1[j] = rb[1]; L.col2[j] = rb[2]; L.col3[j] = rb[3];
+                }
+                S.fit = bf;
+                ++taken;
+                __syncthreads();
+                S.cr.scan(L.col0, M.col1, T);
+            }
+        }
+        pre2 = i == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[i]);
+        pre3 = i == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[i]);
+    }
+    return taken;
 }
 }  // namespace
 
@@ -237,16 +389,62 @@ __global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __
                                                      double* __restrict__ history, int32_t* __restrict__ sweeps_out,
                                                      int32_t* __restrict__ moves_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    double* col = reinterpret_cast<double*>(lds_raw);
-    int* tab = reinterpret_cast<int*>(col + 260);
-    DescendMem M;
-    M.L = WideLds{col, col + 128, col + 192, nullptr, nullptr, tab, tab + 64, col + 256};
-    M.col1 = col + 64;
-    M.sib = nullptr;
-    M.cur = tab + 128;
-    M.table = reinterpret_cast<double*>(tab + 192);
-    descend_problem<64, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness, best_pos_out, history,
-                              sweeps_out, moves_out);
+    descend_problem<64, true>(lane_mem(lds_raw), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness,
+                              best_pos_out, history, sweeps_out, moves_out);
+}
+
+// ---- pair-swap descent, lane form only: one wavefront per problem (<= 64 slots), descend_kernel's LDS layout ------------------------------
+// Phase 0 = the one-swap sweeps; then up to max_rounds rounds of one pair sweep and, where it moved, the one-swap sweeps again.  A round
+// whose pair sweep moved nothing is the last (it is counted).  round_history[r] = the merit after round r, past the last round the final
+// value (max_rounds = 0: its one entry is phase 0's merit); converged = the last pair sweep moved nothing and the last one-swap phase
+// ended with a sweep that moved nothing.  No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths.
+struct PairOut {
+    double* best_fitness; double* start_fitness; int32_t* best_pos; double* round_history;
+    int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged;
+};
+
+__global__ __launch_bounds__(64) void descend_pairs_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
+                                                           const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
+                                                           int32_t max_sweeps, int32_t max_rounds, PairOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const DescendMem M = lane_mem(lds_raw);
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int rh_ld = max_rounds > 1 ? max_rounds : 1;             // round_history has at least one entry per problem
+    double* rh = o.round_history + (size_t)p * rh_ld;
+    DescendState S;
+    if (!descend_load<64, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, o.start_fitness, S)) {
+        not_searched(p, lane, 64, o.best_fitness, o.start_fitness, o.round_history, rh_ld, o.sweeps, o.moves);
+        if (lane == 0) {
+            o.rounds[p] = -1;
+            o.pair_moves[p] = 0;
+            o.converged[p] = 0;
+        }
+        return;
+    }
+    int sweeps = 0, moves = 0, rounds = 0, pair_moves = 0;
+    bool settled = false, still = false;                           // still: the last pair sweep moved nothing
+    one_swap_sweeps<64>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+    while (rounds < max_rounds) {
+        const int taken = pair_sweep(M, S);
+        pair_moves += taken;
+        still = taken == 0;
+        if (!still) {
+            settled = false;                                       // max_sweeps = 0: no sweep follows the move
+            one_swap_sweeps<64>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+        }
+        if (lane == 0) rh[rounds] = S.fit;
+        ++rounds;
+        if (still) break;
+    }
+    for (int r = rounds + lane; r < rh_ld; r += 64) rh[r] = S.fit;
+    descend_store<64, true>(M, sh, S, o.best_fitness, o.best_pos);
+    if (lane == 0) {
+        o.sweeps[p] = sweeps;
+        o.moves[p] = moves;
+        o.rounds[p] = rounds;
+        o.pair_moves[p] = pair_moves;
+        o.converged[p] = still && settled;
+    }
 }
 
 // ---- workgroup form: any slot count, 256 threads per problem ----------------------------------------------------------------------------
@@ -296,6 +494,29 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
     return search_launch(lds, too_large, use_wide ? descend_wide_kernel : descend_kernel, B, use_wide ? WNT : 64, stream,
                          use_wide ? "descend_ragged_f64 (workgroup form)" : "descend_ragged_f64", sh, cand_ptr, cand, bounds, start_pos,
                          max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
+}
+
+extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                              const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                              int32_t max_sweeps, int32_t max_rounds, double* best_fitness, double* start_fitness,
+                                              int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
+                                              int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_slots >= 1, "descend_pairs_ragged: bad argument");
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
+                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_ragged: null operand");
+    if (max_slots > 64)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
+                   "gnnpn_descend_ragged_f64 descends larger problems by single swaps", max_slots);
+    if (max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: max_cand must be >= 1 (it sizes the table in LDS)");
+    const size_t lds = descend_lds_bytes(max_cand);
+    auto too_large = [&]() -> int {
+        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: %zu B of LDS per problem (%d candidates) exceed a CU", lds, max_cand);
+    };
+    const Shape sh{prob_ptr, 0, max_slots, 64, max_cand, n_lists, best_rows};
+    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
+    return search_launch(lds, too_large, descend_pairs_kernel, B, 64, stream, "descend_pairs_ragged_f64", sh, cand_ptr, cand, bounds,
+                         start_pos, max_sweeps, max_rounds, o);
 }
 
 

@@ -47,8 +47,9 @@ __device__ double pw_leaf(const double* a, int n, int lane) {
     for (int i = body; i < n; ++i) sum = __dadd_rn(sum, a[i]);
     return sum;
 }
-__device__ double pw_leaf_swapped(const double* a, int n, int jj, double v) {
-    auto at = [&](int i) { return i == jj ? v : a[i]; };
+// pw_leaf_swapped: a[jj] replaced by v and a[kk] by w (kk < 0: one element only).
+__device__ __forceinline__ double pw_leaf_swapped(const double* a, int n, int jj, double v, int kk, double w) {
+    auto at = [&](int i) { return i == jj ? v : i == kk ? w : a[i]; };
     if (n < 8) {
         double s = at(0);
         for (int i = 1; i < n; ++i) s = __dadd_rn(s, at(i));
@@ -66,6 +67,7 @@ __device__ double pw_leaf_swapped(const double* a, int n, int jj, double v) {
     for (int i = body; i < n; ++i) s = __dadd_rn(s, at(i));
     return s;
 }
+__device__ double pw_leaf_swapped(const double* a, int n, int jj, double v) { return pw_leaf_swapped(a, n, jj, v, -1, 0.0); }
 
 // violate + objFunc of the composition whose category-j row is (q[0..3]) in lane j (lanes >= T idle).
 // `col` = 4 x 64 doubles of LDS scratch, which holds the composition's four columns afterwards.

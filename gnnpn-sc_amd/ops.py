@@ -1288,6 +1288,35 @@ def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, m
     return out
 
 
+def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_slots=None, max_cand=None):
+    """Pair-swap descent, a ragged batch in ONE launch (gnnpn_descend_pairs_ragged_f64): descend_ragged's one-swap descent, then up
+    to ``max_rounds`` rounds of one pair sweep — for every slot pair i < j in order the best (a, b) of their two lists, the lowest
+    among equals, taken while it strictly lowers violate + objFunc — each followed, where it moved, by the one-swap descent again; a
+    round whose pair sweep moves nothing is the last.  Operands as descend_ragged; at most 64 slots per problem (GnnpnError names
+    descend_ragged's entry otherwise).  Returns a dict of device tensors: best_fitness, start_fitness [B] f64, best_pos
+    [B, max_slots] i32 and best_rows [B, max_slots, 4] f64 (0 past a problem's count), round_history [B, max(max_rounds, 1)] f64 (the
+    merit after every round; past the last round the final value; max_rounds = 0: phase 0's merit), sweeps and moves [B] i32 (all
+    one-swap phases together), rounds, pair_moves [B] i32, converged [B] i32 (1: no single swap and no pair swap lowers the result)."""
+    dev = cand.device
+    B = prob_ptr.numel() - 1
+    n = cand_ptr.numel() - 1
+    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or int(max_rounds) < 0:
+        raise GnnpnError("descend_pairs_ragged: inconsistent operand sizes")
+    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
+    out = _descent_fields(B, max_slots, max(int(max_rounds), 1), dev, rows=torch.zeros)
+    out["round_history"] = out.pop("history")
+    out.update({k: torch.empty(B, dtype=I32, device=dev) for k in ("rounds", "pair_moves", "converged")})
+    check(_lib.load().gnnpn_descend_pairs_ragged_f64(
+        B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
+        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), int(max_rounds),
+        dev_ptr(out["best_fitness"], F64, "best_fitness"), dev_ptr(out["start_fitness"], F64, "start_fitness"),
+        dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"),
+        dev_ptr(out["round_history"], F64, "round_history"), dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"),
+        dev_ptr(out["rounds"], I32, "rounds"), dev_ptr(out["pair_moves"], I32, "pair_moves"), dev_ptr(out["converged"], I32, "converged"),
+        stream_ptr()), "gnnpn_descend_pairs_ragged_f64")
+    return out
+
+
 def descend_select(res, actions_all, n_slots):
     """Per problem, the replica whose descent ended lowest (gnnpn_descend_select_f64).  ``res``: descend_ragged's dict over B * R
     rows, row b * R + r = replica r of problem b; actions_all [B, R, T', 8] f32 or f64: the rows the replicas started from;

@@ -139,9 +139,19 @@ def _quality(res, min_cost, dev):
     return res
 
 
-def _descend_tables(tabs, max_sweeps):
-    res = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
-                             max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+def _descend_tables(tabs, max_sweeps, pair_rounds=None):
+    """One-swap descent over the tables, or (pair_rounds an int, 0 included) pair-swap descent with that many rounds allowed."""
+    if pair_rounds is not None:
+        if int(pair_rounds) < 0:
+            raise ops.GnnpnError(f"descend_pairs: the number of rounds must be >= 0, got {pair_rounds}")
+        if tabs["max_slots"] > 64:
+            raise ops.GnnpnError(f"descend_pairs: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
+                                 "per problem (descend runs one-swap descent at any slot count)")
+        res = ops.descend_pairs_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
+                                       int(pair_rounds), max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+    else:
+        res = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
+                                 max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
     res["n_slots"] = tabs["n_slots"]
     return res
 
@@ -161,6 +171,22 @@ def descend(services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patche
 
 
 @torch.no_grad()
+def descend_pairs(services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, min_cost=None, patches=()):
+    """Pair-swap descent of ``out["actions"]`` on the device: ``descend``'s tables and one-swap descent, then up to ``max_rounds``
+    rounds of one pair sweep (every two slots, every pair of their candidates, the best taken while it strictly lowers violate +
+    objFunc) and the one-swap descent again (gnnpn_descend_pairs_ragged_f64; all problems in one launch, deterministic).  It leaves
+    the one-swap optima behind a +1 wall: a swap that breaks a product bound which a second swap restores.  At most 64 slots per
+    problem: a larger one raises GnnpnError (``descend`` takes any).  ``ML2PNPipeline.descend_pairs`` is this, as a method.  Returns
+    ops.descend_pairs_ragged's dict (best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds,
+    pair_moves, converged) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness).  ``max_rounds`` = 0: ``descend``'s
+    result in every shared field."""
+    actions = out["actions"]
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    return _quality(_descend_tables(tabs, max_sweeps, max_rounds), min_cost, actions.device)
+
+
+@torch.no_grad()
 def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
     """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
     [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
@@ -172,6 +198,21 @@ def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=No
     method.  Returns ``descend``'s keys for the winners plus start_index [B] i32, actions [B, T', 8] (the winner's start rows:
     ``refine(services, batch, res, ..., descend=k)`` rebuilds its tables and repeats its descent before ES-WOA), fitness_all and
     start_fitness_all [B, N] f64, sweeps_all and moves_all [B, N] i32 (and quality [B] f64 = min_cost / best_fitness)."""
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, 0)
+
+
+@torch.no_grad()
+def descend_starts_pairs(services, batch, starts, max_sweeps=16, pair_rounds=4, reduct=0, min_cost=None, patches=()):
+    """``descend_starts`` with pair-swap descent per row.  ``pair_rounds`` = r > 0: the B * N rows go through pair-swap descent
+    with r rounds allowed (gnnpn_descend_pairs_ragged_f64 in place of the descent launch; at most 64 slots per problem); the
+    same selection (gnnpn_descend_select_f64, unchanged) picks the winner, the result has round_history in place of history and
+    gains rounds, pair_moves and converged [B] i32 (the winner's, gathered by start_index) and rounds_all, pair_moves_all [B, N] i32.
+    ``pair_rounds`` = 0 is ``descend_starts``: the same launches, the same result.  ``descend_starts`` itself keeps its
+    signature, which is why this is a function of its own.  ``ML2PNPipeline.descend_starts_pairs`` is this, as a method."""
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, int(pair_rounds))
+
+
+def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pair_rounds):
     all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
     if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
         raise ops.GnnpnError(f"descend_starts: starts [B, N, T, 8|9] expected, got {tuple(getattr(all_rows, 'shape', ()))}")
@@ -179,16 +220,23 @@ def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=No
     B, N = all_rows.shape[:2]
     tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                                        all_rows, reduct=reduct, patches=patches)
-    per_row = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
-                                 max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+    per_row = _descend_tables(tabs, max_sweeps, int(pair_rounds) if pair_rounds else None)
+    if pair_rounds:                                               # the selection copies the rounds' merits as it does the sweeps'
+        per_row["history"] = per_row.pop("round_history")
     res = ops.descend_select(per_row, all_rows, tabs["n_slots"])
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
+    if pair_rounds:
+        res["round_history"] = res.pop("history")
+        win = res["start_index"].long()[:, None]
+        for key in ("rounds", "pair_moves", "converged"):
+            res[key] = per_row[key].view(B, N).gather(1, win)[:, 0]
+        res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
     return _quality(res, min_cost, all_rows.device)
 
 
 @torch.no_grad()
-def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=(), descend=0):
+def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_cost=None, patches=(), descend=0, pair_rounds=0):
     """The third stage: ES-WOA refinement of ``out["actions"]`` (what ``run`` returned, or any mapping with an actions
     tensor [B,T,8], float32 or float64) on the device — the candidate lists of every problem built from ``services`` /
     ``batch`` (gnnpn_woa_candidates_count / _fill: loadDataOther + WOA._prepare, bit for bit) and the search of every problem
@@ -198,7 +246,9 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
     Returns device tensors: best_fitness [B] f64, best_rows [B, max_slots, 4] f64, n_slots [B] i32, best_pos
     [B, max_slots] i32 (negative: Python list positions), history [B, MAX_Iter] f64, draws [B] i64 (and quality [B] f64).
     ``descend`` = k > 0: the tables are built once, one-swap descent runs up to k sweeps on them (``descend`` above) and ES-WOA
-    starts from descent's best_pos in place of start_pos; the result gains ``descent`` (the descent's dict)."""
+    starts from descent's best_pos in place of start_pos; the result gains ``descent`` (the descent's dict).  ``pair_rounds`` = r > 0
+    (with or without ``descend``, which then allows 0 sweeps): pair-swap descent with r rounds allowed in place of the one-swap
+    descent (``descend_pairs``), ``descent`` is its dict."""
     actions = out["actions"]
     dev = actions.device
     B = batch.n_problems
@@ -210,8 +260,8 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
         seeds = torch.from_numpy(np.asarray(seeds, dtype=np.uint64).reshape(B).view(np.int64).copy())
     seeds = seeds.to(device=dev, dtype=torch.int64).contiguous()
     start_pos, descent = tabs["start_pos"], None
-    if descend:
-        descent = _quality(_descend_tables(tabs, int(descend)), min_cost, dev)
+    if descend or pair_rounds:
+        descent = _quality(_descend_tables(tabs, int(descend), int(pair_rounds) if pair_rounds else None), min_cost, dev)
         # a problem's slots are rows prob_ptr[p] .. of the flat tables and the first n_slots[p] entries of its best_pos row
         slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
         start_pos = descent["best_pos"][slots].contiguous()
@@ -336,6 +386,17 @@ class ML2PNPipeline:
         """Multi-start descent from ``best_of(..., return_all=True)``'s replicas (or any [B, N, T, 8|9] rows): module-level
         ``descend_starts`` (it needs no network).  An extra call: ``run`` / ``capture`` are unchanged."""
         return descend_starts(services, batch, starts, max_sweeps=max_sweeps, reduct=reduct, min_cost=min_cost, patches=patches)
+
+    def descend_pairs(self, services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, min_cost=None, patches=()):
+        """Pair-swap descent of ``out["actions"]`` on the device: module-level ``descend_pairs`` (it needs no network).  An extra
+        call: ``run`` / ``capture`` are unchanged."""
+        return descend_pairs(services, batch, out, max_sweeps=max_sweeps, max_rounds=max_rounds, reduct=reduct, min_cost=min_cost,
+                             patches=patches)
+
+    def descend_starts_pairs(self, services, batch, starts, max_sweeps=16, pair_rounds=4, reduct=0, min_cost=None, patches=()):
+        """Multi-start pair-swap descent: module-level ``descend_starts_pairs`` (it needs no network).  An extra call."""
+        return descend_starts_pairs(services, batch, starts, max_sweeps=max_sweeps, pair_rounds=pair_rounds, reduct=reduct,
+                                    min_cost=min_cost, patches=patches)
 
     def capture(self, services, batch, warmup=2, decode_impl=0, lds_kb=0, ws=None, paired_start=False, pool=None, write_through=False):
         """Record one whole pass over (services, batch) into a HIP graph and return a callable that

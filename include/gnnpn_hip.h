@@ -797,6 +797,36 @@ int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists
                              int32_t max_sweeps, int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos,
                              double* best_rows, double* history, int32_t* sweeps, int32_t* moves, void* stream);
 
+/* Pair-swap descent: one-swap descent, then exchanges of two slots at once, a ragged batch in one launch (csrc/descend.hip).  New: no
+ * reference counterpart.  A single swap that breaks a product bound costs +1 in violate + objFunc and is never taken by
+ * gnnpn_descend_ragged_f64, even where a second swap in another slot restores the bound and the two together are better; this entry
+ * searches that neighbourhood.  Operand meanings are gnnpn_descend_ragged_f64's.  Per problem with T lists:
+ *   phase 0: gnnpn_descend_ragged_f64's search, up to max_sweeps sweeps (start_fitness, and the first sweeps / moves);
+ *   up to max_rounds rounds: ONE pair sweep — for i = 0 .. T-2, j = i+1 .. T-1 in order, f_ab = merit(cur with slot i := a, slot j := b)
+ *   for EVERY (a, b) of lists i and j, current members included; (a*, b*) = the smallest f_ab, the lowest a * len_j + b among equals;
+ *   if f_a*b* < fit (strictly): cur[i] = a*, cur[j] = b*, fit = f_a*b*, one more pair move — then, if the sweep moved, the one-swap
+ *   sweeps again from there (up to max_sweeps; sweeps / moves accumulate).  round_history[r] = fit after round r; a round whose pair
+ *   sweep moved nothing is the last (it is counted); round_history past the last round repeats the final value.
+ * merit and comparisons as gnnpn_descend_ragged_f64: bit for bit numpy's float64 orders, plain <, a NaN never wins.  max_rounds = 0
+ * is gnnpn_descend_ragged_f64's result in every shared field; max_sweeps = 0 means pair sweeps only.
+ * Outputs: best_fitness, start_fitness [B], best_pos [B, max_slots], best_rows [B, max_slots, 4] or NULL, round_history
+ * [B, max(max_rounds, 1)] (every entry written: with max_rounds = 0 its one entry is phase 0's merit), sweeps, moves, rounds,
+ * pair_moves [B], converged [B]: 1 iff the last pair sweep moved nothing and the last one-swap phase ended with a sweep that moved
+ * nothing (no single swap and no pair swap lowers the result), else 0.  A problem that is not searched (as in
+ * gnnpn_descend_ragged_f64's lane form: no list, more than max_slots or 64 lists, more than max_cand candidates, entries past n_lists,
+ * an empty list, a start outside its list) leaves what descent leaves — best_fitness and start_fitness NaN, sweeps -1, moves 0 — and
+ * rounds -1, pair_moves 0, converged 0, its round_history row NaN.
+ * One wavefront per problem, the problem's table in LDS (the lane form only); no atomics, no waits on other workgroups, every loop
+ * bounded by max_rounds, max_sweeps, T or a list length.  GNNPN_E_ARG: negative sizes, max_slots < 1, null operands.  GNNPN_E_UNSUP,
+ * nothing launched: max_slots > 64 (gnnpn_descend_ragged_f64 descends such problems by single swaps); max_cand < 1; the table's
+ * LDS bytes (32 per candidate) beyond a CU.  That cap (about 4900 candidates per problem) is also what bounds a pair sweep: at most
+ * about max_cand^2 / 2 evaluations per problem, and far fewer where the candidates are spread over several lists. */
+int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                   const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                   int32_t max_sweeps, int32_t max_rounds, double* best_fitness, double* start_fitness,
+                                   int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
+                                   int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream);
+
 /* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
  * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
  * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest

@@ -26,6 +26,13 @@
                                          # ES-WOA starts from the winner.  Needs --samples=N (N > 1) and --descend; the PNHigh
                                          # artefact stays the best-of winner by R
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] --pairs[=ROUNDS] [--samples=N --all-starts] [--woa]   # pair-swap descent:
+                                         # after the one-swap descent, exchange two slots at once while that helps (4 rounds at most
+                                         # unless given), re-descending after every round that moved:
+                                         # ./solutions/WOA/<ds>/ML+2PN+pairs.txt (with --all-starts ML+2PN+multistart+pairs.txt) in
+                                         # place of the descent artefact, the same format plus rounds / pair_moves / converged;
+                                         # with --woa ES-WOA starts from the pair-descended composition
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -180,6 +187,10 @@ def main(argv):
         if "--all-starts" in flags and (samples is None or int(samples) < 2 or sweeps is None):
             print("--all-starts: needs --samples=N (N > 1) and --descend[=SWEEPS]")
             return 1
+        rounds = next((a.split("=", 1)[1] if "=" in a else "4" for a in flags if a == "--pairs" or a.startswith("--pairs=")), None)
+        if rounds is not None and (sweeps is None or int(rounds) < 1):
+            print("--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round")
+            return 1
         with open(f"./data/{ds}/serviceFeature.data") as f:
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
@@ -202,6 +213,8 @@ def main(argv):
             best["descend"] = int(sweeps)
         if "--all-starts" in flags:                                 # descent from every best-of-N replica, the lowest optimum kept
             best["all_starts"] = True
+        if rounds is not None:                                      # pair-swap descent in place of the one-swap descent
+            best["pair_rounds"] = int(rounds)
         ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
