@@ -159,30 +159,23 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     written = None
     # each file books the time of its own stages: descent.txt the tables + descent, WOA.txt the tables (+ descent) + ES-WOA.  With
     # both, descent therefore runs twice (it is deterministic and costs about a hundredth of the ES-WOA run beside it).
-    if descend is not None and starts is not None:
+    if descend is not None:
+        multi, pairs = starts is not None, pair_rounds is not None        # from every start or the actions; pair-swap or one-swap
+        name = {(False, False): "ML+2PN+descent.txt", (False, True): "ML+2PN+pairs.txt", (True, False): "ML+2PN+multistart.txt",
+                (True, True): "ML+2PN+multistart+pairs.txt"}[multi, pairs]
+        kw = {"max_sweeps": descend, "reduct": reduct, "min_cost": min_cost}
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
-        if pair_rounds is None:
-            multi = descend_starts(svc, batch, rows, max_sweeps=descend, reduct=reduct, min_cost=min_cost)
+        if multi:
+            rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
+            res = descend_starts_pairs(svc, batch, rows, pair_rounds=pair_rounds, **kw) if pairs else descend_starts(svc, batch, rows, **kw)
         else:
-            multi = descend_starts_pairs(svc, batch, rows, max_sweeps=descend, pair_rounds=pair_rounds, reduct=reduct, min_cost=min_cost)
-        quality = multi["quality"].cpu().tolist()
-        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first,
-                                  name="ML+2PN+multistart.txt" if pair_rounds is None else "ML+2PN+multistart+pairs.txt",
-                                  extra=None if pair_rounds is None else counters(multi))
-        out = {"actions": multi["actions"]}          # refine below rebuilds the winner's tables and repeats its descent
-    elif descend is not None and pair_rounds is not None:
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        res = descend_pairs(svc, batch, out, max_sweeps=descend, max_rounds=pair_rounds, reduct=reduct, min_cost=min_cost)
+            res = descend_pairs(svc, batch, out, max_rounds=pair_rounds, **kw) if pairs else descend_actions(svc, batch, out, **kw)
         quality = res["quality"].cpu().tolist()
-        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+pairs.txt", extra=counters(res))
-    elif descend is not None:
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        quality = descend_actions(svc, batch, out, max_sweeps=descend, reduct=reduct, min_cost=min_cost)["quality"].cpu().tolist()
-        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name="ML+2PN+descent.txt")
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name,
+                                  extra=counters(res) if pairs else None)
+        if multi:
+            out = {"actions": res["actions"]}        # refine below rebuilds the winner's tables and repeats its descent
     if descend is None or popSize > 0:
         torch.cuda.synchronize(dev)
         t0 = time.time()

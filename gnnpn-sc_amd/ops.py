@@ -1119,6 +1119,31 @@ def woa_status_error(status, first, replicas=None):
                       f"{_WOA_STATUS.get(status, 'unknown status')}")
 
 
+class SearchTables(dict):
+    """The candidate tables of a batch as woa_candidates / woa_candidates_replicas return them: a dict of their keys whose
+    methods pass its own operands to the search wrappers below (nothing but forwarding: the wrappers do the checking)."""
+
+    def descend(self, max_sweeps=16, wide=None):
+        return descend_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
+                              max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
+
+    def descend_pairs(self, max_sweeps=16, max_rounds=4):
+        return descend_pairs_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
+                                    max_rounds, max_slots=self["max_slots"], max_cand=self["max_cand"])
+
+    def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
+        """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
+        return eswoa_ragged(self["prob_ptr"], self["cand_ptr"], self["len_init"], self["cand"], self["bounds"],
+                            self["start_pos"] if start_pos is None else start_pos, pop, max_iter, seeds,
+                            max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
+
+    def flat(self, best_pos):
+        """A [B, max_slots] i32 ``best_pos`` as flat [n_lists] positions (what start_pos is): a problem's slots are rows
+        prob_ptr[p] .. of the flat tables and the first n_slots[p] entries of its best_pos row."""
+        slots = torch.arange(self["max_slots"], device=best_pos.device)[None, :] < self["n_slots"][:, None]
+        return best_pos[slots].contiguous()
+
+
 def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches, check_status):
     """woa_candidates (``replicas`` None: the per-problem entries) and woa_candidates_replicas (``replicas`` True: the per-replica
     ones over B * R rows, R read from the actions)."""
@@ -1185,8 +1210,8 @@ def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bo
                dev_ptr(status, I32, "status"), dev_ptr(prob_ptr, I32, "prob_ptr"), n_lists, n_cand,
                dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(len_init, I32, "len_init"),
                dev_ptr(cand, F64, "cand"), dev_ptr(start_pos, I32, "start_pos"), stream_ptr()), entry + "_fill")
-    tabs = {"prob_ptr": prob_ptr, "n_slots": n_slots, "cand_ptr": cand_ptr, "len_init": len_init, "cand": cand,
-            "start_pos": start_pos, "bounds": bounds, "status": status, "max_slots": max_slots, "max_cand": max_cand}
+    tabs = SearchTables(prob_ptr=prob_ptr, n_slots=n_slots, cand_ptr=cand_ptr, len_init=len_init, cand=cand, start_pos=start_pos,
+                        bounds=bounds, status=status, max_slots=max_slots, max_cand=max_cand)
     if replicas is not None:
         tabs["replicas"] = R
     return tabs
@@ -1198,7 +1223,7 @@ def woa_candidates(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, action
     [B,4] f64 (DeviceBatch); actions [B,T',8] f32 or f64 (ML2PNPipeline.run's, or an artefact's rows); patches: WOA._prepare's
     (want 4-tuple, column, value) triples.  Two small copies to the host: the largest category (sizes the workspace) and the
     totals.  A problem the host path raises on raises GnnpnError naming it (``check_status=False``: returned in ``status``).
-    Returns a dict: prob_ptr [B+1], n_slots [B], cand_ptr [n+1], len_init [n], cand [m,4] f64, start_pos [n], bounds [B,4],
+    Returns a SearchTables (a dict): prob_ptr [B+1], n_slots [B], cand_ptr [n+1], len_init [n], cand [m,4] f64, start_pos [n], bounds [B,4],
     status [B] (device tensors) and max_slots, max_cand (ints)."""
     return _woa_tables("woa_candidates", None, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches,
                        check_status)
@@ -1262,6 +1287,32 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
           "gnnpn_eswoa_ragged_f64")
     return best_fit, best_pos, history[:, :int(max_iter)], draws, best_rows
 
+
+def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, middle, max_slots, max_cand, hist, hist_ld,
+                    extra=()):
+    """descend_ragged and descend_pairs_ragged: the C entry ``entry`` over the ten leading operands they share, ``middle`` the one
+    scalar behind max_sweeps (wide / max_rounds), the history under the key ``hist`` with max(hist_ld, 1) columns, ``extra`` the
+    names of the [B] i32 outputs behind the seven fields."""
+    dev = cand.device
+    B = prob_ptr.numel() - 1
+    n = cand_ptr.numel() - 1
+    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or middle < 0:
+        raise GnnpnError(f"{who}: inconsistent operand sizes")
+    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
+    out = _descent_fields(B, max_slots, max(int(hist_ld), 1), dev, rows=torch.zeros)
+    if hist != "history":
+        out[hist] = out.pop("history")
+    out.update({k: torch.empty(B, dtype=I32, device=dev) for k in extra})
+    fields = ("best_fitness", "start_fitness", "best_pos", "best_rows", hist, "sweeps", "moves", *extra)       # the C order
+    check(getattr(_lib.load(), entry)(
+        B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
+        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), middle,
+        *(dev_ptr(out[k], out[k].dtype, k) for k in fields), stream_ptr()), entry)
+    if hist == "history":
+        out[hist] = out[hist][:, :int(max_sweeps)]
+    return out
+
+
 def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_slots=None, max_cand=None, wide=None):
     """One-swap coordinate descent over the ES-WOA figure of merit, a ragged batch in ONE launch (gnnpn_descend_ragged_f64): from
     every problem's start composition, slot by slot the best candidate of the slot's list (the lowest position among equals) is
@@ -1271,21 +1322,8 @@ def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, m
     exceeds the LDS).  Returns a dict of device tensors: best_fitness [B] f64, start_fitness [B] f64, best_pos [B, max_slots] i32
     and best_rows [B, max_slots, 4] f64 (0 past a problem's count), history [B, max_sweeps] f64 (the merit after every sweep; past
     the last sweep the final value), sweeps [B] i32 (the last, fruitless one included), moves [B] i32."""
-    dev = cand.device
-    B = prob_ptr.numel() - 1
-    n = cand_ptr.numel() - 1
-    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0:
-        raise GnnpnError("descend_ragged: inconsistent operand sizes")
-    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
-    out = _descent_fields(B, max_slots, max(int(max_sweeps), 1), dev, rows=torch.zeros)
-    check(_lib.load().gnnpn_descend_ragged_f64(
-        B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
-        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), int(bool(wide)),
-        dev_ptr(out["best_fitness"], F64, "best_fitness"), dev_ptr(out["start_fitness"], F64, "start_fitness"),
-        dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"), dev_ptr(out["history"], F64, "history"),
-        dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"), stream_ptr()), "gnnpn_descend_ragged_f64")
-    out["history"] = out["history"][:, :int(max_sweeps)]
-    return out
+    return _descend_launch("gnnpn_descend_ragged_f64", "descend_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
+                           int(bool(wide)), max_slots, max_cand, "history", max_sweeps)
 
 
 def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_slots=None, max_cand=None):
@@ -1297,24 +1335,8 @@ def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps
     [B, max_slots] i32 and best_rows [B, max_slots, 4] f64 (0 past a problem's count), round_history [B, max(max_rounds, 1)] f64 (the
     merit after every round; past the last round the final value; max_rounds = 0: phase 0's merit), sweeps and moves [B] i32 (all
     one-swap phases together), rounds, pair_moves [B] i32, converged [B] i32 (1: no single swap and no pair swap lowers the result)."""
-    dev = cand.device
-    B = prob_ptr.numel() - 1
-    n = cand_ptr.numel() - 1
-    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or int(max_rounds) < 0:
-        raise GnnpnError("descend_pairs_ragged: inconsistent operand sizes")
-    max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
-    out = _descent_fields(B, max_slots, max(int(max_rounds), 1), dev, rows=torch.zeros)
-    out["round_history"] = out.pop("history")
-    out.update({k: torch.empty(B, dtype=I32, device=dev) for k in ("rounds", "pair_moves", "converged")})
-    check(_lib.load().gnnpn_descend_pairs_ragged_f64(
-        B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
-        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), int(max_rounds),
-        dev_ptr(out["best_fitness"], F64, "best_fitness"), dev_ptr(out["start_fitness"], F64, "start_fitness"),
-        dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"),
-        dev_ptr(out["round_history"], F64, "round_history"), dev_ptr(out["sweeps"], I32, "sweeps"), dev_ptr(out["moves"], I32, "moves"),
-        dev_ptr(out["rounds"], I32, "rounds"), dev_ptr(out["pair_moves"], I32, "pair_moves"), dev_ptr(out["converged"], I32, "converged"),
-        stream_ptr()), "gnnpn_descend_pairs_ragged_f64")
-    return out
+    return _descend_launch("gnnpn_descend_pairs_ragged_f64", "descend_pairs_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
+                           int(max_rounds), max_slots, max_cand, "round_history", max_rounds, ("rounds", "pair_moves", "converged"))
 
 
 def descend_select(res, actions_all, n_slots):
@@ -1323,14 +1345,17 @@ def descend_select(res, actions_all, n_slots):
     n_slots [B * R] i32 (woa_candidates_replicas').  The key is (best_fitness, replica) under plain <: a NaN never wins, equal
     merits (-0.0 and 0.0 too) go to the lowest replica, and where every row of a problem is NaN replica 0 is returned with its
     NaN / -1 fields.  Returns descend_ragged's keys for the B winners plus start_index [B] i32 (the winning replica), actions
-    [B, T', 8] (its start rows, actions_all's dtype) and n_slots [B] i32."""
+    [B, T', 8] (its start rows, actions_all's dtype) and n_slots [B] i32.  ``res`` may as well be descend_pairs_ragged's dict: its
+    round_history is selected in history's place and returned under its own name, and every further [B * R] i32 field of ``res``
+    (rounds, pair_moves, converged) comes back as the winner's entry [B], gathered by start_index."""
     if not isinstance(actions_all, torch.Tensor) or actions_all.dim() != 4 or actions_all.shape[3] != 8 or actions_all.shape[1] < 1:
         raise GnnpnError(f"descend_select: actions_all [B, R >= 1, T, 8] expected, got {tuple(getattr(actions_all, 'shape', ()))}")
     if actions_all.dtype not in (F32, F64):
         raise GnnpnError(f"descend_select: actions_all must be float32 or float64, got {actions_all.dtype}")
     B, R, aT, _ = actions_all.shape
     fit, pos, rows = res["best_fitness"], res["best_pos"], res["best_rows"]
-    hist = res["history"].contiguous()
+    hist_key = "round_history" if "round_history" in res and "history" not in res else "history"
+    hist = res[hist_key].contiguous()
     if fit.numel() != B * R or pos.dim() != 2 or pos.shape[0] != B * R or rows.shape != (B * R, pos.shape[1], 4) or \
             hist.shape[0] != B * R or n_slots.numel() != B * R:
         raise GnnpnError(f"descend_select: {B} x {R} rows expected in every field of res and in n_slots")
@@ -1349,6 +1374,12 @@ def descend_select(res, actions_all, n_slots):
         dev_ptr(out["best_pos"], I32, "best_pos"), dev_ptr(out["best_rows"], F64, "best_rows"), dev_ptr(out["history"], F64, "history"),
         dev_ptr(out["actions"], adt, "actions"), dev_ptr(out["start_index"], I32, "start_index"), stream_ptr()),
         "gnnpn_descend_select_f64")
+    if hist_key != "history":
+        out[hist_key] = out.pop("history")
+    more = [k for k, v in res.items() if k not in out and isinstance(v, torch.Tensor) and v.dtype == I32 and v.shape == (B * R,)]
+    if more:
+        win = out["start_index"].long()[:, None]
+        out.update({k: res[k].view(B, R).gather(1, win)[:, 0] for k in more})
     return out
 
 # ---- REINFORCE training step of the High-level pointer network (csrc/train.hip; include/gnnpn_hip.h) -----------------

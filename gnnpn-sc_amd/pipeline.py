@@ -147,13 +147,19 @@ def _descend_tables(tabs, max_sweeps, pair_rounds=None):
         if tabs["max_slots"] > 64:
             raise ops.GnnpnError(f"descend_pairs: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
                                  "per problem (descend runs one-swap descent at any slot count)")
-        res = ops.descend_pairs_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
-                                       int(pair_rounds), max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+        res = tabs.descend_pairs(max_sweeps, int(pair_rounds))
     else:
-        res = ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], max_sweeps,
-                                 max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+        res = tabs.descend(max_sweeps)
     res["n_slots"] = tabs["n_slots"]
     return res
+
+
+def _descend_actions(services, batch, out, max_sweeps, pair_rounds, reduct, min_cost, patches):
+    """``descend`` (pair_rounds None) and ``descend_pairs``: the tables of ``out["actions"]``, their descent, the quality."""
+    actions = out["actions"]
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    return _quality(_descend_tables(tabs, max_sweeps, pair_rounds), min_cost, actions.device)
 
 
 @torch.no_grad()
@@ -164,10 +170,7 @@ def descend(services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patche
     problems in one launch, deterministic: no seeds).  A problem the host path raises on raises GnnpnError naming it.
     ``ML2PNPipeline.descend`` is this, as a method.  Returns ops.descend_ragged's dict (best_fitness, start_fitness, best_pos,
     best_rows, history, sweeps, moves) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness)."""
-    actions = out["actions"]
-    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
-                              actions, reduct=reduct, patches=patches)
-    return _quality(_descend_tables(tabs, max_sweeps), min_cost, actions.device)
+    return _descend_actions(services, batch, out, max_sweeps, None, reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -180,10 +183,7 @@ def descend_pairs(services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, m
     ops.descend_pairs_ragged's dict (best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds,
     pair_moves, converged) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness).  ``max_rounds`` = 0: ``descend``'s
     result in every shared field."""
-    actions = out["actions"]
-    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
-                              actions, reduct=reduct, patches=patches)
-    return _quality(_descend_tables(tabs, max_sweeps, max_rounds), min_cost, actions.device)
+    return _descend_actions(services, batch, out, max_sweeps, max_rounds, reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -221,16 +221,10 @@ def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patch
     tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                                        all_rows, reduct=reduct, patches=patches)
     per_row = _descend_tables(tabs, max_sweeps, int(pair_rounds) if pair_rounds else None)
-    if pair_rounds:                                               # the selection copies the rounds' merits as it does the sweeps'
-        per_row["history"] = per_row.pop("round_history")
-    res = ops.descend_select(per_row, all_rows, tabs["n_slots"])
+    res = ops.descend_select(per_row, all_rows, tabs["n_slots"])        # (the rounds' merits and counters too, where there are any)
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
     if pair_rounds:
-        res["round_history"] = res.pop("history")
-        win = res["start_index"].long()[:, None]
-        for key in ("rounds", "pair_moves", "converged"):
-            res[key] = per_row[key].view(B, N).gather(1, win)[:, 0]
         res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
     return _quality(res, min_cost, all_rows.device)
 
@@ -259,15 +253,11 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
     if not isinstance(seeds, torch.Tensor):
         seeds = torch.from_numpy(np.asarray(seeds, dtype=np.uint64).reshape(B).view(np.int64).copy())
     seeds = seeds.to(device=dev, dtype=torch.int64).contiguous()
-    start_pos, descent = tabs["start_pos"], None
+    start_pos, descent = None, None
     if descend or pair_rounds:
         descent = _quality(_descend_tables(tabs, int(descend), int(pair_rounds) if pair_rounds else None), min_cost, dev)
-        # a problem's slots are rows prob_ptr[p] .. of the flat tables and the first n_slots[p] entries of its best_pos row
-        slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
-        start_pos = descent["best_pos"][slots].contiguous()
-    fit, pos, hist, draws, rows = ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"],
-                                                   tabs["bounds"], start_pos, popSize, MAX_Iter, seeds,
-                                                   max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+        start_pos = tabs.flat(descent["best_pos"])
+    fit, pos, hist, draws, rows = tabs.eswoa(popSize, MAX_Iter, seeds, start_pos)
     res = {"best_fitness": fit, "best_rows": rows, "n_slots": tabs["n_slots"], "best_pos": pos, "history": hist, "draws": draws}
     if descent is not None:
         res["descent"] = descent

@@ -195,17 +195,16 @@ def main(argv):
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
         net, low, high, K = _models(cfg, ds, n_services, len(sf), epoch, "--random-init" in flags)
+        args = argv[3:]
+        seed = int(args[args.index("--seed") + 1]) if "--seed" in args else None      # the ES-WOA streams' and the best-of-N draws'
         woa = None
         if "--woa" in flags:                                        # + ES-WOA refinement on the device ([<ds>-WOA])
             w = cfg[f"{ds}-WOA"]
-            args = argv[3:]
             woa = {"popSize": int(w["popSize"]), "MAX_Iter": int(w["MAX_Iter"]),
-                   "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]),
-                   "seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
+                   "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]), "seed": seed}
         best = {}
         if samples is not None:                                     # best-of-N decoding of the High level
-            args = argv[3:]
-            best = {"samples": int(samples), "sample_seed": int(args[args.index("--seed") + 1]) if "--seed" in args else None}
+            best = {"samples": int(samples), "sample_seed": seed}
         if sweeps is not None:                                      # one-swap descent of the test quarter's actions
             if int(sweeps) < 1:
                 print("--descend=SWEEPS: at least one sweep")

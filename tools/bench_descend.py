@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The one-swap descent beside the ES-WOA refinement it precedes, on the two configurations and the generators of
-tools/bench_refine.py (1000 synthetic test problems each):
+tools/bench_refine.py (tools/search_bench.py holds them; 1000 synthetic test problems each):
 
     qws     47 categories, 2507 services, 10 tasks, reduct 0,    pop 50, 250 iterations
     normal  50 categories, 5000 services, 10 tasks, reduct 0.55, pop 60, 500 iterations
@@ -26,62 +26,36 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from bench_refine import CONFIGS, _seed_rows          # noqa: E402  (the same configurations, the same generators)
+from search_bench import CONFIGS, _seed_rows, mean, setup, timed          # noqa: E402
 
 
 def run_config(cfg, n_test, repeat, sweeps, dev, wide=None):
     import torch
-    import gnnpn_sc_amd.synth as synth
     from gnnpn_sc_amd import ops
-    from gnnpn_sc_amd.loadData import tables_from_dataset
-    from gnnpn_sc_amd.pipeline import DeviceBatch, DeviceServices
-    P = n_test * 4
-    first = P // 4 * 3
-    ds = synth.make_dataset(cfg["T"], cfg["S"], P, seed=1, tasks_per_problem=cfg["tasks"])
-    acts = _seed_rows(ds, cfg["reduct"], np.random.default_rng(2))
-    table, pb = tables_from_dataset(ds, first, None)
-    svc, batch = DeviceServices.from_table(table, dev), DeviceBatch.from_problems(pb, dev)
-    a = torch.from_numpy(acts).to(dev)
-    sd = torch.tensor([1000 + first + i for i in range(n_test)], dtype=torch.int64, device=dev)
+    ds, svc, batch, _first, sd = setup(cfg, n_test, dev)
+    a = torch.from_numpy(_seed_rows(ds, cfg["reduct"], np.random.default_rng(2))).to(dev)
 
     def build():
         return ops.woa_candidates(svc.cat_ptr, svc.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds, a,
                                   reduct=cfg["reduct"])
 
-    def descend(tabs):
-        return ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], sweeps,
-                                  max_slots=tabs["max_slots"], max_cand=tabs["max_cand"], wide=wide)
-
-    def eswoa(tabs, start_pos):
-        return ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"], tabs["bounds"], start_pos,
-                                cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"], wide=wide)
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        return out, e0.elapsed_time(e1)
+    def eswoa(tabs, start_pos=None):
+        return tabs.eswoa(cfg["pop"], cfg["iters"], sd, start_pos, wide=wide)
 
     tabs = build()                                                                     # warm-up of the three stages
-    slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
-    des = descend(tabs)
-    descended_pos = des["best_pos"][slots].contiguous()
-    eswoa(tabs, tabs["start_pos"])
+    descended_pos = tabs.flat(tabs.descend(sweeps, wide)["best_pos"])
+    eswoa(tabs)
     ms = {"builder": [], "descent": [], "eswoa": [], "eswoa_after_descent": []}
     for _ in range(repeat):
-        tabs, t = timed(build)
+        tabs, t = timed(build, dev)
         ms["builder"].append(t)
-        des, t = timed(lambda: descend(tabs))
+        des, t = timed(lambda: tabs.descend(sweeps, wide), dev)
         ms["descent"].append(t)
-        alone, t = timed(lambda: eswoa(tabs, tabs["start_pos"]))
+        alone, t = timed(lambda: eswoa(tabs), dev)
         ms["eswoa"].append(t)
-        both, t = timed(lambda: eswoa(tabs, descended_pos))
+        both, t = timed(lambda: eswoa(tabs, descended_pos), dev)
         ms["eswoa_after_descent"].append(t)
     med = {k: float(np.median(v)) for k, v in ms.items()}
-    mean = lambda t: round(float(t.double().mean().item()), 6)      # noqa: E731
     per_s = lambda t: round(n_test / (t * 1e-3), 1)                 # noqa: E731
     return {"problems": n_test, **cfg, "max_sweeps": sweeps, "mean_slots": mean(tabs["n_slots"]),
             "mean_candidates": round(tabs["cand"].shape[0] / n_test, 2),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Multi-start descent — descent from N start compositions per problem, the lowest local optimum kept — on the two configurations
-and the generators of tools/bench_descend.py, over its 1000 synthetic test problems and over the first 256 of them:
+and the generators of tools/search_bench.py, over tools/bench_descend.py's 1000 synthetic test problems and over the first 256 of them:
 
     qws     47 categories, 2507 services, 10 tasks, reduct 0,    pop 50, 250 iterations
     normal  50 categories, 5000 services, 10 tasks, reduct 0.55, pop 60, 500 iterations
@@ -30,20 +30,15 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from bench_refine import CONFIGS, _seed_rows          # noqa: E402  (the same configurations, the same generators)
+from search_bench import CONFIGS, _seed_rows, dataset, mean, setup, timed          # noqa: E402
 
 N_TEST = 1000       # bench_descend's problems: the test quarter of a data set of 4000
-
-
-def _dataset(cfg):
-    import gnnpn_sc_amd.synth as synth
-    return synth.make_dataset(cfg["T"], cfg["S"], N_TEST * 4, seed=1, tasks_per_problem=cfg["tasks"])
 
 
 def _start_rows(job):
     name, r = job
     cfg = CONFIGS[name]
-    return _seed_rows(_dataset(cfg), cfg["reduct"], np.random.default_rng(2 + r))
+    return _seed_rows(dataset(cfg, N_TEST), cfg["reduct"], np.random.default_rng(2 + r))
 
 
 def make_starts(names, n_replicas):
@@ -57,42 +52,23 @@ def make_starts(names, n_replicas):
 def run_config(cfg, ds, starts, n_test, replicas, repeat, sweeps, dev):
     import torch
     from gnnpn_sc_amd import ops
-    from gnnpn_sc_amd.loadData import tables_from_dataset
-    from gnnpn_sc_amd.pipeline import DeviceBatch, DeviceServices
-    first = len(ds["nodefeatures"]) // 4 * 3
-    table, pb = tables_from_dataset(ds, first, first + n_test)
-    svc, batch = DeviceServices.from_table(table, dev), DeviceBatch.from_problems(pb, dev)
+    _ds, svc, batch, _first, sd = setup(cfg, N_TEST, dev, last=n_test, ds=ds)
     a_all = torch.from_numpy(starts[:n_test]).to(dev)
     operands = (svc.cat_ptr, svc.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds)
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        return out, e0.elapsed_time(e1)
-
-    def descend(tabs):
-        return ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], sweeps,
-                                  max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
-
-    mean = lambda t: round(float(t.double().mean().item()), 6)      # noqa: E731
     rows = []
     for N in replicas:
         a = a_all[:, :N].contiguous()
         build = lambda: ops.woa_candidates_replicas(*operands, a, reduct=cfg["reduct"])      # noqa: E731
         tabs = build()                                                                     # warm-up of the three stages at this shape
-        per_row = descend(tabs)
+        per_row = tabs.descend(sweeps)
         win = ops.descend_select(per_row, a, tabs["n_slots"])
         ms = {"builder": [], "descent": [], "select": []}
         for _ in range(repeat):
-            tabs, t = timed(build)
+            tabs, t = timed(build, dev)
             ms["builder"].append(t)
-            per_row, t = timed(lambda: descend(tabs))
+            per_row, t = timed(lambda: tabs.descend(sweeps), dev)
             ms["descent"].append(t)
-            win, t = timed(lambda: ops.descend_select(per_row, a, tabs["n_slots"]))
+            win, t = timed(lambda: ops.descend_select(per_row, a, tabs["n_slots"]), dev)
             ms["select"].append(t)
         med = {k: float(np.median(v)) for k, v in ms.items()}
         total = sum(med.values())
@@ -107,22 +83,15 @@ def run_config(cfg, ds, starts, n_test, replicas, repeat, sweeps, dev):
         r["descent_over_one_start"] = round(r["descent_ms"] / rows[0]["descent_ms"], 3) if rows[0]["replicas"] == 1 else None
 
     # the comparison of tools/bench_descend.py in the same run: ES-WOA alone, and descent (one start) + ES-WOA
-    a0 = a_all[:, 0].contiguous()
-    sd = torch.tensor([1000 + first + i for i in range(n_test)], dtype=torch.int64, device=dev)
-    tabs = ops.woa_candidates(*operands, a0, reduct=cfg["reduct"])
-    des = descend(tabs)
-    slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
-    descended_pos = des["best_pos"][slots].contiguous()
-
-    def eswoa(start_pos):
-        return ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"], tabs["bounds"], start_pos,
-                                cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
-    eswoa(tabs["start_pos"])
+    tabs = ops.woa_candidates(*operands, a_all[:, 0].contiguous(), reduct=cfg["reduct"])
+    des = tabs.descend(sweeps)
+    descended_pos = tabs.flat(des["best_pos"])
+    tabs.eswoa(cfg["pop"], cfg["iters"], sd)
     ms = {"eswoa": [], "eswoa_after_descent": []}
     for _ in range(repeat):
-        alone, t = timed(lambda: eswoa(tabs["start_pos"]))
+        alone, t = timed(lambda: tabs.eswoa(cfg["pop"], cfg["iters"], sd), dev)
         ms["eswoa"].append(t)
-        both, t = timed(lambda: eswoa(descended_pos))
+        both, t = timed(lambda: tabs.eswoa(cfg["pop"], cfg["iters"], sd, descended_pos), dev)
         ms["eswoa_after_descent"].append(t)
     return {"problems": n_test, **cfg, "max_sweeps": sweeps, "mean_slots": mean(tabs["n_slots"]),
             "start": {"mean_best_fitness": mean(des["start_fitness"])}, "multistart": rows,
@@ -145,7 +114,7 @@ def main():
     dev = torch.device("cuda:0")
     out = {"metric": "multistart", "starts": "synthetic (_seed_rows, default_rng(2 + replica)): no trained policy", "configs": {}}
     for name in names:
-        ds = _dataset(CONFIGS[name])
+        ds = dataset(CONFIGS[name], N_TEST)
         out["configs"][name] = {str(n): run_config(CONFIGS[name], ds, starts[name], int(n), replicas, args.repeat, args.sweeps, dev)
                                 for n in args.problems.split(",")}
     print(json.dumps(out))

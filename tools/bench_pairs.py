@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The pair-swap descent beside the one-swap descent it extends and the ES-WOA refinement both precede, on the two configurations,
-the generators and the 1000 problems of tools/bench_descend.py (tools/bench_refine.py's):
+the generators and the 1000 problems of tools/bench_descend.py (tools/search_bench.py holds them):
 
     qws     47 categories, 2507 services, 10 tasks, reduct 0,    pop 50, 250 iterations
     normal  50 categories, 5000 services, 10 tasks, reduct 0.55, pop 60, 500 iterations
@@ -25,73 +25,40 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from bench_refine import CONFIGS, _seed_rows          # noqa: E402  (the same configurations, the same generators)
+from search_bench import CONFIGS, _seed_rows, mean, setup, share, timed          # noqa: E402
 
 ROUNDS = (1, 4)
 
 
 def run_config(cfg, n_test, repeat, sweeps, dev):
     import torch
-    import gnnpn_sc_amd.synth as synth
     from gnnpn_sc_amd import ops
-    from gnnpn_sc_amd.loadData import tables_from_dataset
-    from gnnpn_sc_amd.pipeline import DeviceBatch, DeviceServices
-    P = n_test * 4
-    first = P // 4 * 3
-    ds = synth.make_dataset(cfg["T"], cfg["S"], P, seed=1, tasks_per_problem=cfg["tasks"])
-    acts = _seed_rows(ds, cfg["reduct"], np.random.default_rng(2))
-    table, pb = tables_from_dataset(ds, first, None)
-    svc, batch = DeviceServices.from_table(table, dev), DeviceBatch.from_problems(pb, dev)
-    a = torch.from_numpy(acts).to(dev)
-    sd = torch.tensor([1000 + first + i for i in range(n_test)], dtype=torch.int64, device=dev)
+    ds, svc, batch, _first, sd = setup(cfg, n_test, dev)
+    a = torch.from_numpy(_seed_rows(ds, cfg["reduct"], np.random.default_rng(2))).to(dev)
 
     def build():
         return ops.woa_candidates(svc.cat_ptr, svc.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds, a,
                                   reduct=cfg["reduct"])
 
-    def descend(tabs):
-        return ops.descend_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], sweeps,
-                                  max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
-
-    def pairs(tabs, rounds):
-        return ops.descend_pairs_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["cand"], tabs["bounds"], tabs["start_pos"], sweeps, rounds,
-                                        max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
-
-    def eswoa(tabs, start_pos):
-        return ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"], tabs["bounds"], start_pos,
-                                cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        return out, e0.elapsed_time(e1)
-
     tabs = build()                                                                     # warm-up of every launch
-    slots = torch.arange(tabs["max_slots"], device=dev)[None, :] < tabs["n_slots"][:, None]
-    descended_pos = descend(tabs)["best_pos"][slots].contiguous()
-    paired_pos = {r: pairs(tabs, r)["best_pos"][slots].contiguous() for r in ROUNDS}[ROUNDS[-1]]
-    eswoa(tabs, tabs["start_pos"])
+    descended_pos = tabs.flat(tabs.descend(sweeps)["best_pos"])
+    paired_pos = {r: tabs.flat(tabs.descend_pairs(sweeps, r)["best_pos"]) for r in ROUNDS}[ROUNDS[-1]]
+    tabs.eswoa(cfg["pop"], cfg["iters"], sd)
     names = ["builder", "descent"] + [f"pairs_{r}" for r in ROUNDS] + ["eswoa", "eswoa_after_descent", "eswoa_after_pairs"]
     ms, res = {k: [] for k in names}, {}
     for _ in range(repeat):
-        tabs, t = timed(build)
+        tabs, t = timed(build, dev)
         ms["builder"].append(t)
-        res["descent"], t = timed(lambda: descend(tabs))
+        res["descent"], t = timed(lambda: tabs.descend(sweeps), dev)
         ms["descent"].append(t)
         for r in ROUNDS:
-            res[f"pairs_{r}"], t = timed(lambda: pairs(tabs, r))          # noqa: B023
+            res[f"pairs_{r}"], t = timed(lambda: tabs.descend_pairs(sweeps, r), dev)          # noqa: B023
             ms[f"pairs_{r}"].append(t)
-        for name, start in (("eswoa", tabs["start_pos"]), ("eswoa_after_descent", descended_pos), ("eswoa_after_pairs", paired_pos)):
-            out, t = timed(lambda: eswoa(tabs, start))                    # noqa: B023
+        for name, start in (("eswoa", None), ("eswoa_after_descent", descended_pos), ("eswoa_after_pairs", paired_pos)):
+            out, t = timed(lambda: tabs.eswoa(cfg["pop"], cfg["iters"], sd, start), dev)       # noqa: B023
             res[name] = {"best_fitness": out[0]}
             ms[name].append(t)
     med = {k: float(np.median(v)) for k, v in ms.items()}
-    mean = lambda t: round(float(t.double().mean().item()), 6)      # noqa: E731
-    share = lambda t: round(float(t.double().mean().item()), 4)     # noqa: E731
     cols = {"builder": {"ms": round(med["builder"], 3)}}
     for name in names[1:]:
         r = res[name]

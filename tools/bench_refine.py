@@ -23,40 +23,11 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+for p in (ROOT, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 
-CONFIGS = {"qws": dict(T=47, S=2507, tasks=10, reduct=0, pop=50, iters=250),
-           "normal": dict(T=50, S=5000, tasks=10, reduct=0.55, pop=60, iters=500)}
-
-
-def _seed_rows(ds, reduct, g, foreign=0.1):
-    """[nTest, T, 8] action rows: a member of every task's addS list (foreign rows now and then), dummies elsewhere."""
-    from gnnpn_sc_amd.loadData import addS
-    sf = ds["serviceFeature"]
-    n_cat = len(sf)
-    div, mod = [], []
-    for key in sf:
-        div += [int(key) - 1] * len(sf[key])
-        mod += list(range(len(sf[key])))
-    P = len(ds["nodefeatures"])
-    n_train = P // 4 * 3
-    acts = np.zeros((P - n_train, n_cat, 8))
-    acts[:, :, 1:4] = 1.0
-    for b, nodes in enumerate(ds["nodefeatures"][n_train:]):
-        cons = {c: [0] * 8 for c in range(1, n_cat + 1)}
-        for node in nodes:
-            pair = node[-5:-3] + node[-2:]
-            if node[0] == 1:
-                for c in cons:
-                    cons[c][-4:] = pair
-            else:
-                cons[node[:-6].index(1)][-8:-4] = pair
-        cats = [n[:-6].index(1) - 1 for n in nodes][1:]
-        for c, lst in zip(cats, addS(range(len(div)), sf, cons, cats, div, mod, reduct, None)):
-            if lst:
-                acts[b, c, :4] = np.r_[g.random(2), 0.9 + 0.1 * g.random(2)] if g.random() < foreign else lst[int(g.integers(0, len(lst)))]
-    return acts
+from search_bench import CONFIGS, _seed_rows          # noqa: E402,F401  (re-exported: whoever imported them from here still can)
 
 
 def run_config(name, cfg, n_test, repeat, dev):
@@ -101,8 +72,7 @@ def run_config(name, cfg, n_test, repeat, dev):
             tabs = ops.woa_candidates(svc.cat_ptr, svc.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds, a,
                                       reduct=cfg["reduct"])
             e1.record()
-            ops.eswoa_ragged(tabs["prob_ptr"], tabs["cand_ptr"], tabs["len_init"], tabs["cand"], tabs["bounds"], tabs["start_pos"],
-                             cfg["pop"], cfg["iters"], sd, max_slots=tabs["max_slots"], max_cand=tabs["max_cand"])
+            tabs.eswoa(cfg["pop"], cfg["iters"], sd)
             e2.record()
             torch.cuda.synchronize(dev)
             walls.append(time.perf_counter() - w0)
