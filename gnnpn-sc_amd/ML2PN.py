@@ -75,7 +75,26 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     ``ML+2PN+descent.txt``; with ``woa`` ES-WOA starts from that winner.  The PNHigh artefact is the best-of winner by R either way.
     ``pair_rounds`` (>= 1, with descend): pair-swap descent with that many rounds allowed in place of the one-swap descent
     (pipeline.descend_pairs / descend_starts_pairs): ``ML+2PN+pairs.txt`` (``ML+2PN+multistart+pairs.txt`` with all_starts) in
-    place of the descent artefact, its format plus the per-problem rounds, pair_moves and converged; ES-WOA starts from its result."""
+    place of the descent artefact, its format plus the per-problem rounds, pair_moves and converged; ES-WOA starts from its result.
+    ``infer_pairs_windowed`` is this run with the pair-swap descent over a window of slots."""
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts,
+                  pair_rounds, None)
+
+
+def infer_pairs_windowed(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1,
+                         sample_seed=None, descend=16, pair_rounds=4, pair_span=0):
+    """``infer`` with ``descend`` and ``pair_rounds`` whose pair-swap descent takes any number of slots and exchanges only slots at most
+    ``pair_span`` apart (>= 0; 0: every pair; pipeline.descend_pairs_windowed): ``ML+2PN+pairs.txt`` in ``infer``'s format plus ``span``.
+    A function of its own because ``infer``'s parameter list is pinned by the host tests; without ``woa`` and ``all_starts``, which
+    stay with the full sweep of at most 64 slots."""
+    if descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0:
+        raise ValueError("ML2PN.infer_pairs_windowed: pair_span needs descend, at least one round and a span >= 0")
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, False,
+                  pair_rounds, pair_span)
+
+
+def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, pair_rounds,
+           pair_span):
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -126,8 +145,8 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
             test_actions.append(act[max(0, n_train - lo):])
     paths = write_artifacts(dataset, epoch, rankings, actions)
     if woa is not None or descend is not None:
-        refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
-                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds,
+        _refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
+                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds, pair_span=pair_span,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
@@ -141,11 +160,19 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     (pipeline.descend_starts), written as ``ML+2PN+multistart.txt`` instead; ES-WOA then starts from the winner's rows.
     ``pair_rounds`` (>= 1, with ``descend``): pair-swap descent in place of the one-swap descent in each of these, written as
     ``ML+2PN+pairs.txt`` / ``ML+2PN+multistart+pairs.txt`` with the per-problem rounds, pair_moves and converged beside the four keys."""
+    return _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=seed, descend=descend, starts=starts,
+                                pair_rounds=pair_rounds)
+
+
+def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, pair_rounds=None,
+                         pair_span=None):
+    """refine_test_quarter; ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
+    with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import DeviceBatch, descend as descend_actions, descend_pairs, descend_starts, descend_starts_pairs, refine
+    from .pipeline import DeviceBatch, descend as descend_actions, descend_pairs, descend_pairs_windowed, descend_starts, descend_starts_pairs, refine
     counters = lambda r: {k: r[k].cpu().tolist() for k in ("rounds", "pair_moves", "converged")}      # noqa: E731
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
@@ -169,11 +196,13 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
         if multi:
             rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
             res = descend_starts_pairs(svc, batch, rows, pair_rounds=pair_rounds, **kw) if pairs else descend_starts(svc, batch, rows, **kw)
+        elif pair_span is not None:
+            res = descend_pairs_windowed(svc, batch, out, max_rounds=pair_rounds, max_span=pair_span, **kw)
         else:
             res = descend_pairs(svc, batch, out, max_rounds=pair_rounds, **kw) if pairs else descend_actions(svc, batch, out, **kw)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name,
-                                  extra=counters(res) if pairs else None)
+                                  extra=({**counters(res), **({} if pair_span is None else {"span": pair_span})}) if pairs else None)
         if multi:
             out = {"actions": res["actions"]}        # refine below rebuilds the winner's tables and repeats its descent
     if descend is None or popSize > 0:

@@ -12,13 +12,16 @@
 // chains through cur[j+1 .. T-1] (every lane reads the same LDS address: broadcasts), and forms np.sum of column 0 in numpy's
 // order with element j replaced.  No atomics, no waits on other workgroups; every loop is bounded by max_sweeps, T or a list length.
 //
-// Pair-swap descent (descend_pairs_kernel) goes on from the one-swap optimum: a swap that breaks a product bound costs +1 and is
-// never taken alone, even where a second swap restores the bound.  A pair sweep tries, for every two slots, every pair of their
-// candidates (one pair per lane, the same carried prefix, two rows replaced), and the one-swap sweeps run again after a sweep that
-// moved — the same sweeps, not a second statement of them (tests/pair_descent_reference.py is its Python restatement).
+// Pair-swap descent (descend_pairs_kernel, descend_pairs_wide_kernel) goes on from the one-swap optimum: a swap that breaks a product
+// bound costs +1 and is never taken alone, even where a second swap restores the bound.  A pair sweep tries, for every two slots (or
+// every two at most max_span apart), every pair of their candidates (one pair per thread, the same carried prefix, two rows replaced),
+// and the one-swap sweeps run again after a sweep that moved — the same sweeps, not a second statement of them
+// (tests/pair_descent_reference.py and, with the span, tests/pair_window_reference.py are its Python restatements).
 #include "woa_eval.h"
 
 #include <climits>
+#include <limits>
+#include <type_traits>
 
 namespace {
 // What a slot's candidates share: the smallest (min1, at `owner`), second smallest (min2, at `owner2`) and third smallest (min3)
@@ -60,7 +63,8 @@ struct Carried {
 };
 
 // (value, position) order: the smaller merit, the lower position among equals.  A NaN merit never enters (callers keep +inf for it).
-__device__ __forceinline__ void take_better(double& f, int& c, double of, int oc) {
+template <class K>
+__device__ __forceinline__ void take_better(double& f, K& c, double of, K oc) {
     if (of < f || (of == f && oc < c)) {
         f = of;
         c = oc;
@@ -75,6 +79,16 @@ __device__ __forceinline__ void wave_argmin(double& f, int& c, int lane) {
     }
 }
 
+// The same with a 64-bit position (the workgroup form's pair products: a * len_j + b over lists only int32 cand_ptr bounds).
+__device__ __forceinline__ void wave_argmin(double& f, long long& c, int lane) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double of = wave_bcast(f, (lane + o) & 63);
+        const long long oc = __double_as_longlong(wave_bcast(__longlong_as_double(c), (lane + o) & 63));      // a move of bits
+        take_better(f, c, of, oc);
+    }
+}
+
 constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halves (to within 7 terms) per level
 
 // Where a problem's state lives: the columns of cur (L.col0, col1, L.col2, L.col3), the base / len tables and the bounds in LDS;
@@ -82,7 +96,7 @@ constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halv
 struct DescendMem {
     WideLds L;
     double* col1;      // [T] column 1 (np.min)
-    double* sib;       // [SIB_MAX] sums of the sibling blocks on np.sum's path to the current slot
+    double* sib;       // [SIB_MAX] sums of the sibling blocks on np.sum's path to the current slot (pair sweep: three such rows)
     int* cur;          // [T]
     double* table;     // [n_cand][4]
 };
@@ -111,7 +125,7 @@ struct DescendState {
 };
 
 // The search in three parts, each by the NT threads of a problem's workgroup — load and validate, one-swap sweeps from the state in
-// LDS, write the outputs — which descend_problem (both one-swap kernels) and descend_pairs_kernel call.  TABLE_IN_LDS: the problem's
+// LDS, write the outputs — which descend_problem (both one-swap kernels) and descend_pairs_problem (both pair kernels) call.  TABLE_IN_LDS: the problem's
 // candidate table is copied to M.table and cur is LDS too (else the table stays in global memory and cur IS the output row).
 // NT = 64 is one wave whose columns are [4][64]: at most 64 slots, so np.sum is always one leaf and nothing crosses waves.
 
@@ -312,27 +326,90 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
     }
 }
 
-// One pair sweep from the state in LDS by ONE wave (lane form): for every slot pair i < j in order, lanes stride over k = a * len_j + b
-// — the composition with slots i and j replaced by candidates a and b of their lists, current members included — lowest k first,
-// each keeping its best under strict <; the wave's argmin is by (value, k); the pair is taken if it is strictly below the current
-// merit.  A lane continues the carried prefix pre2 / pre3 (np.cumprod up to slot i - 1) with row a, cur[i+1 .. j-1], row b,
-// cur[j+1 .. T-1], one __dmul_rn each: numpy's order.  Returns the number of pairs taken.  Bounded by T and list lengths.
-__device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S) {
+// A pair product's position k = a * len_j + b: an int where the table is in LDS (a CU's LDS holds under 5000 candidates), 64 bits in
+// the workgroup form, whose lists only the int32 cand_ptr bounds (len_i + len_j < 2^31, so k < 2^62).
+template <int NT>
+using pair_key_t = std::conditional_t<(NT > 64), long long, int>;
+
+// One pair sweep from the state in LDS by the NT threads of the problem's workgroup: for every slot pair i < j in order (max_span = s
+// > 0: only j <= i + s), threads stride over k = a * len_j + b — the composition with slots i and j replaced by candidates a and b of
+// their lists, current members included — lowest k first, each keeping its best under strict <; the argmin over the workgroup is by
+// (value, k); the pair is taken if it is strictly below the current merit.  A thread continues the carried prefix pre2 / pre3
+// (np.cumprod up to slot i - 1) with row a, cur[i+1 .. j-1], row b, cur[j+1 .. T-1], one __dmul_rn each: numpy's order.  Returns the
+// number of pairs taken.  Bounded by T and list lengths; (i, j) and every barrier are workgroup-uniform, the k loop has no barrier.
+//
+// np.sum above 128 slots (workgroup form only) replaces two elements of numpy's recursion tree.  Both in one leaf block: that leaf
+// with both replaced, then the untouched siblings up to the root (M.sib[0 ..], as in the one-swap sweep).  In two leaves: the tree
+// node where their paths part (the lowest common ancestor) has slot i in its left child and slot j in its right; a thread sums each
+// leaf with its own element in it, adds the untouched siblings of each path up to that child (M.sib[SIB_MAX ..] for i,
+// M.sib[2 SIB_MAX ..] for j), adds left + right, and goes on up the common path — the recursion's own additions (a + b rounds as
+// b + a).  The sibling sums are formed per (i, j) by pw_sum, the waves taking them in turn.
+template <int NT>
+__device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, int32_t max_span) {
+    constexpr bool WAVES = NT > 64;
+    using Key = pair_key_t<NT>;
     const WideLds& L = M.L;
-    const int lane = threadIdx.x, T = S.T;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = S.T;
     const double* cand = S.cand;
     int taken = 0;
     double pre2 = 1.0, pre3 = 1.0;
     for (int i = 0; i < T; ++i) {
         const int bi = L.base[i], li = L.len[i];
-        for (int j = i + 1; j < T; ++j) {
-            const int bj = L.base[j], lj = L.len[j], n = li * lj;
+        const int j_end = max_span > 0 && max_span < T - 1 - i ? i + max_span + 1 : T;
+        for (int j = i + 1; j < j_end; ++j) {
+            int off = 0, ln = T, n_up = 0;                             // the block that holds both slots, its siblings up to the root
+            int off_i = 0, ln_i = 0, n_i = 0, off_j = 0, ln_j = 0, n_j = 0;      // two leaves: each slot's leaf and its path's length
+            bool two = false;
+            if constexpr (WAVES) {
+                // One walk in three stretches (part 0: the common path from the root, 1: slot i's below the parting node, 2: slot
+                // j's), so that pw_sum stands once; the waves take the siblings in turn.  Thread-uniform, no barrier inside.
+                int part = 0, o = 0, l = T, d = 0, turn = 0, right_o = 0, right_l = 0;
+                for (int step = 0; step < 3 * SIB_MAX + 4; ++step) {
+                    if (l <= 128 || d >= SIB_MAX) {                    // a leaf block ends the stretch
+                        if (part == 0) {
+                            off = o; ln = l; n_up = d;
+                            break;
+                        }
+                        if (part == 2) {
+                            off_j = o; ln_j = l; n_j = d;
+                            break;
+                        }
+                        off_i = o; ln_i = l; n_i = d;
+                        part = 2; o = right_o; l = right_l; d = 0;
+                        continue;
+                    }
+                    int n2 = l / 2;
+                    n2 -= n2 % 8;
+                    if (part == 0 && i < o + n2 && j >= o + n2) {      // i left, j right: the paths part here
+                        two = true;
+                        n_up = d;
+                        right_o = o + n2; right_l = l - n2;
+                        part = 1; l = n2; d = 0;
+                        continue;
+                    }
+                    int so, sl;
+                    if ((part == 2 ? j : i) < o + n2) {                // (common path: both slots are on slot i's side)
+                        so = o + n2; sl = l - n2; l = n2;
+                    } else {
+                        so = o; sl = n2; o += n2; l -= n2;
+                    }
+                    if (wave == (turn & (NT / 64 - 1))) {
+                        const double v = pw_sum(L.col0 + so, sl, lane);
+                        if (lane == 0) M.sib[part * SIB_MAX + d] = v;
+                    }
+                    ++turn;
+                    ++d;
+                }
+                __syncthreads();                                       // sib is written, red of the pair before is read
+            }
+            const int bj = L.base[j], lj = L.len[j];
+            const Key n = (Key)li * lj;
             const double rest_min = S.cr.min_without(i, j);
             const int rest_real = S.cr.n_real - (L.col0[i] > 0.0) - (L.col0[j] > 0.0);
             double bf = INFINITY;
-            int bk = INT_MAX;
-            for (int k = lane; k < n; k += 64) {                       // products beyond a wave: chunks, lowest k first
-                const int a = k / lj, b = k - a * lj;
+            Key bk = std::numeric_limits<Key>::max();
+            for (Key k = tid; k < n; k += NT) {                        // products beyond the workgroup: chunks, lowest k first
+                const int a = (int)(k / lj), b = (int)(k - (Key)a * lj);
                 const double* ra = cand + (size_t)(bi + a) * 4;
                 const double* rb = cand + (size_t)(bj + b) * 4;
                 const double a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
@@ -347,7 +424,21 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S) 
                     p2 = __dmul_rn(p2, L.col2[m]);
                     p3 = __dmul_rn(p3, L.col3[m]);
                 }
-                const double sum = pw_leaf_swapped(L.col0, T, i, a0, j, b0);
+                double sum;
+                if constexpr (WAVES) {
+                    if (two) {
+                        double left = pw_leaf_swapped(L.col0 + off_i, ln_i, i - off_i, a0);
+                        for (int d = n_i - 1; d >= 0; --d) left = __dadd_rn(left, M.sib[SIB_MAX + d]);
+                        double right = pw_leaf_swapped(L.col0 + off_j, ln_j, j - off_j, b0);
+                        for (int d = n_j - 1; d >= 0; --d) right = __dadd_rn(right, M.sib[2 * SIB_MAX + d]);
+                        sum = __dadd_rn(left, right);
+                    } else {
+                        sum = pw_leaf_swapped(L.col0 + off, ln, i - off, a0, j - off, b0);
+                    }
+                    for (int d = n_up - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
+                } else {
+                    sum = pw_leaf_swapped(L.col0, T, i, a0, j, b0);
+                }
                 const int n_real = rest_real + (a0 > 0.0) + (b0 > 0.0);
                 const double f = merit_of(sum, n_real, fmin(fmin(rest_min, a1), b1), p2, p3, L.bounds);
                 if (f < bf) {
@@ -356,9 +447,20 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S) 
                 }
             }
             wave_argmin(bf, bk, lane);
-            if (bf < S.fit) {                                          // wave-uniform
+            if constexpr (WAVES) {
+                Key* red_k = reinterpret_cast<Key*>(L.red + 4);        // red[4 .. 7]: the waves' 64-bit positions (cnt holds ints)
                 if (lane == 0) {
-                    const int a = bk / lj, b = bk - a * lj;
+                    L.red[wave] = bf;
+                    red_k[wave] = bk;
+                }
+                __syncthreads();
+                bf = L.red[0];
+                bk = red_k[0];
+                for (int w = 1; w < NT / 64; ++w) take_better(bf, bk, L.red[w], red_k[w]);
+            }
+            if (bf < S.fit) {                                          // workgroup-uniform
+                if (tid == 0) {
+                    const int a = (int)(bk / lj), b = (int)(bk - (Key)a * lj);
                     const double* ra = cand + (size_t)(bi + a) * 4;
                     const double* rb = cand + (size_t)(bj + b) * 4;
                     M.cur[i] = a;
@@ -377,6 +479,59 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S) 
     }
     return taken;
 }
+
+// Pair-swap descent of one problem, both forms: phase 0 = the one-swap sweeps; then up to max_rounds rounds of one pair sweep and,
+// where it moved, the one-swap sweeps again.  A round whose pair sweep moved nothing is the last (it is counted).  round_history[r] =
+// the merit after round r, past the last round the final value (max_rounds = 0: its one entry is phase 0's merit); converged = the
+// last pair sweep moved nothing and the last one-swap phase ended with a sweep that moved nothing (with a span: no pair within it).
+struct PairOut {
+    double* best_fitness; double* start_fitness; int32_t* best_pos; double* round_history;
+    int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged;
+};
+
+template <int NT, bool TABLE_IN_LDS>
+__device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+                                                      const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                      const int32_t* __restrict__ start_pos, int32_t max_sweeps, int32_t max_rounds,
+                                                      int32_t max_span, const PairOut& o) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int rh_ld = max_rounds > 1 ? max_rounds : 1;             // round_history has at least one entry per problem
+    double* rh = o.round_history + (size_t)p * rh_ld;
+    DescendState S;
+    if (!descend_load<NT, TABLE_IN_LDS>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, o.start_fitness, S)) {
+        not_searched(p, tid, NT, o.best_fitness, o.start_fitness, o.round_history, rh_ld, o.sweeps, o.moves);
+        if (tid == 0) {
+            o.rounds[p] = -1;
+            o.pair_moves[p] = 0;
+            o.converged[p] = 0;
+        }
+        return;
+    }
+    int sweeps = 0, moves = 0, rounds = 0, pair_moves = 0;
+    bool settled = false, still = false;                           // still: the last pair sweep moved nothing
+    one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+    while (rounds < max_rounds) {
+        const int taken = pair_sweep<NT>(M, S, max_span);
+        pair_moves += taken;
+        still = taken == 0;
+        if (!still) {
+            settled = false;                                       // max_sweeps = 0: no sweep follows the move
+            one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+        }
+        if (tid == 0) rh[rounds] = S.fit;
+        ++rounds;
+        if (still) break;
+    }
+    for (int r = rounds + tid; r < rh_ld; r += NT) rh[r] = S.fit;
+    descend_store<NT, TABLE_IN_LDS>(M, sh, S, o.best_fitness, o.best_pos);
+    if (tid == 0) {
+        o.sweeps[p] = sweeps;
+        o.moves[p] = moves;
+        o.rounds[p] = rounds;
+        o.pair_moves[p] = pair_moves;
+        o.converged[p] = still && settled;
+    }
+}
 }  // namespace
 
 // ---- lane form: one wavefront per problem (<= 64 slots) --------------------------------------------------------------------------------
@@ -393,58 +548,24 @@ __global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __
                               best_pos_out, history, sweeps_out, moves_out);
 }
 
-// ---- pair-swap descent, lane form only: one wavefront per problem (<= 64 slots), descend_kernel's LDS layout ------------------------------
-// Phase 0 = the one-swap sweeps; then up to max_rounds rounds of one pair sweep and, where it moved, the one-swap sweeps again.  A round
-// whose pair sweep moved nothing is the last (it is counted).  round_history[r] = the merit after round r, past the last round the final
-// value (max_rounds = 0: its one entry is phase 0's merit); converged = the last pair sweep moved nothing and the last one-swap phase
-// ended with a sweep that moved nothing.  No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths.
-struct PairOut {
-    double* best_fitness; double* start_fitness; int32_t* best_pos; double* round_history;
-    int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged;
-};
-
+// ---- pair-swap descent, lane form: one wavefront per problem (<= 64 slots), descend_kernel's LDS layout ----------------------------------
+// No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths.
 __global__ __launch_bounds__(64) void descend_pairs_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
                                                            const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
-                                                           int32_t max_sweeps, int32_t max_rounds, PairOut o) {
+                                                           int32_t max_sweeps, int32_t max_rounds, int32_t max_span, PairOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const DescendMem M = lane_mem(lds_raw);
-    const int p = blockIdx.x, lane = threadIdx.x;
-    const int rh_ld = max_rounds > 1 ? max_rounds : 1;             // round_history has at least one entry per problem
-    double* rh = o.round_history + (size_t)p * rh_ld;
-    DescendState S;
-    if (!descend_load<64, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, o.start_fitness, S)) {
-        not_searched(p, lane, 64, o.best_fitness, o.start_fitness, o.round_history, rh_ld, o.sweeps, o.moves);
-        if (lane == 0) {
-            o.rounds[p] = -1;
-            o.pair_moves[p] = 0;
-            o.converged[p] = 0;
-        }
-        return;
-    }
-    int sweeps = 0, moves = 0, rounds = 0, pair_moves = 0;
-    bool settled = false, still = false;                           // still: the last pair sweep moved nothing
-    one_swap_sweeps<64>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
-    while (rounds < max_rounds) {
-        const int taken = pair_sweep(M, S);
-        pair_moves += taken;
-        still = taken == 0;
-        if (!still) {
-            settled = false;                                       // max_sweeps = 0: no sweep follows the move
-            one_swap_sweeps<64>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
-        }
-        if (lane == 0) rh[rounds] = S.fit;
-        ++rounds;
-        if (still) break;
-    }
-    for (int r = rounds + lane; r < rh_ld; r += 64) rh[r] = S.fit;
-    descend_store<64, true>(M, sh, S, o.best_fitness, o.best_pos);
-    if (lane == 0) {
-        o.sweeps[p] = sweeps;
-        o.moves[p] = moves;
-        o.rounds[p] = rounds;
-        o.pair_moves[p] = pair_moves;
-        o.converged[p] = still && settled;
-    }
+    descend_pairs_problem<64, true>(lane_mem(lds_raw), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
+}
+
+// The workgroup form's carve-up (descend_wide_lds_bytes sizes it): WideLds, column 1, `sib_rows` rows of SIB_MAX sibling sums (one
+// for the one-swap sweeps, three for the pair sweep); cur is the problem's best_pos row, the table stays in global memory.
+__device__ __forceinline__ DescendMem wide_mem(unsigned char* lds_raw, int T, int sib_rows, int32_t* cur) {
+    DescendMem M;
+    M.col1 = M.L.carve(lds_raw, T, T + sib_rows * SIB_MAX);
+    M.sib = M.col1 + T;
+    M.cur = cur;
+    M.table = nullptr;
+    return M;
 }
 
 // ---- workgroup form: any slot count, 256 threads per problem ----------------------------------------------------------------------------
@@ -457,20 +578,27 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
                                                            int32_t* __restrict__ best_pos_out, double* __restrict__ history,
                                                            int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int T = sh.count(blockIdx.x);
-    DescendMem M;
-    M.col1 = M.L.carve(lds_raw, T, T + SIB_MAX);
-    M.sib = M.col1 + T;
-    M.cur = best_pos_out + sh.out_row(blockIdx.x);
-    M.table = nullptr;
+    const DescendMem M = wide_mem(lds_raw, sh.count(blockIdx.x), 1, best_pos_out + sh.out_row(blockIdx.x));
     descend_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness, best_pos_out,
                                 history, sweeps_out, moves_out);
 }
 
+// Pair-swap descent, workgroup form: the same rounds over the same state, the pair products spread over the 256 threads.
+__global__ __launch_bounds__(WNT) void descend_pairs_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                                 const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                                 const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                                 int32_t max_rounds, int32_t max_span, PairOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const DescendMem M = wide_mem(lds_raw, sh.count(blockIdx.x), 3, o.best_pos + sh.out_row(blockIdx.x));
+    descend_pairs_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
+}
+
 // LDS bytes one problem needs (host side).  Lane form: the columns + bounds + base / len / cur + its candidate table.  Workgroup
-// form: four columns, red[8] + bounds[4] + sib[SIB_MAX], cnt[4] + base / len tables.
+// form: four columns, red[8] + bounds[4] + sib[sib_rows][SIB_MAX], cnt[4] + base / len tables.
 static size_t descend_lds_bytes(int n_cand) { return (256 + 4 + (size_t)n_cand * 4) * sizeof(double) + 3 * 64 * sizeof(int); }
-static size_t descend_wide_lds_bytes(int T) { return ((size_t)4 * T + 12 + SIB_MAX) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int); }
+static size_t descend_wide_lds_bytes(int T, int sib_rows = 1) {
+    return ((size_t)4 * T + 12 + (size_t)sib_rows * SIB_MAX) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int);
+}
 
 extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
                                         const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
@@ -496,6 +624,26 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
                          max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
 }
 
+// The one launch of pair-swap descent, behind the argument checks of its two entries (`who` names the caller in the messages).  Lane
+// form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots slots within a CU.
+static int descend_pairs_launch(const char* who, bool use_wide, int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
+                                int32_t max_cand, const int32_t* cand_ptr, const double* cand, const double* bounds,
+                                const int32_t* start_pos, int32_t max_sweeps, int32_t max_rounds, int32_t max_span, double* best_rows,
+                                const PairOut& o, void* stream) {
+    if (!use_wide && max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the table in LDS)", who);
+    const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand);
+    auto too_large = [&]() -> int {
+        if (use_wide)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", who, max_slots, lds);
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d candidates) exceed a CU", who, lds, max_cand);
+    };
+    char entry[80];
+    snprintf(entry, sizeof(entry), "%s_f64%s", who, use_wide ? " (workgroup form)" : "");
+    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, n_lists, best_rows};
+    return search_launch(lds, too_large, use_wide ? descend_pairs_wide_kernel : descend_pairs_kernel, B, use_wide ? WNT : 64, stream, entry,
+                         sh, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, o);
+}
+
 extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
                                               const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
                                               int32_t max_sweeps, int32_t max_rounds, double* best_fitness, double* start_fitness,
@@ -508,15 +656,25 @@ extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr
     if (max_slots > 64)
         GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
                    "gnnpn_descend_ragged_f64 descends larger problems by single swaps", max_slots);
-    if (max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: max_cand must be >= 1 (it sizes the table in LDS)");
-    const size_t lds = descend_lds_bytes(max_cand);
-    auto too_large = [&]() -> int {
-        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: %zu B of LDS per problem (%d candidates) exceed a CU", lds, max_cand);
-    };
-    const Shape sh{prob_ptr, 0, max_slots, 64, max_cand, n_lists, best_rows};
     const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
-    return search_launch(lds, too_large, descend_pairs_kernel, B, 64, stream, "descend_pairs_ragged_f64", sh, cand_ptr, cand, bounds,
-                         start_pos, max_sweeps, max_rounds, o);
+    return descend_pairs_launch("descend_pairs_ragged", false, B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos,
+                                max_sweeps, max_rounds, 0, best_rows, o, stream);
+}
+
+extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
+                                                       int32_t max_cand, const int32_t* cand_ptr, const double* cand, const double* bounds,
+                                                       const int32_t* start_pos, int32_t max_sweeps, int32_t max_rounds, int32_t max_span,
+                                                       int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos,
+                                                       double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
+                                                       int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_span >= 0 && max_slots >= 1,
+                  "descend_pairs_windowed_ragged: bad argument");
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
+                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_windowed_ragged: null operand");
+    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
+    return descend_pairs_launch("descend_pairs_windowed_ragged", wide || max_slots > 64, B, prob_ptr, n_lists, max_slots, max_cand,
+                                cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, best_rows, o, stream);
 }
 
 

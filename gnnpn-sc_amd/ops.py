@@ -1131,6 +1131,10 @@ class SearchTables(dict):
         return descend_pairs_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
                                     max_rounds, max_slots=self["max_slots"], max_cand=self["max_cand"])
 
+    def descend_pairs_windowed(self, max_sweeps=16, max_rounds=4, max_span=0, wide=None):
+        return descend_pairs_windowed_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
+                                             max_rounds, max_span, max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
+
     def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
         """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
         return eswoa_ragged(self["prob_ptr"], self["cand_ptr"], self["len_init"], self["cand"], self["bounds"],
@@ -1290,13 +1294,15 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
 
 def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, middle, max_slots, max_cand, hist, hist_ld,
                     extra=()):
-    """descend_ragged and descend_pairs_ragged: the C entry ``entry`` over the ten leading operands they share, ``middle`` the one
-    scalar behind max_sweeps (wide / max_rounds), the history under the key ``hist`` with max(hist_ld, 1) columns, ``extra`` the
-    names of the [B] i32 outputs behind the seven fields."""
+    """descend_ragged, descend_pairs_ragged and descend_pairs_windowed_ragged: the C entry ``entry`` over the ten leading operands
+    they share, ``middle`` the scalars behind max_sweeps (wide / max_rounds / max_rounds, max_span, wide: an int or a tuple of them,
+    none negative), the history under the key ``hist`` with max(hist_ld, 1) columns, ``extra`` the names of the [B] i32 outputs
+    behind the seven fields."""
     dev = cand.device
     B = prob_ptr.numel() - 1
     n = cand_ptr.numel() - 1
-    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or middle < 0:
+    middle = tuple(middle) if isinstance(middle, (tuple, list)) else (middle,)
+    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or min(middle) < 0:
         raise GnnpnError(f"{who}: inconsistent operand sizes")
     max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
     out = _descent_fields(B, max_slots, max(int(hist_ld), 1), dev, rows=torch.zeros)
@@ -1306,7 +1312,7 @@ def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max
     fields = ("best_fitness", "start_fitness", "best_pos", "best_rows", hist, "sweeps", "moves", *extra)       # the C order
     check(getattr(_lib.load(), entry)(
         B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
-        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), middle,
+        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), *middle,
         *(dev_ptr(out[k], out[k].dtype, k) for k in fields), stream_ptr()), entry)
     if hist == "history":
         out[hist] = out[hist][:, :int(max_sweeps)]
@@ -1337,6 +1343,18 @@ def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps
     one-swap phases together), rounds, pair_moves [B] i32, converged [B] i32 (1: no single swap and no pair swap lowers the result)."""
     return _descend_launch("gnnpn_descend_pairs_ragged_f64", "descend_pairs_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
                            int(max_rounds), max_slots, max_cand, "round_history", max_rounds, ("rounds", "pair_moves", "converged"))
+
+
+def descend_pairs_windowed_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_span=0, max_slots=None,
+                                  max_cand=None, wide=None):
+    """descend_pairs_ragged at any slot count and over a window of neighbouring slots, a ragged batch in ONE launch
+    (gnnpn_descend_pairs_windowed_ragged_f64).  ``max_span`` = 0: every slot pair i < j; s > 0: only the pairs with j <= i + s, in the
+    same order — what makes a pair sweep affordable at hundreds of slots; converged then means that no single swap and no pair
+    within the span lowers the result.  ``wide``: the workgroup form for every problem (taken anyway above 64 slots; it keeps the
+    table in global memory).  Both forms give the same run.  Returns descend_pairs_ragged's dict."""
+    return _descend_launch("gnnpn_descend_pairs_windowed_ragged_f64", "descend_pairs_windowed_ragged", prob_ptr, cand_ptr, cand, bounds,
+                           start_pos, max_sweeps, (int(max_rounds), int(max_span), int(bool(wide))), max_slots, max_cand, "round_history",
+                           max_rounds, ("rounds", "pair_moves", "converged"))
 
 
 def descend_select(res, actions_all, n_slots):

@@ -187,6 +187,23 @@ def descend_pairs(services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, m
 
 
 @torch.no_grad()
+def descend_pairs_windowed(services, batch, out, max_sweeps=16, max_rounds=4, max_span=0, reduct=0, min_cost=None, patches=()):
+    """``descend_pairs`` at any slot count and over a window of neighbouring slots (gnnpn_descend_pairs_windowed_ragged_f64): the same
+    tables, the same search, the same dict.  ``max_span`` = 0: every slot pair; s > 0: only slots at most s apart, which is what
+    makes a pair sweep affordable at hundreds of slots (converged then means: no single swap and no pair within the span lowers the
+    result).  Problems of more than 64 slots run in the workgroup form (all of the batch, then).  A negative span or a negative
+    number of rounds raises GnnpnError.  ``ML2PNPipeline.descend_pairs_windowed`` is this, as a method."""
+    if int(max_rounds) < 0 or int(max_span) < 0:
+        raise ops.GnnpnError(f"descend_pairs_windowed: the number of rounds and the span must be >= 0, got {max_rounds} and {max_span}")
+    actions = out["actions"]
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    res = tabs.descend_pairs_windowed(max_sweeps, int(max_rounds), int(max_span))
+    res["n_slots"] = tabs["n_slots"]
+    return _quality(res, min_cost, actions.device)
+
+
+@torch.no_grad()
 def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
     """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
     [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
@@ -382,6 +399,12 @@ class ML2PNPipeline:
         call: ``run`` / ``capture`` are unchanged."""
         return descend_pairs(services, batch, out, max_sweeps=max_sweeps, max_rounds=max_rounds, reduct=reduct, min_cost=min_cost,
                              patches=patches)
+
+    def descend_pairs_windowed(self, services, batch, out, max_sweeps=16, max_rounds=4, max_span=0, reduct=0, min_cost=None, patches=()):
+        """Pair-swap descent at any slot count, over slots at most ``max_span`` apart (0: all): module-level
+        ``descend_pairs_windowed`` (it needs no network).  An extra call: ``run`` / ``capture`` are unchanged."""
+        return descend_pairs_windowed(services, batch, out, max_sweeps=max_sweeps, max_rounds=max_rounds, max_span=max_span, reduct=reduct,
+                                      min_cost=min_cost, patches=patches)
 
     def descend_starts_pairs(self, services, batch, starts, max_sweeps=16, pair_rounds=4, reduct=0, min_cost=None, patches=()):
         """Multi-start pair-swap descent: module-level ``descend_starts_pairs`` (it needs no network).  An extra call."""

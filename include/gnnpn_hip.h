@@ -827,6 +827,29 @@ int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n
                                    int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
                                    int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream);
 
+/* Pair-swap descent at any slot count and over a window of neighbouring slots (csrc/descend.hip).  New: no reference counterpart, as
+ * gnnpn_descend_pairs_ragged_f64, whose search, operands, outputs and not-searched record this entry has, with two more arguments:
+ *   max_span      0: every pair i < j, as gnnpn_descend_pairs_ragged_f64; s > 0: only the pairs with j <= i + s, in the same order (the
+ *                 pair sweep then costs O(T * s) pairs instead of O(T^2)); converged = 1 then means: no single swap and no pair
+ *                 within the span lowers the result;
+ *   wide          0: the lane form (one wavefront per problem, the table in LDS) where max_slots <= 64, the workgroup form above;
+ *                 != 0: the workgroup form for every problem — 256 threads per problem, the columns of the composition in LDS, the
+ *                 table in global memory (list lengths bounded by the int32 cand_ptr only; pair positions a * len_j + b are held in
+ *                 64 bits), best_pos doubling as the working composition.  Both forms give the same run.
+ * np.sum above 128 slots follows numpy's recursion with two elements replaced: both in one leaf block, or one in each of two (each
+ * leaf summed with its element, the untouched sibling blocks of both paths added up to the node where the paths part, left + right
+ * there, the common path above).  A problem that is not searched: as gnnpn_descend_pairs_ragged_f64, with "more than max_slots lists"
+ * in the workgroup form (64 does not bound it, max_cand is not read).
+ * No atomics, no waits on other workgroups, every loop bounded by max_rounds, max_sweeps, T or a list length.  GNNPN_E_ARG: negative
+ * sizes (max_span < 0 among them), max_slots < 1, null operands.  GNNPN_E_UNSUP, nothing launched: lane form with max_cand < 1 or a
+ * table beyond a CU's LDS; workgroup form whose columns for max_slots slots (about 40 B per slot) exceed a CU's LDS. */
+int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                            const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                            int32_t max_sweeps, int32_t max_rounds, int32_t max_span, int32_t wide, double* best_fitness,
+                                            double* start_fitness, int32_t* best_pos, double* best_rows, double* round_history,
+                                            int32_t* sweeps, int32_t* moves, int32_t* rounds, int32_t* pair_moves, int32_t* converged,
+                                            void* stream);
+
 /* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
  * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
  * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest

@@ -33,6 +33,10 @@
                                          # place of the descent artefact, the same format plus rounds / pair_moves / converged;
                                          # with --woa ES-WOA starts from the pair-descended composition
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] --pairs[=ROUNDS] --span=N   # ... at ANY number of slots, exchanging only
+                                         # slots at most N apart (N = 0: every pair; above 64 slots one workgroup per problem):
+                                         # ML+2PN+pairs.txt gains a `span` entry.  Not with --all-starts or --woa
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -191,6 +195,15 @@ def main(argv):
         if rounds is not None and (sweeps is None or int(rounds) < 1):
             print("--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round")
             return 1
+        span = next((a.split("=", 1)[1] for a in flags if a.startswith("--span=")), "" if "--span" in flags else None)
+        if span is not None:
+            if rounds is None or not span.lstrip("+").isdigit():
+                print("--span=N: needs --pairs[=ROUNDS] and N >= 0 (0: every slot pair)")
+                return 1
+            if "--all-starts" in flags or "--woa" in flags:
+                print("--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at "
+                      "most 64 slots)")
+                return 1
         with open(f"./data/{ds}/serviceFeature.data") as f:
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
@@ -214,7 +227,12 @@ def main(argv):
             best["all_starts"] = True
         if rounds is not None:                                      # pair-swap descent in place of the one-swap descent
             best["pair_rounds"] = int(rounds)
-        ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
+        if span is not None:                                        # ... at any slot count, over slots at most N apart
+            best["pair_span"] = int(span)
+        if "pair_span" in best:                                     # (refused above beside --woa and --all-starts)
+            ML2PN.infer_pairs_windowed(ds, net, low, high, K, epoch, **best)
+        else:
+            ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
     return 0
