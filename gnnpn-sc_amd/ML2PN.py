@@ -93,8 +93,20 @@ def infer_pairs_windowed(dataset, net, low, high, n_per, epoch=-1, device="cuda:
                   pair_rounds, pair_span)
 
 
+def infer_pairs_shortlist(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1,
+                          sample_seed=None, descend=16, all_starts=False, pair_rounds=4, pair_span=0, pair_rank=0):
+    """``infer_pairs_windowed`` whose pair sweeps look only at the ``pair_rank`` best candidates of each slot (>= 0; 0: all;
+    pipeline.descend_pairs_shortlist): ``ML+2PN+pairs.txt`` in ``infer``'s format plus ``span`` and ``top``.  With ``all_starts`` (and
+    samples > 1) the descent runs from every replica (pipeline.descend_starts_pairs_shortlist): ``ML+2PN+multistart+pairs.txt``.
+    Without ``woa``, whose start takes the full pair sweep of at most 64 slots."""
+    if descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0 or pair_rank is None or pair_rank < 0:
+        raise ValueError("ML2PN.infer_pairs_shortlist: pair_rank needs descend, at least one round, a span >= 0 and a rank >= 0")
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts,
+                  pair_rounds, pair_span, pair_rank)
+
+
 def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, pair_rounds,
-           pair_span):
+           pair_span, pair_rank=None):
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -147,6 +159,7 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
     if woa is not None or descend is not None:
         _refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
                             **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds, pair_span=pair_span,
+                            pair_rank=pair_rank,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
@@ -165,14 +178,17 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
 
 
 def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, pair_rounds=None,
-                         pair_span=None):
+                         pair_span=None, pair_rank=None):
     """refine_test_quarter; ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
-    with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``."""
+    with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``.  ``pair_rank`` (>= 0, with ``pair_span``, without
+    ES-WOA): pipeline.descend_pairs_shortlist (with ``starts``: descend_starts_pairs_shortlist) with that span and rank, and the file
+    gains ``top`` too."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import DeviceBatch, descend as descend_actions, descend_pairs, descend_pairs_windowed, descend_starts, descend_starts_pairs, refine
+    from .pipeline import (DeviceBatch, descend as descend_actions, descend_pairs, descend_pairs_shortlist, descend_pairs_windowed,
+                           descend_starts, descend_starts_pairs, descend_starts_pairs_shortlist, refine)
     counters = lambda r: {k: r[k].cpu().tolist() for k in ("rounds", "pair_moves", "converged")}      # noqa: E731
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
@@ -195,14 +211,22 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
         t0 = time.time()
         if multi:
             rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
-            res = descend_starts_pairs(svc, batch, rows, pair_rounds=pair_rounds, **kw) if pairs else descend_starts(svc, batch, rows, **kw)
+            if pair_rank is not None:
+                res = descend_starts_pairs_shortlist(svc, batch, rows, pair_rounds=pair_rounds, pair_span=pair_span, pair_rank=pair_rank, **kw)
+            elif pairs:
+                res = descend_starts_pairs(svc, batch, rows, pair_rounds=pair_rounds, **kw)
+            else:
+                res = descend_starts(svc, batch, rows, **kw)
+        elif pair_rank is not None:
+            res = descend_pairs_shortlist(svc, batch, out, max_rounds=pair_rounds, max_span=pair_span, max_rank=pair_rank, **kw)
         elif pair_span is not None:
             res = descend_pairs_windowed(svc, batch, out, max_rounds=pair_rounds, max_span=pair_span, **kw)
         else:
             res = descend_pairs(svc, batch, out, max_rounds=pair_rounds, **kw) if pairs else descend_actions(svc, batch, out, **kw)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name,
-                                  extra=({**counters(res), **({} if pair_span is None else {"span": pair_span})}) if pairs else None)
+                                  extra=({**counters(res), **({} if pair_span is None else {"span": pair_span}),
+                                         **({} if pair_rank is None else {"top": pair_rank})}) if pairs else None)
         if multi:
             out = {"actions": res["actions"]}        # refine below rebuilds the winner's tables and repeats its descent
     if descend is None or popSize > 0:

@@ -17,6 +17,11 @@
 // every two at most max_span apart), every pair of their candidates (one pair per thread, the same carried prefix, two rows replaced),
 // and the one-swap sweeps run again after a sweep that moved — the same sweeps, not a second statement of them
 // (tests/pair_descent_reference.py and, with the span, tests/pair_window_reference.py are its Python restatements).
+//
+// Over shortlists (descend_pairs_shortlist_kernel, descend_pairs_shortlist_wide_kernel): before every pair sweep each slot keeps the
+// max_rank candidates whose single swap into the current composition has the lowest merit — the one-swap sweep's own evaluation
+// (slot_path, one_swap_merit), ranked by counting in LDS — and the sweep tries only pairs of kept candidates
+// (tests/pair_shortlist_reference.py).  The four builds without shortlists compile none of it.
 #include "woa_eval.h"
 
 #include <climits>
@@ -92,13 +97,18 @@ __device__ __forceinline__ void wave_argmin(double& f, long long& c, int lane) {
 constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halves (to within 7 terms) per level
 
 // Where a problem's state lives: the columns of cur (L.col0, col1, L.col2, L.col3), the base / len tables and the bounds in LDS;
-// cur, in LDS or the problem's best_pos row; the candidate table's LDS copy (lane form); red / cnt / sib (workgroup form).
+// cur, in LDS or the problem's best_pos row; the candidate table's LDS copy (lane form); red / cnt / sib (workgroup form).  The
+// shortlist builds add mer / rk (one list's single-swap merits and their ranks) and list (every slot's shortlist), all in LDS.
 struct DescendMem {
     WideLds L;
     double* col1;      // [T] column 1 (np.min)
     double* sib;       // [SIB_MAX] sums of the sibling blocks on np.sum's path to the current slot (pair sweep: three such rows)
     int* cur;          // [T]
     double* table;     // [n_cand][4]
+    double* mer;       // [max_cand] shortlist builds: the single-swap merit of every candidate of the slot being ranked
+    int* rk;           // [max_cand] ... and its rank in the (merit, position) order
+    int* list;         // [T][rank] ... every slot's shortlist, positions ascending, -1 past its length
+    int rank;          // row length of list: min(max_rank, max_cand)
 };
 
 // The lane form's carve-up (descend_lds_bytes sizes it): the four columns of cur [4][64] (figure_of_merit's layout), bounds [4],
@@ -187,7 +197,58 @@ __device__ __forceinline__ bool descend_load(const DescendMem& M, const Shape& s
 // `moves`, `settled` = the last sweep moved nothing (unchanged where max_sweeps = 0); hist (or NULL) takes the merit after every sweep.
 // Above 128 slots np.sum follows numpy's recursion: only the block of at most 128 terms that holds slot j changes with the
 // candidate, so a thread sums that block with its own value in it and adds the sums of the untouched sibling blocks (`sib`, formed
-// once per slot by pw_sum) on the way up, deepest first — the same additions as the recursion (a + b rounds as b + a).
+// once per slot by pw_sum) on the way up, deepest first — the same additions as the recursion (a + b rounds as b + a).  The two
+// pieces below (slot_path, one_swap_merit) are that evaluation; the shortlist pass (form_shortlists) calls them too.
+
+// np.sum's leaf block of slot j and, in the workgroup form, the length of its path from the root: M.sib[0 .. depth - 1] get the
+// sums of the untouched sibling blocks, root first (wave 0 forms them by pw_sum), and a barrier follows.  Workgroup-uniform.
+struct SlotPath {
+    int off, ln, depth;
+};
+template <int NT>
+__device__ __forceinline__ SlotPath slot_path(const DescendMem& M, int T, int j) {
+    int off = 0, ln = T, depth = 0;
+    if constexpr (NT > 64) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        while (ln > 128 && depth < SIB_MAX) {
+            int n2 = ln / 2;
+            n2 -= n2 % 8;
+            int so, sl;
+            if (j < off + n2) {
+                so = off + n2; sl = ln - n2; ln = n2;
+            } else {
+                so = off; sl = n2; off += n2; ln -= n2;
+            }
+            if (wave == 0) {
+                const double v = pw_sum(M.L.col0 + so, sl, lane);
+                if (lane == 0) M.sib[depth] = v;
+            }
+            ++depth;
+        }
+        __syncthreads();                                              // sib is written
+    }
+    return SlotPath{off, ln, depth};
+}
+
+// The merit of the current composition with slot j alone replaced by row r, by ONE thread: the one statement of the single-swap
+// evaluation, for the one-swap sweeps and for the ranking behind the shortlists.  pre2 / pre3: np.cumprod up to slot j - 1; the
+// thread continues both chains through cur[j+1 .. T-1] and forms np.sum with element j replaced (its leaf, then the siblings up).
+template <int NT>
+__device__ __forceinline__ double one_swap_merit(const DescendMem& M, const Carried& cr, const double* r, int T, int j, const SlotPath& sp,
+                                                 double old0, double pre2, double pre3) {
+    const WideLds& L = M.L;
+    const double q0 = r[0], q1 = r[1];
+    double p2 = j == 0 ? r[2] : __dmul_rn(pre2, r[2]), p3 = j == 0 ? r[3] : __dmul_rn(pre3, r[3]);
+    for (int i = j + 1; i < T; ++i) {
+        p2 = __dmul_rn(p2, L.col2[i]);
+        p3 = __dmul_rn(p3, L.col3[i]);
+    }
+    double sum = pw_leaf_swapped(L.col0 + sp.off, sp.ln, j - sp.off, q0);
+    if constexpr (NT > 64)
+        for (int d = sp.depth - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
+    return merit_of(sum, cr.real_with(old0, q0), cr.min_with(j, q1), p2, p3, L.bounds);
+}
+
 template <int NT>
 __device__ __forceinline__ void one_swap_sweeps(const DescendMem& M, DescendState& S, int32_t max_sweeps, double* __restrict__ hist,
                                                 int& sweeps, int& moves, bool& settled) {
@@ -202,41 +263,13 @@ __device__ __forceinline__ void one_swap_sweeps(const DescendMem& M, DescendStat
         bool improved = false;
         double pre2 = 1.0, pre3 = 1.0;                                // np.cumprod of columns 2 and 3 up to slot j - 1
         for (int j = 0; j < T; ++j) {
-            int off = 0, ln = T, depth = 0;                           // np.sum's leaf block of slot j
-            if constexpr (WAVES) {                                    // its path from the root: the siblings' sums, root first
-                while (ln > 128 && depth < SIB_MAX) {
-                    int n2 = ln / 2;
-                    n2 -= n2 % 8;
-                    int so, sl;
-                    if (j < off + n2) {
-                        so = off + n2; sl = ln - n2; ln = n2;
-                    } else {
-                        so = off; sl = n2; off += n2; ln -= n2;
-                    }
-                    if (wave == 0) {
-                        const double v = pw_sum(L.col0 + so, sl, lane);
-                        if (lane == 0) M.sib[depth] = v;
-                    }
-                    ++depth;
-                }
-                __syncthreads();                                      // sib is written, red / cnt of slot j - 1 are read
-            }
+            const SlotPath sp = slot_path<NT>(M, T, j);               // (workgroup form: red / cnt of slot j - 1 are read behind it)
             const int bj = L.base[j], lj = L.len[j];
             const double old0 = L.col0[j];
             double bf = INFINITY;
             int bc = INT_MAX;
             for (int c = tid; c < lj; c += NT) {                      // lists longer than the workgroup: chunks, lowest position first
-                const double* r = cand + (size_t)(bj + c) * 4;
-                const double q0 = r[0], q1 = r[1];
-                double p2 = j == 0 ? r[2] : __dmul_rn(pre2, r[2]), p3 = j == 0 ? r[3] : __dmul_rn(pre3, r[3]);
-                for (int i = j + 1; i < T; ++i) {
-                    p2 = __dmul_rn(p2, L.col2[i]);
-                    p3 = __dmul_rn(p3, L.col3[i]);
-                }
-                double sum = pw_leaf_swapped(L.col0 + off, ln, j - off, q0);
-                if constexpr (WAVES)
-                    for (int d = depth - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
-                const double f = merit_of(sum, cr.real_with(old0, q0), cr.min_with(j, q1), p2, p3, L.bounds);
+                const double f = one_swap_merit<NT>(M, cr, cand + (size_t)(bj + c) * 4, T, j, sp, old0, pre2, pre3);
                 if (f < bf) {
                     bf = f;
                     bc = c;
@@ -326,6 +359,59 @@ __device__ __forceinline__ void descend_problem(const DescendMem& M, const Shape
     }
 }
 
+// (merit, position) order of the shortlists, is (f2, c2) before (f, c): plain < on the merits, the lower position among equals
+// (-0.0 and 0.0 are equal), a NaN after every number and NaNs among themselves by position.
+__device__ __forceinline__ bool ranks_before(double f2, int c2, double f, int c) {
+    if (f2 < f) return true;
+    if (f < f2) return false;
+    const bool n2 = f2 != f2, n = f != f;
+    return n2 == n ? c2 < c : n;
+}
+
+// The shortlists of one pair sweep, from the state in LDS by the NT threads of the problem's workgroup: per slot j the min(rank,
+// len_j) candidates whose single swap into the CURRENT composition has the lowest merit, positions ascending, into M.list[j][..]
+// (-1 behind them).  Per slot: the merits of the list (one_swap_merit, thread = one candidate, chunks beyond the workgroup) into
+// M.mer; every candidate's rank by counting the candidates before it (len_j reads of M.mer, every thread the same address); a kept
+// candidate's place = the kept ones at lower positions.  A list no longer than `rank` is kept whole and nothing is evaluated.
+// Nothing moves here.  Bounded by T and list lengths; j, keep and every barrier are workgroup-uniform.
+template <int NT>
+__device__ __forceinline__ void form_shortlists(const DescendMem& M, const DescendState& S) {
+    const WideLds& L = M.L;
+    const int tid = threadIdx.x, T = S.T, rank = M.rank;
+    const double* cand = S.cand;
+    double pre2 = 1.0, pre3 = 1.0;                                    // np.cumprod of columns 2 and 3 up to slot j - 1
+    for (int j = 0; j < T; ++j) {
+        const int bj = L.base[j], lj = L.len[j];
+        const int keep = lj < rank ? lj : rank;
+        int* row = M.list + (size_t)j * rank;
+        if (keep == lj) {
+            for (int c = tid; c < lj; c += NT) row[c] = c;
+        } else {
+            const SlotPath sp = slot_path<NT>(M, T, j);
+            const double old0 = L.col0[j];
+            for (int c = tid; c < lj; c += NT) M.mer[c] = one_swap_merit<NT>(M, S.cr, cand + (size_t)(bj + c) * 4, T, j, sp, old0, pre2, pre3);
+            __syncthreads();
+            for (int c = tid; c < lj; c += NT) {
+                const double f = M.mer[c];
+                int r = 0;
+                for (int c2 = 0; c2 < lj; ++c2) r += ranks_before(M.mer[c2], c2, f, c);
+                M.rk[c] = r;
+            }
+            __syncthreads();
+            for (int c = tid; c < lj; c += NT) {
+                if (M.rk[c] >= keep) continue;
+                int at = 0;
+                for (int c2 = 0; c2 < c; ++c2) at += M.rk[c2] < keep;
+                row[at] = c;
+            }
+        }
+        for (int k = keep + tid; k < rank; k += NT) row[k] = -1;
+        __syncthreads();                                              // the row stands; mer / rk / sib are free for slot j + 1
+        pre2 = j == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[j]);
+        pre3 = j == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[j]);
+    }
+}
+
 // A pair product's position k = a * len_j + b: an int where the table is in LDS (a CU's LDS holds under 5000 candidates), 64 bits in
 // the workgroup form, whose lists only the int32 cand_ptr bounds (len_i + len_j < 2^31, so k < 2^62).
 template <int NT>
@@ -344,7 +430,10 @@ using pair_key_t = std::conditional_t<(NT > 64), long long, int>;
 // leaf with its own element in it, adds the untouched siblings of each path up to that child (M.sib[SIB_MAX ..] for i,
 // M.sib[2 SIB_MAX ..] for j), adds left + right, and goes on up the common path — the recursion's own additions (a + b rounds as
 // b + a).  The sibling sums are formed per (i, j) by pw_sum, the waves taking them in turn.
-template <int NT>
+//
+// SHORT: the sweep runs over the shortlists M.list (form_shortlists, formed by the caller before the sweep and left as they are
+// through it): a and b are the ia-th and ib-th kept position of their lists, k = ia * |S_j| + ib; everything else is the same code.
+template <int NT, bool SHORT = false>
 __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, int32_t max_span) {
     constexpr bool WAVES = NT > 64;
     using Key = pair_key_t<NT>;
@@ -354,7 +443,8 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, 
     int taken = 0;
     double pre2 = 1.0, pre3 = 1.0;
     for (int i = 0; i < T; ++i) {
-        const int bi = L.base[i], li = L.len[i];
+        const int bi = L.base[i], li = SHORT && M.rank < L.len[i] ? M.rank : L.len[i];      // SHORT: |S_i|
+        const int* si = SHORT ? M.list + (size_t)i * M.rank : nullptr;
         const int j_end = max_span > 0 && max_span < T - 1 - i ? i + max_span + 1 : T;
         for (int j = i + 1; j < j_end; ++j) {
             int off = 0, ln = T, n_up = 0;                             // the block that holds both slots, its siblings up to the root
@@ -402,14 +492,16 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, 
                 }
                 __syncthreads();                                       // sib is written, red of the pair before is read
             }
-            const int bj = L.base[j], lj = L.len[j];
+            const int bj = L.base[j], lj = SHORT && M.rank < L.len[j] ? M.rank : L.len[j];
+            const int* sj = SHORT ? M.list + (size_t)j * M.rank : nullptr;
             const Key n = (Key)li * lj;
             const double rest_min = S.cr.min_without(i, j);
             const int rest_real = S.cr.n_real - (L.col0[i] > 0.0) - (L.col0[j] > 0.0);
             double bf = INFINITY;
             Key bk = std::numeric_limits<Key>::max();
             for (Key k = tid; k < n; k += NT) {                        // products beyond the workgroup: chunks, lowest k first
-                const int a = (int)(k / lj), b = (int)(k - (Key)a * lj);
+                const int ia = (int)(k / lj), ib = (int)(k - (Key)ia * lj);
+                const int a = SHORT ? si[ia] : ia, b = SHORT ? sj[ib] : ib;
                 const double* ra = cand + (size_t)(bi + a) * 4;
                 const double* rb = cand + (size_t)(bj + b) * 4;
                 const double a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
@@ -460,7 +552,8 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, 
             }
             if (bf < S.fit) {                                          // workgroup-uniform
                 if (tid == 0) {
-                    const int a = (int)(bk / lj), b = (int)(bk - (Key)a * lj);
+                    const int ia = (int)(bk / lj), ib = (int)(bk - (Key)ia * lj);
+                    const int a = SHORT ? si[ia] : ia, b = SHORT ? sj[ib] : ib;
                     const double* ra = cand + (size_t)(bi + a) * 4;
                     const double* rb = cand + (size_t)(bj + b) * 4;
                     M.cur[i] = a;
@@ -489,11 +582,30 @@ struct PairOut {
     int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged;
 };
 
-template <int NT, bool TABLE_IN_LDS>
+// SHORT (the shortlist builds): every pair sweep is preceded by form_shortlists and runs over what it formed; so.shortlist (or NULL)
+// [B, stride, max_rank] takes the shortlists of the last pair sweep that ran: row s of a problem = M.list[s], -1 past its length,
+// past the LDS row (max_rank > M.rank: no list is that long) and past T; all -1 where no pair sweep ran or nothing was searched.
+struct ShortOut {
+    int32_t* shortlist;
+    int32_t max_rank;
+};
+
+template <int NT>
+__device__ __forceinline__ void shortlist_store(const DescendMem& M, const Shape& sh, const ShortOut& so, int T, bool formed) {
+    if (!so.shortlist) return;
+    const size_t n = (size_t)sh.stride * so.max_rank;
+    int32_t* out = so.shortlist + (size_t)blockIdx.x * n;
+    for (size_t x = threadIdx.x; x < n; x += NT) {
+        const int s = (int)(x / so.max_rank), k = (int)(x - (size_t)s * so.max_rank);
+        out[x] = formed && s < T && k < M.rank ? M.list[(size_t)s * M.rank + k] : -1;
+    }
+}
+
+template <int NT, bool TABLE_IN_LDS, bool SHORT = false>
 __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
                                                       const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                       const int32_t* __restrict__ start_pos, int32_t max_sweeps, int32_t max_rounds,
-                                                      int32_t max_span, const PairOut& o) {
+                                                      int32_t max_span, const PairOut& o, const ShortOut& so = ShortOut{nullptr, 0}) {
     const int p = blockIdx.x, tid = threadIdx.x;
     const int rh_ld = max_rounds > 1 ? max_rounds : 1;             // round_history has at least one entry per problem
     double* rh = o.round_history + (size_t)p * rh_ld;
@@ -505,13 +617,15 @@ __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const
             o.pair_moves[p] = 0;
             o.converged[p] = 0;
         }
+        if constexpr (SHORT) shortlist_store<NT>(M, sh, so, 0, false);
         return;
     }
     int sweeps = 0, moves = 0, rounds = 0, pair_moves = 0;
     bool settled = false, still = false;                           // still: the last pair sweep moved nothing
     one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
     while (rounds < max_rounds) {
-        const int taken = pair_sweep<NT>(M, S, max_span);
+        if constexpr (SHORT) form_shortlists<NT>(M, S);
+        const int taken = pair_sweep<NT, SHORT>(M, S, max_span);
         pair_moves += taken;
         still = taken == 0;
         if (!still) {
@@ -524,6 +638,7 @@ __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const
     }
     for (int r = rounds + tid; r < rh_ld; r += NT) rh[r] = S.fit;
     descend_store<NT, TABLE_IN_LDS>(M, sh, S, o.best_fitness, o.best_pos);
+    if constexpr (SHORT) shortlist_store<NT>(M, sh, so, S.T, rounds > 0);
     if (tid == 0) {
         o.sweeps[p] = sweeps;
         o.moves[p] = moves;
@@ -555,6 +670,22 @@ __global__ __launch_bounds__(64) void descend_pairs_kernel(Shape sh, const int32
                                                            int32_t max_sweeps, int32_t max_rounds, int32_t max_span, PairOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     descend_pairs_problem<64, true>(lane_mem(lds_raw), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
+}
+
+// ---- pair-swap descent over shortlists, lane form: descend_pairs_kernel with the shortlist pass before every pair sweep -------------------
+// LDS: descend_kernel's layout, then mer [max_cand] f64, rk [max_cand] i32, list [stride][rank] i32 (descend_short_lds_bytes).
+// No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths, max_rank.
+__global__ __launch_bounds__(64) void descend_pairs_shortlist_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                                     const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                                     const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                                     int32_t max_rounds, int32_t max_span, int32_t rank, PairOut o, ShortOut so) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    DescendMem M = lane_mem(lds_raw);
+    M.mer = M.table + (size_t)sh.max_cand * 4;
+    M.rk = reinterpret_cast<int*>(M.mer + sh.max_cand);
+    M.list = M.rk + sh.max_cand;
+    M.rank = rank;
+    descend_pairs_problem<64, true, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o, so);
 }
 
 // The workgroup form's carve-up (descend_wide_lds_bytes sizes it): WideLds, column 1, `sib_rows` rows of SIB_MAX sibling sums (one
@@ -593,11 +724,39 @@ __global__ __launch_bounds__(WNT) void descend_pairs_wide_kernel(Shape sh, const
     descend_pairs_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
 }
 
+// Pair-swap descent over shortlists, workgroup form.  LDS: descend_pairs_wide_kernel's, with mer [max_cand] f64 behind the sibling
+// sums and rk [max_cand], list [T][rank] i32 behind the base / len tables (descend_short_lds_bytes).
+__global__ __launch_bounds__(WNT) void descend_pairs_shortlist_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                                           const double* __restrict__ cand_g,
+                                                                           const double* __restrict__ bounds_g,
+                                                                           const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                                           int32_t max_rounds, int32_t max_span, int32_t rank, PairOut o,
+                                                                           ShortOut so) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int T = sh.count(blockIdx.x);
+    DescendMem M;
+    M.col1 = M.L.carve(lds_raw, T, T + 3 * SIB_MAX + sh.max_cand);
+    M.sib = M.col1 + T;
+    M.mer = M.sib + 3 * SIB_MAX;
+    M.cur = o.best_pos + sh.out_row(blockIdx.x);
+    M.table = nullptr;
+    M.rk = M.L.len + T;
+    M.list = M.rk + sh.max_cand;
+    M.rank = rank;
+    descend_pairs_problem<WNT, false, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o, so);
+}
+
 // LDS bytes one problem needs (host side).  Lane form: the columns + bounds + base / len / cur + its candidate table.  Workgroup
 // form: four columns, red[8] + bounds[4] + sib[sib_rows][SIB_MAX], cnt[4] + base / len tables.
 static size_t descend_lds_bytes(int n_cand) { return (256 + 4 + (size_t)n_cand * 4) * sizeof(double) + 3 * 64 * sizeof(int); }
 static size_t descend_wide_lds_bytes(int T, int sib_rows = 1) {
     return ((size_t)4 * T + 12 + (size_t)sib_rows * SIB_MAX) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int);
+}
+
+// The shortlist builds: the same, plus mer [max_cand] f64, rk [max_cand] i32 and list [max_slots][rank] i32.
+static size_t descend_short_lds_bytes(bool use_wide, int max_slots, int max_cand, int rank) {
+    return (use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand)) + (size_t)max_cand * (sizeof(double) + sizeof(int)) +
+           (size_t)max_slots * rank * sizeof(int);
 }
 
 extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
@@ -675,6 +834,40 @@ extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t*
     const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
     return descend_pairs_launch("descend_pairs_windowed_ragged", wide || max_slots > 64, B, prob_ptr, n_lists, max_slots, max_cand,
                                 cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, best_rows, o, stream);
+}
+
+extern "C" int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
+                                                        int32_t max_cand, const int32_t* cand_ptr, const double* cand, const double* bounds,
+                                                        const int32_t* start_pos, int32_t max_sweeps, int32_t max_rounds, int32_t max_span,
+                                                        int32_t max_rank, int32_t wide, double* best_fitness, double* start_fitness,
+                                                        int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps,
+                                                        int32_t* moves, int32_t* rounds, int32_t* pair_moves, int32_t* converged,
+                                                        int32_t* shortlist, void* stream) {
+    const char* who = "descend_pairs_shortlist_ragged";
+    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_span >= 0 && max_rank >= 0 && max_slots >= 1,
+                  "descend_pairs_shortlist_ragged: bad argument");
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
+                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_shortlist_ragged: null operand");
+    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
+    const bool use_wide = wide || max_slots > 64;
+    if (max_rank == 0)                                                // no shortlist: the windowed entry's launch, nothing extra
+        return descend_pairs_launch(who, use_wide, B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps,
+                                    max_rounds, max_span, best_rows, o, stream);
+    if (max_cand < 1)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the merit buffer, and in the lane form the table, in LDS)", who);
+    const int rank = max_rank < max_cand ? max_rank : max_cand;       // no list is longer than its problem's table
+    const size_t lds = descend_short_lds_bytes(use_wide, max_slots, max_cand, rank);
+    auto too_large = [&]() -> int {
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
+                   max_slots, max_cand, rank, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
+    };
+    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, n_lists, best_rows};
+    const ShortOut so{shortlist, max_rank};
+    return search_launch(lds, too_large, use_wide ? descend_pairs_shortlist_wide_kernel : descend_pairs_shortlist_kernel, B,
+                         use_wide ? WNT : 64, stream,
+                         use_wide ? "descend_pairs_shortlist_ragged_f64 (workgroup form)" : "descend_pairs_shortlist_ragged_f64", sh, cand_ptr,
+                         cand, bounds, start_pos, max_sweeps, max_rounds, max_span, rank, o, so);
 }
 
 

@@ -1135,6 +1135,11 @@ class SearchTables(dict):
         return descend_pairs_windowed_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
                                              max_rounds, max_span, max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
 
+    def descend_pairs_shortlist(self, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0, wide=None):
+        return descend_pairs_shortlist_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"],
+                                              max_sweeps, max_rounds, max_span, max_rank, max_slots=self["max_slots"],
+                                              max_cand=self["max_cand"], wide=wide)
+
     def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
         """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
         return eswoa_ragged(self["prob_ptr"], self["cand_ptr"], self["len_init"], self["cand"], self["bounds"],
@@ -1293,11 +1298,12 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
 
 
 def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, middle, max_slots, max_cand, hist, hist_ld,
-                    extra=()):
-    """descend_ragged, descend_pairs_ragged and descend_pairs_windowed_ragged: the C entry ``entry`` over the ten leading operands
-    they share, ``middle`` the scalars behind max_sweeps (wide / max_rounds / max_rounds, max_span, wide: an int or a tuple of them,
-    none negative), the history under the key ``hist`` with max(hist_ld, 1) columns, ``extra`` the names of the [B] i32 outputs
-    behind the seven fields."""
+                    extra=(), last=None):
+    """descend_ragged, descend_pairs_ragged, descend_pairs_windowed_ragged and descend_pairs_shortlist_ragged: the C entry ``entry``
+    over the ten leading operands they share, ``middle`` the scalars behind max_sweeps (wide / max_rounds / max_rounds, max_span, wide
+    / max_rounds, max_span, max_rank, wide: an int or a tuple of them, none negative), the history under the key ``hist`` with
+    max(hist_ld, 1) columns, ``extra`` the names of the [B] i32 outputs behind the seven fields, ``last`` = (key, columns | None) one
+    more i32 output [B, max_slots, columns] behind them (None: a NULL pointer and no such key)."""
     dev = cand.device
     B = prob_ptr.numel() - 1
     n = cand_ptr.numel() - 1
@@ -1310,10 +1316,15 @@ def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max
         out[hist] = out.pop("history")
     out.update({k: torch.empty(B, dtype=I32, device=dev) for k in extra})
     fields = ("best_fitness", "start_fitness", "best_pos", "best_rows", hist, "sweeps", "moves", *extra)       # the C order
+    tail = ()
+    if last is not None:
+        if last[1] is not None:
+            out[last[0]] = torch.empty(B, max_slots, int(last[1]), dtype=I32, device=dev)
+        tail = (dev_ptr(out.get(last[0]), I32, last[0], allow_none=True),)
     check(getattr(_lib.load(), entry)(
         B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
         dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), *middle,
-        *(dev_ptr(out[k], out[k].dtype, k) for k in fields), stream_ptr()), entry)
+        *(dev_ptr(out[k], out[k].dtype, k) for k in fields), *tail, stream_ptr()), entry)
     if hist == "history":
         out[hist] = out[hist][:, :int(max_sweeps)]
     return out
@@ -1355,6 +1366,25 @@ def descend_pairs_windowed_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, m
     return _descend_launch("gnnpn_descend_pairs_windowed_ragged_f64", "descend_pairs_windowed_ragged", prob_ptr, cand_ptr, cand, bounds,
                            start_pos, max_sweeps, (int(max_rounds), int(max_span), int(bool(wide))), max_slots, max_cand, "round_history",
                            max_rounds, ("rounds", "pair_moves", "converged"))
+
+
+def descend_pairs_shortlist_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0,
+                                   max_slots=None, max_cand=None, wide=None, return_shortlist=False):
+    """descend_pairs_windowed_ragged whose pair sweeps look only at a shortlist of each slot's best candidates, a ragged batch in ONE
+    launch (gnnpn_descend_pairs_shortlist_ragged_f64).  ``max_rank`` = 0: no shortlist, descend_pairs_windowed_ragged's launch and
+    result.  m > 0: at the start of every pair sweep each slot keeps the min(m, len) candidates whose single swap into the current
+    composition has the lowest merit (the lowest position among equals, a NaN last), and a slot pair costs at most m * m evaluations
+    instead of len_i * len_j; the shortlists are a snapshot for the whole sweep.  m is clamped to the longest list (one small copy to
+    the host): by definition the same search, and it keeps the optional output small.  converged = 1 means: no single swap, and no
+    pair within the span and the final composition's shortlists, lowers the result.  Returns descend_pairs_ragged's dict;
+    ``return_shortlist``: plus shortlist [B, max_slots, m] i32, the shortlists of the last pair sweep that ran, positions ascending,
+    -1 past a shortlist's length and a problem's count, all -1 where no pair sweep ran or the problem was not searched."""
+    if int(max_rank) > 0 and isinstance(cand_ptr, torch.Tensor) and cand_ptr.is_cuda and cand_ptr.numel() > 1:
+        max_rank = min(int(max_rank), max(int((cand_ptr[1:] - cand_ptr[:-1]).max().item()), 1))
+    return _descend_launch("gnnpn_descend_pairs_shortlist_ragged_f64", "descend_pairs_shortlist_ragged", prob_ptr, cand_ptr, cand, bounds,
+                           start_pos, max_sweeps, (int(max_rounds), int(max_span), int(max_rank), int(bool(wide))), max_slots, max_cand,
+                           "round_history", max_rounds, ("rounds", "pair_moves", "converged"),
+                           last=("shortlist", int(max_rank) if return_shortlist else None))
 
 
 def descend_select(res, actions_all, n_slots):

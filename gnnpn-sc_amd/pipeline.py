@@ -204,6 +204,25 @@ def descend_pairs_windowed(services, batch, out, max_sweeps=16, max_rounds=4, ma
 
 
 @torch.no_grad()
+def descend_pairs_shortlist(services, batch, out, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0, reduct=0, min_cost=None, patches=()):
+    """``descend_pairs_windowed`` whose pair sweeps look only at the ``max_rank`` best candidates of each slot
+    (gnnpn_descend_pairs_shortlist_ragged_f64): the same tables, the same dict.  ``max_rank`` = 0: no shortlist, that function's
+    result.  m > 0: before every pair sweep each slot keeps the m candidates whose single swap into the current composition has the
+    lowest merit, so a slot pair costs at most m * m evaluations (converged then means: no single swap, and no pair within the span
+    and the final composition's shortlists, lowers the result).  Any slot count.  A negative span, rank or number of rounds raises
+    GnnpnError.  ``ML2PNPipeline.descend_pairs_shortlist`` is this, as a method."""
+    if int(max_rounds) < 0 or int(max_span) < 0 or int(max_rank) < 0:
+        raise ops.GnnpnError(f"descend_pairs_shortlist: the number of rounds, the span and the rank must be >= 0, got {max_rounds}, "
+                             f"{max_span} and {max_rank}")
+    actions = out["actions"]
+    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                              actions, reduct=reduct, patches=patches)
+    res = tabs.descend_pairs_shortlist(max_sweeps, int(max_rounds), int(max_span), int(max_rank))
+    res["n_slots"] = tabs["n_slots"]
+    return _quality(res, min_cost, actions.device)
+
+
+@torch.no_grad()
 def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
     """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
     [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
@@ -229,7 +248,23 @@ def descend_starts_pairs(services, batch, starts, max_sweeps=16, pair_rounds=4, 
     return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, int(pair_rounds))
 
 
-def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pair_rounds):
+@torch.no_grad()
+def descend_starts_pairs_shortlist(services, batch, starts, max_sweeps=16, pair_rounds=4, pair_span=0, pair_rank=0, reduct=0, min_cost=None,
+                                   patches=()):
+    """``descend_starts_pairs`` whose B * N rows go through gnnpn_descend_pairs_shortlist_ragged_f64: any slot count, only slots at
+    most ``pair_span`` apart (0: every pair) and only the ``pair_rank`` best candidates of each slot (0: all) — what makes pair-swap
+    descent affordable N times over; the same selection (gnnpn_descend_select_f64, unchanged) picks the winner.  ``pair_span`` =
+    ``pair_rank`` = 0 at up to 64 slots is ``descend_starts_pairs``' result in every shared field (``pair_rounds`` = 0 included: then
+    the rows' one-swap descent, reported in the pair-swap format).  A negative span, rank or number of rounds raises GnnpnError.
+    ``ML2PNPipeline.descend_starts_pairs_shortlist`` is this, as a method."""
+    if int(pair_rounds) < 0 or int(pair_span) < 0 or int(pair_rank) < 0:
+        raise ops.GnnpnError(f"descend_starts_pairs_shortlist: the number of rounds, the span and the rank must be >= 0, got {pair_rounds}, "
+                             f"{pair_span} and {pair_rank}")
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, int(pair_rounds),
+                           shortlist=(int(pair_span), int(pair_rank)))
+
+
+def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pair_rounds, shortlist=None):
     all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
     if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
         raise ops.GnnpnError(f"descend_starts: starts [B, N, T, 8|9] expected, got {tuple(getattr(all_rows, 'shape', ()))}")
@@ -237,11 +272,15 @@ def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patch
     B, N = all_rows.shape[:2]
     tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                                        all_rows, reduct=reduct, patches=patches)
-    per_row = _descend_tables(tabs, max_sweeps, int(pair_rounds) if pair_rounds else None)
+    if shortlist is not None:                                           # (span, rank): the shortlist entry, at any slot count
+        per_row = tabs.descend_pairs_shortlist(max_sweeps, int(pair_rounds), *shortlist)
+        per_row["n_slots"] = tabs["n_slots"]
+    else:
+        per_row = _descend_tables(tabs, max_sweeps, int(pair_rounds) if pair_rounds else None)
     res = ops.descend_select(per_row, all_rows, tabs["n_slots"])        # (the rounds' merits and counters too, where there are any)
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
-    if pair_rounds:
+    if pair_rounds or shortlist is not None:
         res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
     return _quality(res, min_cost, all_rows.device)
 
@@ -405,6 +444,20 @@ class ML2PNPipeline:
         ``descend_pairs_windowed`` (it needs no network).  An extra call: ``run`` / ``capture`` are unchanged."""
         return descend_pairs_windowed(services, batch, out, max_sweeps=max_sweeps, max_rounds=max_rounds, max_span=max_span, reduct=reduct,
                                       min_cost=min_cost, patches=patches)
+
+    def descend_pairs_shortlist(self, services, batch, out, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0, reduct=0, min_cost=None,
+                                patches=()):
+        """Pair-swap descent of ``out["actions"]`` over shortlists of each slot's best candidates: module-level
+        ``descend_pairs_shortlist`` (it needs no network).  An extra call: ``run`` / ``capture`` are unchanged."""
+        return descend_pairs_shortlist(services, batch, out, max_sweeps=max_sweeps, max_rounds=max_rounds, max_span=max_span,
+                                       max_rank=max_rank, reduct=reduct, min_cost=min_cost, patches=patches)
+
+    def descend_starts_pairs_shortlist(self, services, batch, starts, max_sweeps=16, pair_rounds=4, pair_span=0, pair_rank=0, reduct=0,
+                                       min_cost=None, patches=()):
+        """Multi-start pair-swap descent at any slot count, over a span and shortlists: module-level ``descend_starts_pairs_shortlist``
+        (it needs no network).  An extra call."""
+        return descend_starts_pairs_shortlist(services, batch, starts, max_sweeps=max_sweeps, pair_rounds=pair_rounds, pair_span=pair_span,
+                                              pair_rank=pair_rank, reduct=reduct, min_cost=min_cost, patches=patches)
 
     def descend_starts_pairs(self, services, batch, starts, max_sweeps=16, pair_rounds=4, reduct=0, min_cost=None, patches=()):
         """Multi-start pair-swap descent: module-level ``descend_starts_pairs`` (it needs no network).  An extra call."""

@@ -850,6 +850,37 @@ int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t* prob_ptr, 
                                             int32_t* sweeps, int32_t* moves, int32_t* rounds, int32_t* pair_moves, int32_t* converged,
                                             void* stream);
 
+/* Pair-swap descent over a shortlist of each slot's best candidates (csrc/descend.hip).  New: no reference counterpart, as
+ * gnnpn_descend_pairs_windowed_ragged_f64 (the comment and prototype right above), whose search, operands, outputs, forms and
+ * not-searched record this entry has, with two more arguments:
+ *   max_rank      m = 0: no shortlist — that entry's launch and result, nothing extra is paid.  m > 0: at the START of every pair sweep
+ *                 each slot s gets a shortlist S_s: every candidate c of list s gets the merit of the CURRENT composition with slot s
+ *                 alone replaced by c (the value the one-swap sweep forms, the same code); the candidates are ordered by (merit,
+ *                 position) under plain < — a NaN after every number, NaNs among themselves by position, -0.0 equal to 0.0 — and S_s
+ *                 is the first min(m, len_s) of that order, then sorted by position ascending (the current member is treated as any
+ *                 other).  The shortlists stay as formed through the whole sweep, pair moves included; the next round's sweep forms new
+ *                 ones.  For a slot pair (i, j) only (a, b) in S_i x S_j are evaluated, at pair position k = ia * |S_j| + ib (ia, ib:
+ *                 the places in the position-sorted shortlists); among equal merits the lowest k wins.  Pair order, max_span, strict
+ *                 <, the move rule, the re-descent, rounds, round_history are unchanged.  m >= every list's length is that entry's
+ *                 run in every field.  converged = 1 means: no single swap lowers the result, and no pair within the span and within
+ *                 the final composition's shortlists does (a sweep that moved nothing used the shortlists of the composition it
+ *                 ended with);
+ *   shortlist     [B, max_slots, max_rank] int32, or NULL: the shortlists of the LAST pair sweep that ran, row s = S_s by position, -1
+ *                 past |S_s| and past the problem's T; all -1 where no pair sweep ran (max_rounds = 0) or the problem is not searched.
+ *                 Not touched with max_rank = 0 (it has no entries).
+ * With m > 0 max_cand is read in BOTH forms: the merits and ranks of one list (12 B per candidate of the largest problem) and the
+ * shortlists (4 B * max_slots * min(m, max_cand)) live in LDS beside the form's own state, and a problem with more than max_cand
+ * candidates is not searched in the workgroup form either.  A list no longer than m is kept whole without being evaluated.
+ * No atomics, no waits on other workgroups, every loop bounded by max_rounds, max_sweeps, T, a list length or max_rank.  GNNPN_E_ARG:
+ * that entry's cases and max_rank < 0.  GNNPN_E_UNSUP, nothing launched: that entry's cases; with m > 0 also max_cand < 1 in the
+ * workgroup form, and state + merits + ranks + shortlists beyond a CU's LDS. */
+int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                             const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                             int32_t max_sweeps, int32_t max_rounds, int32_t max_span, int32_t max_rank, int32_t wide,
+                                             double* best_fitness, double* start_fitness, int32_t* best_pos, double* best_rows,
+                                             double* round_history, int32_t* sweeps, int32_t* moves, int32_t* rounds, int32_t* pair_moves,
+                                             int32_t* converged, int32_t* shortlist, void* stream);
+
 /* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
  * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
  * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest

@@ -37,6 +37,12 @@
                                          # slots at most N apart (N = 0: every pair; above 64 slots one workgroup per problem):
                                          # ML+2PN+pairs.txt gains a `span` entry.  Not with --all-starts or --woa
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] --pairs[=ROUNDS] [--span=N] --top=M [--samples=N --all-starts]   # ... and
+                                         # exchanging only the M candidates of each slot whose single swap is best (M = 0: all; a
+                                         # slot pair then costs M * M evaluations): the artefact gains a `top` entry; with
+                                         # --all-starts from every replica, at any slot count and span
+                                         # (ML+2PN+multistart+pairs.txt).  Not with --woa
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -196,11 +202,19 @@ def main(argv):
             print("--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round")
             return 1
         span = next((a.split("=", 1)[1] for a in flags if a.startswith("--span=")), "" if "--span" in flags else None)
+        top = next((a.split("=", 1)[1] for a in flags if a.startswith("--top=")), "" if "--top" in flags else None)
+        if top is not None:
+            if rounds is None or not top.lstrip("+").isdigit():
+                print("--top=M: needs --pairs[=ROUNDS] and M >= 0 (0: every candidate)")
+                return 1
+            if "--woa" in flags:
+                print("--top=M: not with --woa (the ES-WOA start takes the full pair sweep of at most 64 slots)")
+                return 1
         if span is not None:
             if rounds is None or not span.lstrip("+").isdigit():
                 print("--span=N: needs --pairs[=ROUNDS] and N >= 0 (0: every slot pair)")
                 return 1
-            if "--all-starts" in flags or "--woa" in flags:
+            if ("--all-starts" in flags and top is None) or "--woa" in flags:
                 print("--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at "
                       "most 64 slots)")
                 return 1
@@ -229,7 +243,9 @@ def main(argv):
             best["pair_rounds"] = int(rounds)
         if span is not None:                                        # ... at any slot count, over slots at most N apart
             best["pair_span"] = int(span)
-        if "pair_span" in best:                                     # (refused above beside --woa and --all-starts)
+        if top is not None:                                         # ... over the M best candidates of each slot (refused beside --woa)
+            ML2PN.infer_pairs_shortlist(ds, net, low, high, K, epoch, pair_rank=int(top), **best)
+        elif "pair_span" in best:                                   # (refused above beside --woa and --all-starts)
             ML2PN.infer_pairs_windowed(ds, net, low, high, K, epoch, **best)
         else:
             ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
