@@ -187,15 +187,14 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
-    from .pipeline import (DeviceBatch, descend as descend_actions, descend_pairs, descend_pairs_shortlist, descend_pairs_windowed,
-                           descend_starts, descend_starts_pairs, descend_starts_pairs_shortlist, refine)
+    from . import pipeline as pl
     counters = lambda r: {k: r[k].cpu().tolist() for k in ("rounds", "pair_moves", "converged")}      # noqa: E731
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
     first = P // 4 * 3
     n = actions.shape[0]
     _, pb = ld.tables_from_dataset(ds, first, first + n)
-    batch = DeviceBatch.from_problems(pb, dev)
+    batch = pl.DeviceBatch.from_problems(pb, dev)
     seeds = None if seed is None else [(seed + first + i) & 0xFFFFFFFFFFFFFFFF for i in range(n)]
     out = {"actions": torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float64)).to(dev)}
     min_cost = ds["minCostList"][first:first + n]
@@ -209,20 +208,15 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
         kw = {"max_sweeps": descend, "reduct": reduct, "min_cost": min_cost}
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        if multi:
-            rows = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev)
-            if pair_rank is not None:
-                res = descend_starts_pairs_shortlist(svc, batch, rows, pair_rounds=pair_rounds, pair_span=pair_span, pair_rank=pair_rank, **kw)
-            elif pairs:
-                res = descend_starts_pairs(svc, batch, rows, pair_rounds=pair_rounds, **kw)
-            else:
-                res = descend_starts(svc, batch, rows, **kw)
-        elif pair_rank is not None:
-            res = descend_pairs_shortlist(svc, batch, out, max_rounds=pair_rounds, max_span=pair_span, max_rank=pair_rank, **kw)
-        elif pair_span is not None:
-            res = descend_pairs_windowed(svc, batch, out, max_rounds=pair_rounds, max_span=pair_span, **kw)
-        else:
-            res = descend_pairs(svc, batch, out, max_rounds=pair_rounds, **kw) if pairs else descend_actions(svc, batch, out, **kw)
+        # the function, chosen once by how many of (rounds, span, rank) it takes: each option needs the one before it, and a span
+        # without a rank is not for starts
+        given = 3 if pair_rank is not None else 2 if pair_span is not None and not multi else 1 if pairs else 0
+        search = {(False, 0): pl.descend, (False, 1): pl.descend_pairs, (False, 2): pl.descend_pairs_windowed,
+                  (False, 3): pl.descend_pairs_shortlist, (True, 0): pl.descend_starts, (True, 1): pl.descend_starts_pairs,
+                  (True, 3): pl.descend_starts_pairs_shortlist}[multi, given]
+        names = ("pair_rounds", "pair_span", "pair_rank") if multi else ("max_rounds", "max_span", "max_rank")
+        kw.update(zip(names[:given], (pair_rounds, pair_span, pair_rank)))
+        res = search(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev) if multi else out, **kw)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name,
                                   extra=({**counters(res), **({} if pair_span is None else {"span": pair_span}),
@@ -235,8 +229,8 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
         if descend is None:
             res = pipe.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost)
         else:
-            res = refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend,
-                         pair_rounds=pair_rounds or 0)
+            res = pl.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend,
+                            pair_rounds=pair_rounds or 0)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first)
     return written

@@ -783,24 +783,57 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
                          max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
 }
 
-// The one launch of pair-swap descent, behind the argument checks of its two entries (`who` names the caller in the messages).  Lane
-// form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots slots within a CU.
-static int descend_pairs_launch(const char* who, bool use_wide, int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
-                                int32_t max_cand, const int32_t* cand_ptr, const double* cand, const double* bounds,
-                                const int32_t* start_pos, int32_t max_sweeps, int32_t max_rounds, int32_t max_span, double* best_rows,
-                                const PairOut& o, void* stream) {
-    if (!use_wide && max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the table in LDS)", who);
-    const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand);
-    auto too_large = [&]() -> int {
-        if (use_wide)
-            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", who, max_slots, lds);
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d candidates) exceed a CU", who, lds, max_cand);
-    };
+// The arguments of a pair entry: the shortlist entry's parameter list in include/gnnpn_hip.h, name for name and in its order, so an
+// entry passes its own list through as it stands, with 0 / NULL where it has no span, rank, wide or shortlist.
+struct PairArgs {
+    int32_t B; const int32_t* prob_ptr; int32_t n_lists, max_slots, max_cand; const int32_t* cand_ptr; const double* cand;
+    const double* bounds; const int32_t* start_pos; int32_t max_sweeps, max_rounds, max_span, max_rank, wide;
+    double* best_fitness; double* start_fitness; int32_t* best_pos; double* best_rows; double* round_history;
+    int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged; int32_t* shortlist; void* stream;
+};
+
+// The three pair entries: their argument checks (`who` names the entry in every message) and the one launch of pair-swap descent.
+// Lane form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots slots within a CU.
+// max_rank > 0: the shortlist builds, whose merit buffer, rank buffer and lists come on top in both forms; they run with the rank
+// clamped to max_cand (no list is longer than its problem's table).  max_rank = 0: the same launch from every entry, nothing extra.
+static int descend_pairs_entry(const char* who, bool lane_only, const PairArgs& a) {
+    GNNPN_REQUIRE(a.B >= 0 && a.n_lists >= 0 && a.max_sweeps >= 0 && a.max_rounds >= 0 && a.max_span >= 0 && a.max_rank >= 0 &&
+                  a.max_slots >= 1, "%s: bad argument", who);
+    if (a.B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(a.prob_ptr && a.cand_ptr && a.cand && a.bounds && a.start_pos && a.best_fitness && a.start_fitness && a.best_pos &&
+                  a.round_history && a.sweeps && a.moves && a.rounds && a.pair_moves && a.converged, "%s: null operand", who);
+    if (lane_only && a.max_slots > 64)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
+                   "gnnpn_descend_ragged_f64 descends larger problems by single swaps", who, a.max_slots);
+    const PairOut o{a.best_fitness, a.start_fitness, a.best_pos, a.round_history, a.sweeps, a.moves, a.rounds, a.pair_moves, a.converged};
+    const bool use_wide = a.wide || a.max_slots > 64;
+    const int max_slots = a.max_slots, max_cand = a.max_cand, nt = use_wide ? WNT : 64;
     char entry[80];
     snprintf(entry, sizeof(entry), "%s_f64%s", who, use_wide ? " (workgroup form)" : "");
-    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, n_lists, best_rows};
-    return search_launch(lds, too_large, use_wide ? descend_pairs_wide_kernel : descend_pairs_kernel, B, use_wide ? WNT : 64, stream, entry,
-                         sh, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, o);
+    if (a.max_rank == 0) {
+        if (!use_wide && max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the table in LDS)", who);
+        const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand);
+        auto too_large = [&]() -> int {
+            if (use_wide)
+                GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", who, max_slots, lds);
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d candidates) exceed a CU", who, lds, max_cand);
+        };
+        const Shape sh{a.prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, a.n_lists, a.best_rows};
+        return search_launch(lds, too_large, use_wide ? descend_pairs_wide_kernel : descend_pairs_kernel, a.B, nt, a.stream, entry, sh,
+                             a.cand_ptr, a.cand, a.bounds, a.start_pos, a.max_sweeps, a.max_rounds, a.max_span, o);
+    }
+    if (max_cand < 1)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the merit buffer, and in the lane form the table, in LDS)", who);
+    const int rank = a.max_rank < max_cand ? a.max_rank : max_cand;
+    const size_t lds = descend_short_lds_bytes(use_wide, max_slots, max_cand, rank);
+    auto too_large = [&]() -> int {
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
+                   max_slots, max_cand, rank, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
+    };
+    const Shape sh{a.prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, a.n_lists, a.best_rows};
+    return search_launch(lds, too_large, use_wide ? descend_pairs_shortlist_wide_kernel : descend_pairs_shortlist_kernel, a.B, nt, a.stream,
+                         entry, sh, a.cand_ptr, a.cand, a.bounds, a.start_pos, a.max_sweeps, a.max_rounds, a.max_span, rank, o,
+                         ShortOut{a.shortlist, a.max_rank});
 }
 
 extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
@@ -808,16 +841,9 @@ extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr
                                               int32_t max_sweeps, int32_t max_rounds, double* best_fitness, double* start_fitness,
                                               int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
                                               int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_slots >= 1, "descend_pairs_ragged: bad argument");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
-                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_ragged: null operand");
-    if (max_slots > 64)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_pairs_ragged: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
-                   "gnnpn_descend_ragged_f64 descends larger problems by single swaps", max_slots);
-    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
-    return descend_pairs_launch("descend_pairs_ragged", false, B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos,
-                                max_sweeps, max_rounds, 0, best_rows, o, stream);
+    return descend_pairs_entry("descend_pairs_ragged", true,
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, 0, 0, 0,
+         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, nullptr, stream});
 }
 
 extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
@@ -826,14 +852,9 @@ extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t*
                                                        int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos,
                                                        double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
                                                        int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_span >= 0 && max_slots >= 1,
-                  "descend_pairs_windowed_ragged: bad argument");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
-                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_windowed_ragged: null operand");
-    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
-    return descend_pairs_launch("descend_pairs_windowed_ragged", wide || max_slots > 64, B, prob_ptr, n_lists, max_slots, max_cand,
-                                cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, best_rows, o, stream);
+    return descend_pairs_entry("descend_pairs_windowed_ragged", false,
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, 0, wide,
+         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, nullptr, stream});
 }
 
 extern "C" int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
@@ -843,31 +864,9 @@ extern "C" int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t
                                                         int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps,
                                                         int32_t* moves, int32_t* rounds, int32_t* pair_moves, int32_t* converged,
                                                         int32_t* shortlist, void* stream) {
-    const char* who = "descend_pairs_shortlist_ragged";
-    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_rounds >= 0 && max_span >= 0 && max_rank >= 0 && max_slots >= 1,
-                  "descend_pairs_shortlist_ragged: bad argument");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && round_history &&
-                  sweeps && moves && rounds && pair_moves && converged, "descend_pairs_shortlist_ragged: null operand");
-    const PairOut o{best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged};
-    const bool use_wide = wide || max_slots > 64;
-    if (max_rank == 0)                                                // no shortlist: the windowed entry's launch, nothing extra
-        return descend_pairs_launch(who, use_wide, B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps,
-                                    max_rounds, max_span, best_rows, o, stream);
-    if (max_cand < 1)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the merit buffer, and in the lane form the table, in LDS)", who);
-    const int rank = max_rank < max_cand ? max_rank : max_cand;       // no list is longer than its problem's table
-    const size_t lds = descend_short_lds_bytes(use_wide, max_slots, max_cand, rank);
-    auto too_large = [&]() -> int {
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
-                   max_slots, max_cand, rank, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
-    };
-    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, n_lists, best_rows};
-    const ShortOut so{shortlist, max_rank};
-    return search_launch(lds, too_large, use_wide ? descend_pairs_shortlist_wide_kernel : descend_pairs_shortlist_kernel, B,
-                         use_wide ? WNT : 64, stream,
-                         use_wide ? "descend_pairs_shortlist_ragged_f64 (workgroup form)" : "descend_pairs_shortlist_ragged_f64", sh, cand_ptr,
-                         cand, bounds, start_pos, max_sweeps, max_rounds, max_span, rank, o, so);
+    return descend_pairs_entry("descend_pairs_shortlist_ragged", false,
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, max_rank, wide,
+         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, shortlist, stream});
 }
 
 

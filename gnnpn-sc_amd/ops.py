@@ -1123,22 +1123,22 @@ class SearchTables(dict):
     """The candidate tables of a batch as woa_candidates / woa_candidates_replicas return them: a dict of their keys whose
     methods pass its own operands to the search wrappers below (nothing but forwarding: the wrappers do the checking)."""
 
+    def _to(self, wrapper, *search, **kw):
+        """The descent ``wrapper`` over the tables' own five operands and two sizes, ``search`` the arguments between them."""
+        return wrapper(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], *search,
+                       max_slots=self["max_slots"], max_cand=self["max_cand"], **kw)
+
     def descend(self, max_sweeps=16, wide=None):
-        return descend_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
-                              max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
+        return self._to(descend_ragged, max_sweeps, wide=wide)
 
     def descend_pairs(self, max_sweeps=16, max_rounds=4):
-        return descend_pairs_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
-                                    max_rounds, max_slots=self["max_slots"], max_cand=self["max_cand"])
+        return self._to(descend_pairs_ragged, max_sweeps, max_rounds)
 
     def descend_pairs_windowed(self, max_sweeps=16, max_rounds=4, max_span=0, wide=None):
-        return descend_pairs_windowed_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"], max_sweeps,
-                                             max_rounds, max_span, max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
+        return self._to(descend_pairs_windowed_ragged, max_sweeps, max_rounds, max_span, wide=wide)
 
     def descend_pairs_shortlist(self, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0, wide=None):
-        return descend_pairs_shortlist_ragged(self["prob_ptr"], self["cand_ptr"], self["cand"], self["bounds"], self["start_pos"],
-                                              max_sweeps, max_rounds, max_span, max_rank, max_slots=self["max_slots"],
-                                              max_cand=self["max_cand"], wide=wide)
+        return self._to(descend_pairs_shortlist_ragged, max_sweeps, max_rounds, max_span, max_rank, wide=wide)
 
     def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
         """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
@@ -1297,37 +1297,25 @@ def eswoa_ragged(prob_ptr, cand_ptr, len_init, cand, bounds, start_pos, pop, max
     return best_fit, best_pos, history[:, :int(max_iter)], draws, best_rows
 
 
-def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, middle, max_slots, max_cand, hist, hist_ld,
-                    extra=(), last=None):
-    """descend_ragged, descend_pairs_ragged, descend_pairs_windowed_ragged and descend_pairs_shortlist_ragged: the C entry ``entry``
-    over the ten leading operands they share, ``middle`` the scalars behind max_sweeps (wide / max_rounds / max_rounds, max_span, wide
-    / max_rounds, max_span, max_rank, wide: an int or a tuple of them, none negative), the history under the key ``hist`` with
-    max(hist_ld, 1) columns, ``extra`` the names of the [B] i32 outputs behind the seven fields, ``last`` = (key, columns | None) one
-    more i32 output [B, max_slots, columns] behind them (None: a NULL pointer and no such key)."""
+def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, scalars, max_slots, max_cand, hist_ld, behind=()):
+    """What every descent entry shares: the operand checks, the largest problem, descend_ragged's seven fields (the history with
+    ``hist_ld`` columns) and the call of the C entry ``entry`` — the ten leading operands, ``scalars`` (the ints behind max_sweeps,
+    none negative), the seven fields, then ``behind``: (key, columns) of the i32 outputs an entry has behind them, in the C order —
+    () a [B] vector, (m,) [B, max_slots, m], None a NULL pointer and no such key.  Returns the dict of all of them."""
     dev = cand.device
     B = prob_ptr.numel() - 1
     n = cand_ptr.numel() - 1
-    middle = tuple(middle) if isinstance(middle, (tuple, list)) else (middle,)
-    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or min(middle) < 0:
+    if n != start_pos.numel() or bounds.shape != (B, 4) or int(max_sweeps) < 0 or min(scalars) < 0:
         raise GnnpnError(f"{who}: inconsistent operand sizes")
     max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
-    out = _descent_fields(B, max_slots, max(int(hist_ld), 1), dev, rows=torch.zeros)
-    if hist != "history":
-        out[hist] = out.pop("history")
-    out.update({k: torch.empty(B, dtype=I32, device=dev) for k in extra})
-    fields = ("best_fitness", "start_fitness", "best_pos", "best_rows", hist, "sweeps", "moves", *extra)       # the C order
-    tail = ()
-    if last is not None:
-        if last[1] is not None:
-            out[last[0]] = torch.empty(B, max_slots, int(last[1]), dtype=I32, device=dev)
-        tail = (dev_ptr(out.get(last[0]), I32, last[0], allow_none=True),)
+    fields = _descent_fields(B, max_slots, hist_ld, dev, rows=torch.zeros)          # (a dict in the C order)
+    more = {k: torch.empty(B, *((max_slots, *cols) if cols else ()), dtype=I32, device=dev) for k, cols in behind if cols is not None}
     check(getattr(_lib.load(), entry)(
         B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
-        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), *middle,
-        *(dev_ptr(out[k], out[k].dtype, k) for k in fields), *tail, stream_ptr()), entry)
-    if hist == "history":
-        out[hist] = out[hist][:, :int(max_sweeps)]
-    return out
+        dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), *scalars,
+        *(dev_ptr(t, t.dtype, k) for k, t in fields.items()), *(dev_ptr(more.get(k), I32, k, allow_none=True) for k, _ in behind),
+        stream_ptr()), entry)
+    return {**fields, **more}
 
 
 def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_slots=None, max_cand=None, wide=None):
@@ -1339,8 +1327,20 @@ def descend_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, m
     exceeds the LDS).  Returns a dict of device tensors: best_fitness [B] f64, start_fitness [B] f64, best_pos [B, max_slots] i32
     and best_rows [B, max_slots, 4] f64 (0 past a problem's count), history [B, max_sweeps] f64 (the merit after every sweep; past
     the last sweep the final value), sweeps [B] i32 (the last, fruitless one included), moves [B] i32."""
-    return _descend_launch("gnnpn_descend_ragged_f64", "descend_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
-                           int(bool(wide)), max_slots, max_cand, "history", max_sweeps)
+    out = _descend_launch("gnnpn_descend_ragged_f64", "descend_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
+                          (int(bool(wide)),), max_slots, max_cand, max(int(max_sweeps), 1))
+    out["history"] = out["history"][:, :int(max_sweeps)]
+    return out
+
+
+def _descend_pairs_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, tail, max_slots, max_cand,
+                          shortlist=()):
+    """What the three pair entries share on top of _descend_launch: the history under the key round_history with max(max_rounds, 1)
+    columns, and rounds, pair_moves, converged [B] i32 behind the seven fields.  What differs: the entry, ``who``, ``tail`` (the
+    scalars behind max_rounds) and ``shortlist``: () for an entry without that output, else (columns | None,)."""
+    out = _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps, (int(max_rounds), *tail), max_slots, max_cand,
+                          max(int(max_rounds), 1), (("rounds", ()), ("pair_moves", ()), ("converged", ()), *(("shortlist", c) for c in shortlist)))
+    return {("round_history" if k == "history" else k): t for k, t in out.items()}
 
 
 def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_slots=None, max_cand=None):
@@ -1352,8 +1352,8 @@ def descend_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps
     [B, max_slots] i32 and best_rows [B, max_slots, 4] f64 (0 past a problem's count), round_history [B, max(max_rounds, 1)] f64 (the
     merit after every round; past the last round the final value; max_rounds = 0: phase 0's merit), sweeps and moves [B] i32 (all
     one-swap phases together), rounds, pair_moves [B] i32, converged [B] i32 (1: no single swap and no pair swap lowers the result)."""
-    return _descend_launch("gnnpn_descend_pairs_ragged_f64", "descend_pairs_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
-                           int(max_rounds), max_slots, max_cand, "round_history", max_rounds, ("rounds", "pair_moves", "converged"))
+    return _descend_pairs_launch("gnnpn_descend_pairs_ragged_f64", "descend_pairs_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos,
+                                 max_sweeps, max_rounds, (), max_slots, max_cand)
 
 
 def descend_pairs_windowed_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_span=0, max_slots=None,
@@ -1363,9 +1363,8 @@ def descend_pairs_windowed_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, m
     same order — what makes a pair sweep affordable at hundreds of slots; converged then means that no single swap and no pair
     within the span lowers the result.  ``wide``: the workgroup form for every problem (taken anyway above 64 slots; it keeps the
     table in global memory).  Both forms give the same run.  Returns descend_pairs_ragged's dict."""
-    return _descend_launch("gnnpn_descend_pairs_windowed_ragged_f64", "descend_pairs_windowed_ragged", prob_ptr, cand_ptr, cand, bounds,
-                           start_pos, max_sweeps, (int(max_rounds), int(max_span), int(bool(wide))), max_slots, max_cand, "round_history",
-                           max_rounds, ("rounds", "pair_moves", "converged"))
+    return _descend_pairs_launch("gnnpn_descend_pairs_windowed_ragged_f64", "descend_pairs_windowed_ragged", prob_ptr, cand_ptr, cand, bounds,
+                                 start_pos, max_sweeps, max_rounds, (int(max_span), int(bool(wide))), max_slots, max_cand)
 
 
 def descend_pairs_shortlist_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0,
@@ -1381,10 +1380,9 @@ def descend_pairs_shortlist_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, 
     -1 past a shortlist's length and a problem's count, all -1 where no pair sweep ran or the problem was not searched."""
     if int(max_rank) > 0 and isinstance(cand_ptr, torch.Tensor) and cand_ptr.is_cuda and cand_ptr.numel() > 1:
         max_rank = min(int(max_rank), max(int((cand_ptr[1:] - cand_ptr[:-1]).max().item()), 1))
-    return _descend_launch("gnnpn_descend_pairs_shortlist_ragged_f64", "descend_pairs_shortlist_ragged", prob_ptr, cand_ptr, cand, bounds,
-                           start_pos, max_sweeps, (int(max_rounds), int(max_span), int(max_rank), int(bool(wide))), max_slots, max_cand,
-                           "round_history", max_rounds, ("rounds", "pair_moves", "converged"),
-                           last=("shortlist", int(max_rank) if return_shortlist else None))
+    return _descend_pairs_launch("gnnpn_descend_pairs_shortlist_ragged_f64", "descend_pairs_shortlist_ragged", prob_ptr, cand_ptr, cand, bounds,
+                                 start_pos, max_sweeps, max_rounds, (int(max_span), int(max_rank), int(bool(wide))), max_slots, max_cand,
+                                 shortlist=((int(max_rank),) if return_shortlist else None,))
 
 
 def descend_select(res, actions_all, n_slots):

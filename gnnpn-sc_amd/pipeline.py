@@ -139,27 +139,43 @@ def _quality(res, min_cost, dev):
     return res
 
 
-def _descend_tables(tabs, max_sweeps, pair_rounds=None):
-    """One-swap descent over the tables, or (pair_rounds an int, 0 included) pair-swap descent with that many rounds allowed."""
-    if pair_rounds is not None:
-        if int(pair_rounds) < 0:
-            raise ops.GnnpnError(f"descend_pairs: the number of rounds must be >= 0, got {pair_rounds}")
-        if tabs["max_slots"] > 64:
-            raise ops.GnnpnError(f"descend_pairs: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
-                                 "per problem (descend runs one-swap descent at any slot count)")
-        res = tabs.descend_pairs(max_sweeps, int(pair_rounds))
-    else:
-        res = tabs.descend(max_sweeps)
+# Pair-swap descent under its three public names, each the SearchTables method of the same name: what a negative argument is told.
+_PAIR_REFUSAL = {"descend_pairs": "the number of rounds must be >= 0, got {}",
+                 "descend_pairs_windowed": "the number of rounds and the span must be >= 0, got {} and {}",
+                 "descend_pairs_shortlist": "the number of rounds, the span and the rank must be >= 0, got {}, {} and {}"}
+
+
+def _pair_options(name, *options, who=None):
+    """(name, max_rounds[, max_span[, max_rank]]) as ints: the pair options of the search stages below, refused where one is negative
+    (``who``: the public name that says so, where it is not ``name``)."""
+    if min(int(v) for v in options) < 0:
+        raise ops.GnnpnError(f"{who or name}: " + _PAIR_REFUSAL[name].format(*options))
+    return (name, *(int(v) for v in options))
+
+
+def _search_tables(tabs, max_sweeps, pairs=None):
+    """One-swap descent over the tables, or (``pairs``: _pair_options) the pair-swap descent of that name; plus n_slots."""
+    if pairs and pairs[0] == "descend_pairs" and tabs["max_slots"] > 64:          # the one entry with the lane form only
+        raise ops.GnnpnError(f"descend_pairs: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
+                             "per problem (descend runs one-swap descent at any slot count)")
+    res = getattr(tabs, pairs[0])(max_sweeps, *pairs[1:]) if pairs else tabs.descend(max_sweeps)
     res["n_slots"] = tabs["n_slots"]
     return res
 
 
-def _descend_actions(services, batch, out, max_sweeps, pair_rounds, reduct, min_cost, patches):
-    """``descend`` (pair_rounds None) and ``descend_pairs``: the tables of ``out["actions"]``, their descent, the quality."""
+def _descend_tables(tabs, max_sweeps, pair_rounds=None):
+    """One-swap descent over the tables, or (pair_rounds an int, 0 included) ``descend_pairs`` with that many rounds allowed."""
+    return _search_tables(tabs, max_sweeps, None if pair_rounds is None else _pair_options("descend_pairs", pair_rounds))
+
+
+def _descend_actions(services, batch, out, max_sweeps, pairs, reduct, min_cost, patches):
+    """``descend`` (pairs None) and the three ``descend_pairs*`` (pairs: _pair_options' arguments): the refusal of a negative
+    argument, the tables of ``out["actions"]``, their descent, the quality."""
+    pairs = pairs and _pair_options(*pairs)
     actions = out["actions"]
     tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                               actions, reduct=reduct, patches=patches)
-    return _quality(_descend_tables(tabs, max_sweeps, pair_rounds), min_cost, actions.device)
+    return _quality(_search_tables(tabs, max_sweeps, pairs), min_cost, actions.device)
 
 
 @torch.no_grad()
@@ -183,7 +199,7 @@ def descend_pairs(services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, m
     ops.descend_pairs_ragged's dict (best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds,
     pair_moves, converged) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness).  ``max_rounds`` = 0: ``descend``'s
     result in every shared field."""
-    return _descend_actions(services, batch, out, max_sweeps, max_rounds, reduct, min_cost, patches)
+    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs", max_rounds), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -193,14 +209,7 @@ def descend_pairs_windowed(services, batch, out, max_sweeps=16, max_rounds=4, ma
     makes a pair sweep affordable at hundreds of slots (converged then means: no single swap and no pair within the span lowers the
     result).  Problems of more than 64 slots run in the workgroup form (all of the batch, then).  A negative span or a negative
     number of rounds raises GnnpnError.  ``ML2PNPipeline.descend_pairs_windowed`` is this, as a method."""
-    if int(max_rounds) < 0 or int(max_span) < 0:
-        raise ops.GnnpnError(f"descend_pairs_windowed: the number of rounds and the span must be >= 0, got {max_rounds} and {max_span}")
-    actions = out["actions"]
-    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
-                              actions, reduct=reduct, patches=patches)
-    res = tabs.descend_pairs_windowed(max_sweeps, int(max_rounds), int(max_span))
-    res["n_slots"] = tabs["n_slots"]
-    return _quality(res, min_cost, actions.device)
+    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs_windowed", max_rounds, max_span), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -211,15 +220,8 @@ def descend_pairs_shortlist(services, batch, out, max_sweeps=16, max_rounds=4, m
     lowest merit, so a slot pair costs at most m * m evaluations (converged then means: no single swap, and no pair within the span
     and the final composition's shortlists, lowers the result).  Any slot count.  A negative span, rank or number of rounds raises
     GnnpnError.  ``ML2PNPipeline.descend_pairs_shortlist`` is this, as a method."""
-    if int(max_rounds) < 0 or int(max_span) < 0 or int(max_rank) < 0:
-        raise ops.GnnpnError(f"descend_pairs_shortlist: the number of rounds, the span and the rank must be >= 0, got {max_rounds}, "
-                             f"{max_span} and {max_rank}")
-    actions = out["actions"]
-    tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
-                              actions, reduct=reduct, patches=patches)
-    res = tabs.descend_pairs_shortlist(max_sweeps, int(max_rounds), int(max_span), int(max_rank))
-    res["n_slots"] = tabs["n_slots"]
-    return _quality(res, min_cost, actions.device)
+    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs_shortlist", max_rounds, max_span, max_rank), reduct, min_cost,
+                            patches)
 
 
 @torch.no_grad()
@@ -234,7 +236,7 @@ def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=No
     method.  Returns ``descend``'s keys for the winners plus start_index [B] i32, actions [B, T', 8] (the winner's start rows:
     ``refine(services, batch, res, ..., descend=k)`` rebuilds its tables and repeats its descent before ES-WOA), fitness_all and
     start_fitness_all [B, N] f64, sweeps_all and moves_all [B, N] i32 (and quality [B] f64 = min_cost / best_fitness)."""
-    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, 0)
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, None)
 
 
 @torch.no_grad()
@@ -245,7 +247,8 @@ def descend_starts_pairs(services, batch, starts, max_sweeps=16, pair_rounds=4, 
     gains rounds, pair_moves and converged [B] i32 (the winner's, gathered by start_index) and rounds_all, pair_moves_all [B, N] i32.
     ``pair_rounds`` = 0 is ``descend_starts``: the same launches, the same result.  ``descend_starts`` itself keeps its
     signature, which is why this is a function of its own.  ``ML2PNPipeline.descend_starts_pairs`` is this, as a method."""
-    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, int(pair_rounds))
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
+                           _pair_options("descend_pairs", pair_rounds) if int(pair_rounds) else None)
 
 
 @torch.no_grad()
@@ -257,14 +260,13 @@ def descend_starts_pairs_shortlist(services, batch, starts, max_sweeps=16, pair_
     ``pair_rank`` = 0 at up to 64 slots is ``descend_starts_pairs``' result in every shared field (``pair_rounds`` = 0 included: then
     the rows' one-swap descent, reported in the pair-swap format).  A negative span, rank or number of rounds raises GnnpnError.
     ``ML2PNPipeline.descend_starts_pairs_shortlist`` is this, as a method."""
-    if int(pair_rounds) < 0 or int(pair_span) < 0 or int(pair_rank) < 0:
-        raise ops.GnnpnError(f"descend_starts_pairs_shortlist: the number of rounds, the span and the rank must be >= 0, got {pair_rounds}, "
-                             f"{pair_span} and {pair_rank}")
-    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, int(pair_rounds),
-                           shortlist=(int(pair_span), int(pair_rank)))
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
+                           _pair_options("descend_pairs_shortlist", pair_rounds, pair_span, pair_rank, who="descend_starts_pairs_shortlist"))
 
 
-def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pair_rounds, shortlist=None):
+def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pairs):
+    """The three ``descend_starts*``: the tables of every start, their descent (``pairs``: _pair_options, or None for the one-swap
+    descent and its result keys), the selection, the per-start fields, the quality."""
     all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
     if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
         raise ops.GnnpnError(f"descend_starts: starts [B, N, T, 8|9] expected, got {tuple(getattr(all_rows, 'shape', ()))}")
@@ -272,15 +274,11 @@ def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patch
     B, N = all_rows.shape[:2]
     tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                                        all_rows, reduct=reduct, patches=patches)
-    if shortlist is not None:                                           # (span, rank): the shortlist entry, at any slot count
-        per_row = tabs.descend_pairs_shortlist(max_sweeps, int(pair_rounds), *shortlist)
-        per_row["n_slots"] = tabs["n_slots"]
-    else:
-        per_row = _descend_tables(tabs, max_sweeps, int(pair_rounds) if pair_rounds else None)
+    per_row = _search_tables(tabs, max_sweeps, pairs)
     res = ops.descend_select(per_row, all_rows, tabs["n_slots"])        # (the rounds' merits and counters too, where there are any)
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
-    if pair_rounds or shortlist is not None:
+    if pairs is not None:
         res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
     return _quality(res, min_cost, all_rows.device)
 

@@ -1,78 +1,18 @@
 """Helper of the shortlist pair-swap descent tests (not a test file): the search of gnnpn_descend_pairs_shortlist_ragged_f64 in plain
-Python — pair_window_reference.descend_pairs whose pair sweeps look only at a shortlist of each slot's best candidates — built on
-descent_reference.descend and merit, a planted wall whose repairing row ranks third in its list, and the cases the host and the GPU
+Python is pair_descent_reference's one statement with a rank (``descend_pairs`` here, with the ``shortlist`` key; ``shortlists``
+beside it); this module holds a planted wall whose repairing row ranks third in its list, and the cases the host and the GPU
 tests share (reference runs cached per session)."""
 import functools
 import math
 
 import numpy as np
 
-from descent_reference import descend, merit, prepare
-from pair_descent_reference import _settled
+from descent_reference import prepare
+import pair_descent_reference
+from pair_descent_reference import shortlists          # noqa: F401
 from pair_window_reference import WALL, planted
 
-
-def shortlists(cats, bounds, cur, m):
-    """Per slot s the min(m, len) candidates c with the lowest merit of ``cur`` with slot s alone replaced by c — ordered by (merit,
-    position) under plain <, a NaN after every number and NaNs by position, -0.0 equal to 0.0 — as ascending positions."""
-    rows = [cats[s][cur[s]] for s in range(len(cats))]
-    out = []
-    for s, cat in enumerate(cats):
-        keyed = []
-        for c, row in enumerate(cat):
-            rows[s] = row
-            f = merit(rows, bounds)
-            keyed.append((f != f, 0.0 if f != f else f, c))
-        rows[s] = cat[cur[s]]
-        out.append(sorted(c for _n, _f, c in sorted(keyed)[:m]))
-    return out
-
-
-def descend_pairs(cats, bounds, start, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0):
-    """pair_window_reference.descend_pairs whose pair sweep, where max_rank = m > 0, forms ``shortlists`` of the composition it starts
-    from and tries only (a, b) of S_i x S_j, in the order of k = ia * |S_j| + ib, the lowest k among equals; the shortlists stay as
-    formed through the sweep.  The dict gains ``shortlist``: the last sweep's shortlists (None: no pair sweep ran, or m = 0)."""
-    T = len(cats)
-    r = descend(cats, bounds, start, max_sweeps)
-    cur, fit, start_fitness = list(r["best_pos"]), r["best_fitness"], r["start_fitness"]
-    sweeps, moves, settled = r["sweeps"], r["moves"], _settled(r)
-    rounds, pair_moves, round_history, moved, lists = 0, 0, [], True, None
-    for _ in range(max_rounds):
-        moved = False
-        rows = [cats[s][cur[s]] for s in range(T)]
-        lists = shortlists(cats, bounds, cur, max_rank) if max_rank > 0 else None
-        short = lists if lists is not None else [range(len(cat)) for cat in cats]
-        for i in range(T):
-            for j in range(i + 1, min(T, i + max_span + 1) if max_span > 0 else T):
-                best_f, best_ab = math.inf, None
-                for a in short[i]:
-                    rows[i] = cats[i][a]
-                    for b in short[j]:
-                        rows[j] = cats[j][b]
-                        f = merit(rows, bounds)
-                        if f < best_f:
-                            best_f, best_ab = f, (a, b)
-                if best_ab is not None and best_f < fit:         # strictly
-                    cur[i], cur[j] = best_ab
-                    fit = best_f
-                    pair_moves += 1
-                    moved = True
-                rows[i], rows[j] = cats[i][cur[i]], cats[j][cur[j]]
-        rounds += 1
-        if moved:
-            r = descend(cats, bounds, cur, max_sweeps)
-            cur, fit = list(r["best_pos"]), r["best_fitness"]
-            sweeps += r["sweeps"]
-            moves += r["moves"]
-            settled = _settled(r)
-        round_history.append(fit)
-        if not moved:
-            break
-    round_history += [fit] * (max(max_rounds, 1) - len(round_history))
-    return {"best_fitness": fit, "start_fitness": start_fitness, "best_pos": cur,
-            "best_rows": [tuple(cats[s][cur[s]]) for s in range(T)], "sweeps": sweeps, "moves": moves, "rounds": rounds,
-            "pair_moves": pair_moves, "round_history": round_history, "converged": int(rounds > 0 and not moved and settled),
-            "shortlist": lists}
+descend_pairs = functools.partial(pair_descent_reference.descend_pairs, with_shortlist=True)      # the shortlist entry: (..., max_span=0, max_rank=0)
 
 
 def shortlist_rows(want, max_slots, m):

@@ -1,56 +1,11 @@
 """Helper of the windowed pair-swap descent tests (not a test file): the search of gnnpn_descend_pairs_windowed_ragged_f64 in plain
-Python — pair_descent_reference.descend_pairs with the slot window — built on descent_reference.descend and merit, the planted
+Python is pair_descent_reference's one statement with the slot window (``descend_pairs`` here); this module holds the planted
 problems whose one-swap optima only a pair leaves, and the cases the host and the GPU tests share (reference runs cached per session)."""
 import functools
-import math
 
 import numpy as np
 
-from descent_reference import descend, merit
-from pair_descent_reference import _settled
-
-
-def descend_pairs(cats, bounds, start, max_sweeps=16, max_rounds=4, max_span=0):
-    """pair_descent_reference.descend_pairs over the pairs i < j < min(T, i + max_span + 1) where max_span > 0 (0: every pair); the
-    order, the rules and the returned dict are its own.  converged then says: no single swap and no pair within the span helps."""
-    T = len(cats)
-    r = descend(cats, bounds, start, max_sweeps)
-    cur, fit, start_fitness = list(r["best_pos"]), r["best_fitness"], r["start_fitness"]
-    sweeps, moves, settled = r["sweeps"], r["moves"], _settled(r)
-    rounds, pair_moves, round_history, moved = 0, 0, [], True
-    for _ in range(max_rounds):
-        moved = False
-        rows = [cats[s][cur[s]] for s in range(T)]
-        for i in range(T):
-            for j in range(i + 1, min(T, i + max_span + 1) if max_span > 0 else T):
-                best_f, best_ab = math.inf, None
-                for a, ra in enumerate(cats[i]):
-                    rows[i] = ra
-                    for b, rb in enumerate(cats[j]):
-                        rows[j] = rb
-                        f = merit(rows, bounds)
-                        if f < best_f:
-                            best_f, best_ab = f, (a, b)
-                if best_ab is not None and best_f < fit:         # strictly
-                    cur[i], cur[j] = best_ab
-                    fit = best_f
-                    pair_moves += 1
-                    moved = True
-                rows[i], rows[j] = cats[i][cur[i]], cats[j][cur[j]]
-        rounds += 1
-        if moved:
-            r = descend(cats, bounds, cur, max_sweeps)
-            cur, fit = list(r["best_pos"]), r["best_fitness"]
-            sweeps += r["sweeps"]
-            moves += r["moves"]
-            settled = _settled(r)
-        round_history.append(fit)
-        if not moved:
-            break
-    round_history += [fit] * (max(max_rounds, 1) - len(round_history))
-    return {"best_fitness": fit, "start_fitness": start_fitness, "best_pos": cur,
-            "best_rows": [tuple(cats[s][cur[s]]) for s in range(T)], "sweeps": sweeps, "moves": moves, "rounds": rounds,
-            "pair_moves": pair_moves, "round_history": round_history, "converged": int(rounds > 0 and not moved and settled)}
+from pair_descent_reference import descend_pairs          # noqa: F401  the windowed entry: (..., max_span=0), the ten fields
 
 
 WALL = {2: [(0.5, 0.95, 0.9, 1.0), (0.6, 0.95, 0.5, 1.0)], 3: [(0.5, 0.95, 1.0, 0.9), (0.6, 0.95, 1.0, 0.5)]}

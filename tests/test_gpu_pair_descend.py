@@ -58,6 +58,39 @@ def _assert_equal(got, tables, want, fields=FIELDS):
         assert [tuple(r) for r in got["best_rows"][p][:T]] == w["best_rows"], (p, T)
 
 
+def _call_entry(dev, entry, tables, max_slots, max_cand, max_sweeps, max_rounds, tail=(), short=()):
+    """The pair entry ``entry`` of the C ABI itself, over buffers filled with the sentinel -7: ``tail`` the scalars it has behind
+    max_rounds, ``short`` = (columns,) for the entry with a shortlist output ((None,): a NULL pointer).  Returns the dict of lists."""
+    from gnnpn_sc_amd import _lib, ops
+    ops_in = _operands(dev, tables)
+    B = len(tables)
+    F64, I32 = torch.float64, torch.int32
+    f = {k: torch.full((B,), -7.0, dtype=F64, device=dev) for k in ("best_fitness", "start_fitness")}
+    i = {k: torch.full((B,), -7, dtype=I32, device=dev) for k in ("sweeps", "moves", "rounds", "pair_moves", "converged")}
+    pos, rows = torch.full((B, max_slots), -7, dtype=I32, device=dev), torch.full((B, max_slots, 4), -7.0, dtype=F64, device=dev)
+    hist = torch.full((B, max(max_rounds, 1)), -7.0, dtype=F64, device=dev)
+    more = {"shortlist": None if m is None else torch.full((B, max_slots, m), -7, dtype=I32, device=dev) for m in short}
+    ops.check(getattr(_lib.load(), entry)(
+        B, ops.dev_ptr(ops_in[0], I32, "prob_ptr"), ops_in[4].numel(), max_slots, max_cand, ops.dev_ptr(ops_in[1], I32, "cand_ptr"),
+        ops.dev_ptr(ops_in[2], F64, "cand"), ops.dev_ptr(ops_in[3], F64, "bounds"), ops.dev_ptr(ops_in[4], I32, "start_pos"),
+        max_sweeps, max_rounds, *tail, ops.dev_ptr(f["best_fitness"], F64, "f"), ops.dev_ptr(f["start_fitness"], F64, "s"),
+        ops.dev_ptr(pos, I32, "p"), ops.dev_ptr(rows, F64, "r"), ops.dev_ptr(hist, F64, "h"), ops.dev_ptr(i["sweeps"], I32, "sw"),
+        ops.dev_ptr(i["moves"], I32, "m"), ops.dev_ptr(i["rounds"], I32, "ro"), ops.dev_ptr(i["pair_moves"], I32, "pm"),
+        ops.dev_ptr(i["converged"], I32, "c"), *(ops.dev_ptr(t, I32, "sl", allow_none=True) for t in more.values()), ops.stream_ptr()), entry)
+    return {**{k: v.cpu().tolist() for k, v in {**f, **i}.items()}, "best_pos": pos.cpu().tolist(), "best_rows": rows.cpu().tolist(),
+            "round_history": hist.cpu().tolist(), **{k: t.cpu().tolist() for k, t in more.items() if t is not None}}
+
+
+def _write_cli_ini(tmp):
+    """The environment.ini of the `main.py QWS ML+2PN -1 --infer ...` runs of the pair-swap tests, into ``tmp``."""
+    (tmp / "environment.ini").write_text(
+        f"[QWS-PNHigh]\nembeddingTag = 0\nUSE_CUDA = 1\nserCategory = {T_}\nepochDiv = 1\nserNumber = {K_}\nhidden_size = {H_}\n"
+        "n_glimpses = 0\ntanh_exploration = 10\nuse_tanh = 1\nbeta = 0.9\nmax_grad_norm = 2.\nlr = 0.5e-4\nepochML = -1\nepochPNLow = -1\n"
+        f"[QWS-ML+2PN]\nserviceCategory = {T_}\nepoch = -1\n"
+        f"[QWS-WOA]\nserCategory = {T_}\nMLESWOAtest = 0\nML2PNWOATest = 1\nMLWOATest = 0\nESWOAtest = 0\n"
+        "serviceNumber = 4\nreduct = 0\nepoch = -1\nMAX_Iter = 5\npopSize = 6\n")
+
+
 # ---- 1. slot counts ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("T", [1, 2, 3, 7, 8, 9, 33, 64])
@@ -182,29 +215,15 @@ def test_pair_descend_cut_off(dev):
 def test_pair_descend_not_searched(dev):
     """The C entry itself, over buffers filled with a sentinel: a batch sized max_slots = 64 whose prob_ptr gives one problem 65 slots.
     That row is NaN / -1 / 0 with every round_history entry written, its best_pos / best_rows rows untouched; the neighbours are right."""
-    from gnnpn_sc_amd import _lib, ops
+    from gnnpn_sc_amd import ops
     small, big, mid = _tables(*_key(7))[2], _tables(465, (65,), 2)[0], _tables(*_key(33))[0]
     tables = [small, big, mid]
     assert [len(t[0]) for t in tables] == [7, 65, 33]
-    ops_in = _operands(dev, tables)
-    F64, I32 = torch.float64, torch.int32
     max_cand = max(sum(len(c) for c in t[0]) for t in (small, mid))
     with pytest.raises(ops.GnnpnError, match="gnnpn_descend_ragged_f64"):
-        ops.descend_pairs_ragged(*ops_in)                                  # sized by the batch itself: 65 slots, refused
+        ops.descend_pairs_ragged(*_operands(dev, tables))                  # sized by the batch itself: 65 slots, refused
     for max_rounds, ld in ((0, 1), (3, 3)):
-        f = {k: torch.full((3,), -7.0, dtype=F64, device=dev) for k in ("best_fitness", "start_fitness")}
-        i = {k: torch.full((3,), -7, dtype=I32, device=dev) for k in ("sweeps", "moves", "rounds", "pair_moves", "converged")}
-        pos, rows = torch.full((3, 64), -7, dtype=I32, device=dev), torch.full((3, 64, 4), -7.0, dtype=F64, device=dev)
-        hist = torch.full((3, ld), -7.0, dtype=F64, device=dev)
-        ops.check(_lib.load().gnnpn_descend_pairs_ragged_f64(
-            3, ops.dev_ptr(ops_in[0], I32, "prob_ptr"), ops_in[4].numel(), 64, max_cand, ops.dev_ptr(ops_in[1], I32, "cand_ptr"),
-            ops.dev_ptr(ops_in[2], F64, "cand"), ops.dev_ptr(ops_in[3], F64, "bounds"), ops.dev_ptr(ops_in[4], I32, "start_pos"),
-            16, max_rounds, ops.dev_ptr(f["best_fitness"], F64, "f"), ops.dev_ptr(f["start_fitness"], F64, "s"), ops.dev_ptr(pos, I32, "p"),
-            ops.dev_ptr(rows, F64, "r"), ops.dev_ptr(hist, F64, "h"), ops.dev_ptr(i["sweeps"], I32, "sw"), ops.dev_ptr(i["moves"], I32, "m"),
-            ops.dev_ptr(i["rounds"], I32, "ro"), ops.dev_ptr(i["pair_moves"], I32, "pm"), ops.dev_ptr(i["converged"], I32, "c"),
-            ops.stream_ptr()), "gnnpn_descend_pairs_ragged_f64")
-        got = {**{k: v.cpu().tolist() for k, v in {**f, **i}.items()}, "best_pos": pos.cpu().tolist(), "best_rows": rows.cpu().tolist(),
-               "round_history": hist.cpu().tolist()}
+        got = _call_entry(dev, "gnnpn_descend_pairs_ragged_f64", tables, 64, max_cand, 16, max_rounds)
         want = [pref.descend_pairs(*t, max_rounds=max_rounds) for t in (small, mid)]
         _assert_equal({k: [v[0], v[2]] for k, v in got.items()}, [small, mid], want)
         assert np.isnan(got["best_fitness"][1]) and np.isnan(got["start_fitness"][1]) and all(np.isnan(h) for h in got["round_history"][1])
@@ -319,12 +338,7 @@ def test_main_cli_infer_descend_pairs(dev, chain, monkeypatch):      # noqa: F81
     from test_gpu_refine import _actions_array, _host_tables
     tmp = chain["tmp"]
     monkeypatch.chdir(tmp)
-    (tmp / "environment.ini").write_text(
-        f"[QWS-PNHigh]\nembeddingTag = 0\nUSE_CUDA = 1\nserCategory = {T_}\nepochDiv = 1\nserNumber = {K_}\nhidden_size = {H_}\n"
-        "n_glimpses = 0\ntanh_exploration = 10\nuse_tanh = 1\nbeta = 0.9\nmax_grad_norm = 2.\nlr = 0.5e-4\nepochML = -1\nepochPNLow = -1\n"
-        f"[QWS-ML+2PN]\nserviceCategory = {T_}\nepoch = -1\n"
-        f"[QWS-WOA]\nserCategory = {T_}\nMLESWOAtest = 0\nML2PNWOATest = 1\nMLWOATest = 0\nESWOAtest = 0\n"
-        "serviceNumber = 4\nreduct = 0\nepoch = -1\nMAX_Iter = 5\npopSize = 6\n")
+    _write_cli_ini(tmp)
     import main as cli
     base = ["main.py", "QWS", "ML+2PN", "-1", "--infer", "--random-init", "--descend=4"]
 

@@ -15,8 +15,8 @@ import torch
 import multistart_reference as mref
 import pair_shortlist_reference as sref
 import pair_window_reference as wref
-from test_gpu_descend import H_, K_, N_TRAIN, P_, T_, _tables, chain      # noqa: F401  (chain: the module-scoped fixture, set up once here)
-from test_gpu_pair_descend import FIELDS, RAGGED, _assert_equal, _operands, _replicas
+from test_gpu_descend import N_TRAIN, P_, _tables, chain      # noqa: F401  (chain: the module-scoped fixture, set up once here)
+from test_gpu_pair_descend import FIELDS, RAGGED, _assert_equal, _call_entry, _operands, _replicas, _write_cli_ini
 
 pytestmark = pytest.mark.gpu
 
@@ -81,29 +81,8 @@ def test_shortlist_both_forms_agree(dev):
 # ---- 3. a mixed ragged batch, through the C entry over sentinel-filled buffers ------------------------------------------------------------------
 
 def _call(dev, tables, max_slots, max_cand, max_sweeps, max_rounds, max_span, max_rank, wide, shortlist=True):
-    from gnnpn_sc_amd import _lib, ops
-    ops_in = _operands(dev, tables)
-    B = len(tables)
-    F64, I32 = torch.float64, torch.int32
-    ld = max(max_rounds, 1)
-    f = {k: torch.full((B,), -7.0, dtype=F64, device=dev) for k in ("best_fitness", "start_fitness")}
-    i = {k: torch.full((B,), -7, dtype=I32, device=dev) for k in ("sweeps", "moves", "rounds", "pair_moves", "converged")}
-    pos, rows = torch.full((B, max_slots), -7, dtype=I32, device=dev), torch.full((B, max_slots, 4), -7.0, dtype=F64, device=dev)
-    hist = torch.full((B, ld), -7.0, dtype=F64, device=dev)
-    short = torch.full((B, max_slots, max_rank), -7, dtype=I32, device=dev) if shortlist else None
-    ops.check(_lib.load().gnnpn_descend_pairs_shortlist_ragged_f64(
-        B, ops.dev_ptr(ops_in[0], I32, "prob_ptr"), ops_in[4].numel(), max_slots, max_cand, ops.dev_ptr(ops_in[1], I32, "cand_ptr"),
-        ops.dev_ptr(ops_in[2], F64, "cand"), ops.dev_ptr(ops_in[3], F64, "bounds"), ops.dev_ptr(ops_in[4], I32, "start_pos"),
-        max_sweeps, max_rounds, max_span, max_rank, wide, ops.dev_ptr(f["best_fitness"], F64, "f"), ops.dev_ptr(f["start_fitness"], F64, "s"),
-        ops.dev_ptr(pos, I32, "p"), ops.dev_ptr(rows, F64, "r"), ops.dev_ptr(hist, F64, "h"), ops.dev_ptr(i["sweeps"], I32, "sw"),
-        ops.dev_ptr(i["moves"], I32, "m"), ops.dev_ptr(i["rounds"], I32, "ro"), ops.dev_ptr(i["pair_moves"], I32, "pm"),
-        ops.dev_ptr(i["converged"], I32, "c"), ops.dev_ptr(short, I32, "sl", allow_none=True), ops.stream_ptr()),
-        "gnnpn_descend_pairs_shortlist_ragged_f64")
-    got = {**{k: v.cpu().tolist() for k, v in {**f, **i}.items()}, "best_pos": pos.cpu().tolist(), "best_rows": rows.cpu().tolist(),
-           "round_history": hist.cpu().tolist()}
-    if shortlist:
-        got["shortlist"] = short.cpu().tolist()
-    return got
+    return _call_entry(dev, "gnnpn_descend_pairs_shortlist_ragged_f64", tables, max_slots, max_cand, max_sweeps, max_rounds,
+                       (max_span, max_rank, wide), short=(max_rank if shortlist else None,))
 
 
 @functools.lru_cache(maxsize=None)
@@ -222,12 +201,7 @@ def test_main_cli_infer_descend_pairs_top(dev, chain, monkeypatch):      # noqa:
     from test_gpu_refine import _actions_array, _host_tables
     tmp = chain["tmp"]
     monkeypatch.chdir(tmp)
-    (tmp / "environment.ini").write_text(
-        f"[QWS-PNHigh]\nembeddingTag = 0\nUSE_CUDA = 1\nserCategory = {T_}\nepochDiv = 1\nserNumber = {K_}\nhidden_size = {H_}\n"
-        "n_glimpses = 0\ntanh_exploration = 10\nuse_tanh = 1\nbeta = 0.9\nmax_grad_norm = 2.\nlr = 0.5e-4\nepochML = -1\nepochPNLow = -1\n"
-        f"[QWS-ML+2PN]\nserviceCategory = {T_}\nepoch = -1\n"
-        f"[QWS-WOA]\nserCategory = {T_}\nMLESWOAtest = 0\nML2PNWOATest = 1\nMLWOATest = 0\nESWOAtest = 0\n"
-        "serviceNumber = 4\nreduct = 0\nepoch = -1\nMAX_Iter = 5\npopSize = 6\n")
+    _write_cli_ini(tmp)
     import main as cli
     base = ["main.py", "QWS", "ML+2PN", "-1", "--infer", "--random-init", "--descend=4", "--pairs"]
     with contextlib.redirect_stdout(io.StringIO()):

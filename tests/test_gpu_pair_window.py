@@ -12,8 +12,8 @@ import pytest
 import torch
 
 import pair_window_reference as wref
-from test_gpu_descend import H_, K_, N_TRAIN, P_, T_, _tables, chain      # noqa: F401  (chain: the module-scoped fixture, set up once here)
-from test_gpu_pair_descend import RAGGED, _assert_equal, _operands
+from test_gpu_descend import N_TRAIN, P_, _tables, chain      # noqa: F401  (chain: the module-scoped fixture, set up once here)
+from test_gpu_pair_descend import RAGGED, _assert_equal, _call_entry, _operands, _write_cli_ini
 from test_gpu_pair_descend import _want as _pair_want
 
 pytestmark = pytest.mark.gpu
@@ -166,26 +166,11 @@ def test_pair_window_not_searched(dev):
     """The C entry itself, over buffers filled with a sentinel: a batch sized max_slots = 65 whose prob_ptr gives one problem 66 slots.
     That row is NaN / -1 / 0 with rounds -1 and every round_history entry NaN, its best_pos / best_rows rows untouched; the
     neighbours are right and nothing past a row's count is written."""
-    from gnnpn_sc_amd import _lib, ops
     small, big, mid = _tables(1207, (7,), 4, 8)[2], wref.planted(1801, 66, wall2=(0, 65), nfill=1), wref.size_tables(65)[0]
     tables = [small, big, mid]
     assert [len(t[0]) for t in tables] == [7, 66, 65]
-    ops_in = _operands(dev, tables)
-    F64, I32 = torch.float64, torch.int32
     for max_rounds, ld in ((0, 1), (3, 3)):
-        f = {k: torch.full((3,), -7.0, dtype=F64, device=dev) for k in ("best_fitness", "start_fitness")}
-        i = {k: torch.full((3,), -7, dtype=I32, device=dev) for k in ("sweeps", "moves", "rounds", "pair_moves", "converged")}
-        pos, rows = torch.full((3, 65), -7, dtype=I32, device=dev), torch.full((3, 65, 4), -7.0, dtype=F64, device=dev)
-        hist = torch.full((3, ld), -7.0, dtype=F64, device=dev)
-        ops.check(_lib.load().gnnpn_descend_pairs_windowed_ragged_f64(
-            3, ops.dev_ptr(ops_in[0], I32, "prob_ptr"), ops_in[4].numel(), 65, 0, ops.dev_ptr(ops_in[1], I32, "cand_ptr"),
-            ops.dev_ptr(ops_in[2], F64, "cand"), ops.dev_ptr(ops_in[3], F64, "bounds"), ops.dev_ptr(ops_in[4], I32, "start_pos"),
-            16, max_rounds, 0, 0, ops.dev_ptr(f["best_fitness"], F64, "f"), ops.dev_ptr(f["start_fitness"], F64, "s"),
-            ops.dev_ptr(pos, I32, "p"), ops.dev_ptr(rows, F64, "r"), ops.dev_ptr(hist, F64, "h"), ops.dev_ptr(i["sweeps"], I32, "sw"),
-            ops.dev_ptr(i["moves"], I32, "m"), ops.dev_ptr(i["rounds"], I32, "ro"), ops.dev_ptr(i["pair_moves"], I32, "pm"),
-            ops.dev_ptr(i["converged"], I32, "c"), ops.stream_ptr()), "gnnpn_descend_pairs_windowed_ragged_f64")
-        got = {**{k: v.cpu().tolist() for k, v in {**f, **i}.items()}, "best_pos": pos.cpu().tolist(), "best_rows": rows.cpu().tolist(),
-               "round_history": hist.cpu().tolist()}
+        got = _call_entry(dev, "gnnpn_descend_pairs_windowed_ragged_f64", tables, 65, 0, 16, max_rounds, (0, 0))
         want = [wref.descend_pairs(*t, max_rounds=max_rounds) for t in (small, mid)]
         _assert_equal({k: [v[0], v[2]] for k, v in got.items()}, [small, mid], want)
         assert np.isnan(got["best_fitness"][1]) and np.isnan(got["start_fitness"][1]) and all(np.isnan(h) for h in got["round_history"][1])
@@ -220,12 +205,7 @@ def test_main_cli_infer_descend_pairs_span(dev, chain, monkeypatch):      # noqa
     from test_gpu_refine import _actions_array, _host_tables
     tmp = chain["tmp"]
     monkeypatch.chdir(tmp)
-    (tmp / "environment.ini").write_text(
-        f"[QWS-PNHigh]\nembeddingTag = 0\nUSE_CUDA = 1\nserCategory = {T_}\nepochDiv = 1\nserNumber = {K_}\nhidden_size = {H_}\n"
-        "n_glimpses = 0\ntanh_exploration = 10\nuse_tanh = 1\nbeta = 0.9\nmax_grad_norm = 2.\nlr = 0.5e-4\nepochML = -1\nepochPNLow = -1\n"
-        f"[QWS-ML+2PN]\nserviceCategory = {T_}\nepoch = -1\n"
-        f"[QWS-WOA]\nserCategory = {T_}\nMLESWOAtest = 0\nML2PNWOATest = 1\nMLWOATest = 0\nESWOAtest = 0\n"
-        "serviceNumber = 4\nreduct = 0\nepoch = -1\nMAX_Iter = 5\npopSize = 6\n")
+    _write_cli_ini(tmp)
     import main as cli
     with contextlib.redirect_stdout(io.StringIO()):
         assert cli.main(["main.py", "QWS", "ML+2PN", "-1", "--infer", "--random-init", "--descend=4", "--pairs", "--span=2"]) == 0

@@ -39,6 +39,30 @@ def test_no_rank_and_a_full_rank_are_the_windowed_reference():
         assert sref.descend_pairs(*tab, max_rank=0)["shortlist"] is None and sref.descend_pairs(*tab, max_rank=2, max_rounds=0)["shortlist"] is None
 
 
+def test_the_one_reference_replays_the_record_of_the_three():
+    """tests/golden/pair_descent_reference_record.json: what the three reference functions returned while they were three loops
+    (the plain one for span 0 and rank 0, the windowed one for rank 0, the shortlist one otherwise) on the 20 tables, at three
+    cut-offs.  The one loop they are bound to now returns the same, float64 values bit for bit (float.hex)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pair_descent_reference_record.json")) as f:
+        record = json.load(f)
+    tables = sref.seeds_tables()
+    assert len(record["runs"]) == 20 * 3 * 5 and {r["table"] for r in record["runs"]} == set(range(20))
+    assert {(r["max_span"], r["max_rank"]) for r in record["runs"]} == {(0, 0), (1, 0), (0, 1), (0, 2), (2, 2)}
+    for run in record["runs"]:
+        tab, kw, span, rank = tables[run["table"]], record["settings"][run["setting"]], run["max_span"], run["max_rank"]
+        if rank:
+            got = sref.descend_pairs(*tab, max_span=span, max_rank=rank, **kw)
+        else:
+            got = wref.descend_pairs(*tab, max_span=span, **kw) if span else pref.descend_pairs(*tab, **kw)
+        assert got.pop("best_rows") == [tuple(tab[0][s][p]) for s, p in enumerate(got["best_pos"])]
+        got.update(best_fitness=got["best_fitness"].hex(), start_fitness=got["start_fitness"].hex(),
+                   round_history=[h.hex() for h in got["round_history"]])
+        want = {k: v for k, v in run.items() if k not in ("table", "setting", "max_span", "max_rank")}
+        assert got == want, (run["table"], kw, span, rank)
+
+
 def test_a_shortlist_of_one_never_moves_by_pairs():
     """The one-swap optimum's own member is each slot's best single swap (the lowest position among equals is what descent took or
     kept), so S_i x S_j is the current pair: nothing is strictly below the current merit."""
