@@ -105,8 +105,26 @@ def infer_pairs_shortlist(dataset, net, low, high, n_per, epoch=-1, device="cuda
                   pair_rounds, pair_span, pair_rank)
 
 
+def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
+                   sample_seed=None, descend=None, all_starts=False, pair_rounds=None, pair_span=None, pair_rank=None):
+    """``infer`` (with ``pair_span`` / ``pair_rank``: ``infer_pairs_windowed`` / ``infer_pairs_shortlist``) whose last search stage
+    also says which services its compositions consist of: every artefact of that run as before, plus
+    ``./solutions/WOA/<dataset>/ML+2PN+services.txt`` — per test problem the list of [node, category, service] (the node's position
+    in its workflow graph, its 0-based category, the row of the service table; -1: a row of the pointer network that is no kept
+    service and has no id), the merit ``pipeline.score_services`` gives that composition, the stage's best_fitness and the row
+    count.  Needs ``descend`` or ``woa``.  A function of its own because ``infer``'s parameter list is pinned by the host tests."""
+    if descend is None and woa is None:
+        raise ValueError("ML2PN.infer_services: needs descend or woa (the services of a searched composition)")
+    if pair_rank is not None and (descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0 or pair_rank < 0):
+        raise ValueError("ML2PN.infer_services: pair_rank needs descend, at least one round, a span >= 0 and a rank >= 0")
+    if pair_span is not None and (descend is None or pair_rounds is None or pair_rounds < 1 or pair_span < 0):
+        raise ValueError("ML2PN.infer_services: pair_span needs descend, at least one round and a span >= 0")
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts,
+                  pair_rounds, pair_span, pair_rank, services=True)
+
+
 def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, pair_rounds,
-           pair_span, pair_rank=None):
+           pair_span, pair_rank=None, services=False):
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -124,7 +142,7 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
     pipe = ML2PNPipeline(net.to(dev).eval(), low.to(dev).eval(), high.to(dev).eval(), n_per, precision=precision)
     table, _ = ld.tables_from_dataset(ds, 0, 0)
     svc = DeviceServices.from_table(table, dev)
-    rankings, actions, test_actions, test_starts = [], [[] for _ in range(T)], [], []
+    rankings, actions, test_actions, test_starts, test_ids = [], [[] for _ in range(T)], [], [], []      # (test_ids: ``services`` only)
     n_train = P // 4 * 3
     from . import ops
     for lo in range(0, P, batch_size):
@@ -141,13 +159,20 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
             def best(attempt):
                 o = pipe.best_of(svc, batch, samples, seed=seed_b, write_through=attempt > 0, return_all=all_starts)
                 rows = o["actions_all"][..., -8:].cpu().numpy().astype(np.float64) if all_starts else None       # [b,N,T,8]
-                return o["actions"].cpu().numpy().astype(np.float64), rows
-            act, starts = ops.run_checked(best, dev)
+                ids = None
+                if services:                    # the rows of the service table the action rows are: [b,T], with all_starts [b,N,T]
+                    ids = o["candidate_ids"].gather(1, (o["idx_all"].flatten(1) if all_starts else o["idx_high"]).long()).cpu().numpy()
+                    ids = ids.reshape(rows.shape[:3]) if all_starts else ids
+                return o["actions"].cpu().numpy().astype(np.float64), rows, ids
+            act, starts, ids = ops.run_checked(best, dev)
             if all_starts and hi > n_train:
                 test_starts.append(starts[max(0, n_train - lo):])
         else:
-            act = ops.run_checked(lambda attempt: pipe.run(svc, batch, write_through=attempt > 0)["actions"].cpu().numpy().astype(np.float64),
-                                  dev)                                       # [b,T,8]
+            def one(attempt):
+                o = pipe.run(svc, batch, write_through=attempt > 0)
+                return (o["actions"].cpu().numpy().astype(np.float64),
+                        o["candidate_ids"].gather(1, o["idx_high"].long()).cpu().numpy() if services else None)
+            act, ids = ops.run_checked(one, dev)                             # [b,T,8], and (services) the rows of the service table they are [b,T]
         rankings += pipe.rankings(svc, batch).cpu().tolist()
         for b in range(hi - lo):
             if lo + b >= n_train:
@@ -155,11 +180,14 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
                     actions[t].append(act[b, t].tolist())
         if (woa is not None or descend is not None) and hi > n_train:
             test_actions.append(act[max(0, n_train - lo):])
+            if services:
+                test_ids.append(ids[max(0, n_train - lo):])
     paths = write_artifacts(dataset, epoch, rankings, actions)
     if woa is not None or descend is not None:
         _refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
                             **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds, pair_span=pair_span,
-                            pair_rank=pair_rank,
+                            pair_rank=pair_rank, action_ids=np.concatenate(test_ids).astype(np.int32) if services and test_ids else None,
+                            services=services,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
@@ -178,11 +206,12 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
 
 
 def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, pair_rounds=None,
-                         pair_span=None, pair_rank=None):
+                         pair_span=None, pair_rank=None, services=False, action_ids=None):
     """refine_test_quarter; ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
     with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``.  ``pair_rank`` (>= 0, with ``pair_span``, without
     ES-WOA): pipeline.descend_pairs_shortlist (with ``starts``: descend_starts_pairs_shortlist) with that span and rank, and the file
-    gains ``top`` too."""
+    gains ``top`` too.  ``services``: the last stage's compositions also go to ``ML+2PN+services.txt`` (write_services);
+    ``action_ids`` [nTest, T] (with ``starts``: [nTest, N, T]) int32: the rows of the service table the action rows are, or None."""
     import time
     import torch
     from . import loadData as ld
@@ -222,6 +251,10 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
                                   extra=({**counters(res), **({} if pair_span is None else {"span": pair_span}),
                                          **({} if pair_rank is None else {"top": pair_rank})}) if pairs else None)
         if multi:
+            if services and action_ids is not None:  # the winner's ids, as its rows
+                win = res["start_index"].long()[:, None, None]
+                all_ids = torch.from_numpy(np.ascontiguousarray(action_ids)).to(dev)
+                action_ids = all_ids.gather(1, win.expand(-1, 1, all_ids.shape[2]))[:, 0].cpu().numpy()
             out = {"actions": res["actions"]}        # refine below rebuilds the winner's tables and repeats its descent
     if descend is None or popSize > 0:
         torch.cuda.synchronize(dev)
@@ -233,7 +266,39 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
                             pair_rounds=pair_rounds or 0)
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first)
+    if services:
+        write_services(dataset, svc, batch, out, res, reduct, action_ids)
     return written
+
+
+def write_services(dataset, svc, batch, out, res, reduct, action_ids=None):
+    """``./solutions/WOA/<dataset>/ML+2PN+services.txt``: which services the compositions of the search result ``res`` over
+    ``out["actions"]`` consist of (pipeline.name_services; ``action_ids`` [B, T]: the rows of the service table the actions are) and
+    what pipeline.score_services says of them.  Per problem: ``services`` = the list of [node, category, service] of its task nodes (the node's
+    position in its workflow graph, its 0-based category, the row of the service table or -1: no candidate list, or a foreign row
+    without an id), ``merit``, ``best_fitness`` (the stage's own figure: equal to the merit bit for bit where every foreign row has an id),
+    ``n_rows``.  json writes a float64 so that it reads back as the same bits."""
+    import torch
+    from . import pipeline as pl
+    dev = svc.qos.device
+    src = {"actions": out["actions"]}
+    if action_ids is not None:                       # as name_services reads them off run's result: identity picks over the ids
+        ids = torch.from_numpy(np.ascontiguousarray(action_ids, dtype=np.int32)).to(dev)
+        src.update(candidate_ids=ids, idx_high=torch.arange(ids.shape[1], device=dev, dtype=torch.int32).expand(ids.shape[0], -1).contiguous())
+    named = pl.name_services(svc, batch, src, {k: v for k, v in res.items() if k not in ("start_index", "actions")}, reduct=reduct)
+    merit, n_rows = pl.score_services(svc, batch, named["node_services"])
+    seg, x0 = batch.seg_ptr.cpu().tolist(), batch.x[:, 0].cpu().tolist()
+    node = named["node_services"].cpu().tolist()
+    fit = named["best_fitness"].cpu().tolist()
+    rows = []
+    for b in range(len(seg) - 1):
+        rows.append([[g - seg[b], int(x0[g]) - 1, node[g]] for g in range(seg[b] + 1, seg[b + 1])])
+    doc = {"services": rows, "merit": merit.cpu().tolist(), "best_fitness": fit, "n_rows": n_rows.cpu().tolist(),
+           "action_ids_used": bool(named["action_ids_used"])}
+    os.makedirs(f"./solutions/WOA/{dataset}/", exist_ok=True)
+    with open(f"./solutions/WOA/{dataset}/ML+2PN+services.txt", "w") as f:
+        json.dump(doc, f)
+    return doc
 
 
 def artifact_paths(dataset, epoch):

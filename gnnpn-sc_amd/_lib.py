@@ -113,6 +113,12 @@ _SIGNATURES = {
     "gnnpn_woa_candidates_replicas_fill": (c_int, [c_int32, c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, _P, c_int32, c_int32,
                                                    _P, _P, _P, _P, _P]),
     "gnnpn_descend_select_f64": (c_int, [c_int32] * 6 + [_P] * 20),
+    "gnnpn_woa_candidates_services": (c_int, [c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int32, _P, c_int64, _P, _P, c_int32,
+                                              c_int32, _P, _P, _P, _P]),
+    "gnnpn_woa_candidates_replicas_services": (c_int, [c_int32, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int32, _P, c_int64, _P,
+                                                       _P, c_int32, c_int32, _P, _P, _P, _P]),
+    "gnnpn_search_services": (c_int, [c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, c_int32, _P, _P, _P]),
+    "gnnpn_services_merit_f64": (c_int, [c_int32, _P, c_int32, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P]),
     "gnnpn_debug_round5_f64": (c_int, [_P, _P, c_int64, _P]),
     "gnnpn_debug_cell_activations": (c_int, [_P, _P, _P, c_int64, _P]),
     "gnnpn_debug_lds_interferer": (c_int, [c_int32, c_int32, c_int32, _P]),

@@ -15,27 +15,11 @@
 //   fill   — the tables of gnnpn_eswoa_ragged_f64: cand_ptr, len_init, cand, start_pos.
 // Every value is written with plain stores.  A problem the host path would raise on gets a status word instead (header).
 #include "common.h"
+#include "round5.h"
 
 #include <climits>
 
 namespace {
-
-// Python's round(x, 5) bit for bit (CPython rounds the exact binary value, ties to even, and returns the double nearest to
-// the decimal result).  p + e = x * 10^5 exactly (e by fma); n = rint(p), r = p - n is exact and |r| <= 0.5.  The decision
-// reads r and e separately: r + e could round onto 0.5.  For 2^52 <= |p| < 2^53, p is an integer and r = 0, |e| <= 0.5: an
-// exact half there is a tie between n and n +- 1, broken to the even one.  n < 2^53 is exact, so n / 10^5 (IEEE division) is
-// the double nearest to n * 10^-5.  From |p| >= 2^53 on x itself is what Python returns (and NaN / inf stay as they are).
-__device__ __forceinline__ double round5(double x) {
-    const double p = __dmul_rn(x, 1e5);
-    if (!(fabs(p) < 9007199254740992.0)) return x;
-    const double e = fma(x, 1e5, -p);
-    double n = rint(p);
-    const double r = __dsub_rn(p, n);
-    if (r > 0.5 || (r == 0.5 && e > 0.0)) n = __dadd_rn(n, 1.0);
-    else if (r < -0.5 || (r == -0.5 && e < 0.0)) n = __dsub_rn(n, 1.0);
-    else if (r == 0.0 && fabs(e) == 0.5 && fmod(n, 2.0) != 0.0) n = __dadd_rn(n, e > 0.0 ? 1.0 : -1.0);
-    return n / 1e5;
-}
 
 __device__ __forceinline__ bool same4(const double* a, const double* b) {   // Python tuple equality of floats (-0.0 == 0.0)
     return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3];
@@ -372,6 +356,58 @@ __global__ __launch_bounds__(64) void woa_fill_kernel(int32_t B, int32_t N, int3
     }
 }
 
+// Which services the tables of woa_fill_kernel consist of, from the same workspace: per list its task node (position inside
+// the workflow graph, >= 1: node 0 is the request node) and category, per candidate the row of qos it was read from.  The
+// appended foreign row is no row of qos: it gets the id the caller gave for the action row paired with its list (action_ids
+// [rows, a_T], compacted as woa_count_kernel compacts the rows — dummy rows, float64 sum == 3, dropped; the ballot compaction is
+// restated here so that the count kernel compiles to what it did), or -1.  One wavefront per row, plain stores only.
+__global__ __launch_bounds__(64) void woa_services_kernel(int32_t N, int32_t R, const int32_t* __restrict__ seg_ptr,
+                                                          const int32_t* __restrict__ cat_ptr, const void* __restrict__ actions,
+                                                          int32_t actions_f64, int32_t a_T, const int32_t* __restrict__ action_ids,
+                                                          int32_t cap, PrepWs w, const int32_t* __restrict__ status,
+                                                          const int32_t* __restrict__ prob_ptr, int32_t n_lists, int32_t n_cand,
+                                                          int32_t* __restrict__ slot_node, int32_t* __restrict__ slot_cat,
+                                                          int32_t* __restrict__ cand_service) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    int* row_id = reinterpret_cast<int*>(lds_raw);             // [a_T] the ids of the rows that are no dummy rows
+    const int rq = blockIdx.x, b = rq / R, lane = threadIdx.x;
+    const int wq = (rq - b * R) * N;
+    if (status[rq] != GNNPN_WOA_OK) return;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int n_rows = 0;
+    for (int c0 = 0; c0 < a_T && action_ids; c0 += 64) {
+        const int c = c0 + lane;
+        bool real = false;
+        if (c < a_T) {
+            const size_t at = ((size_t)rq * a_T + c) * 8;
+            double r[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                r[k] = actions_f64 ? static_cast<const double*>(actions)[at + k] : (double)static_cast<const float*>(actions)[at + k];
+            real = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), r[2]), r[3]) != 3.0;
+        }
+        const unsigned long long m = __ballot(real);
+        if (real) row_id[n_rows + __popcll(m & below)] = action_ids[(size_t)rq * a_T + c];
+        n_rows += __popcll(m);
+    }
+    __syncthreads();
+    const int n0 = seg_ptr[b], n1 = seg_ptr[b + 1];
+    const int ns = n1 - n0 > 1 ? n1 - n0 - 1 : 0;             // a bad segment has a non-zero status: not reached
+    for (int s = lane; s < ns; s += 64) {
+        const int g = n0 + 1 + s;
+        const int l = w.rank[wq + g];
+        if (l < 0) continue;
+        const int j = prob_ptr[rq] + l, off = w.cand_off[rq] + w.off[wq + g];
+        const int nk = w.n_kept[wq + g], len = w.n_len[wq + g];
+        if (j >= n_lists || off + len > n_cand) continue;      // never for the totals this call was sized by
+        const int cat = w.cat[wq + g];
+        slot_node[j] = g - n0;
+        slot_cat[j] = cat;
+        for (int i = 0; i < nk; ++i) cand_service[off + i] = cat_ptr[cat] + w.kept[(size_t)(wq + g) * cap + i];
+        if (len > nk) cand_service[off + nk] = l < n_rows ? row_id[l] : -1;
+    }
+}
+
 __global__ void round5_kernel(const double* __restrict__ x, double* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = round5(x[i]);
@@ -441,7 +477,52 @@ int fill_launch(const char* who, int32_t B, int32_t R, int32_t n_nodes, const in
     return GNNPN_OK;
 }
 
+int services_launch(const char* who, int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr,
+                    const void* actions, int32_t actions_f64, int32_t actions_T, const int32_t* action_ids, int32_t max_cat_size,
+                    const void* workspace, int64_t workspace_bytes, const int32_t* status, const int32_t* prob_ptr, int32_t n_lists,
+                    int32_t n_cand, int32_t* slot_node, int32_t* slot_cat, int32_t* cand_service, void* stream) {
+    GNNPN_REQUIRE(B >= 0 && R >= 1 && n_nodes >= 0 && max_cat_size >= 0 && n_lists >= 0 && n_cand >= 0 && actions_T >= 1 &&
+                  (actions_f64 == 0 || actions_f64 == 1), "%s: bad argument", who);
+    GNNPN_REQUIRE(rows_fit(B, R, n_nodes), "%s: bad argument: %d problems / %d nodes x %d replicas exceed int32", who, B, n_nodes, R);
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(seg_ptr && cat_ptr && status && prob_ptr && (!action_ids || actions) && (n_lists == 0 || (slot_node && slot_cat)) &&
+                  (n_cand == 0 || cand_service), "%s: null operand", who);
+    const int32_t rows = B * R;
+    const int64_t need = prep_ws_bytes(rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    GNNPN_REQUIRE(workspace && workspace_bytes >= need && gnnpn_aligned(workspace, 8), "%s: workspace of %lld B, %lld B needed", who,
+                  (long long)workspace_bytes, (long long)need);
+    const size_t lds = (size_t)actions_T * sizeof(int32_t);
+    if (lds > 64 * 1024) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d action rows per problem (at most 1024)", who, actions_T);
+    const PrepWs w = prep_ws(const_cast<void*>(workspace), rows, (int64_t)n_nodes * R, (int64_t)max_cat_size + 1);
+    hipLaunchKernelGGL(woa_services_kernel, dim3(rows), dim3(64), lds, (hipStream_t)stream, n_nodes, R, seg_ptr, cat_ptr, actions,
+                       actions_f64, actions_T, action_ids, max_cat_size + 1, w, status, prob_ptr, n_lists, n_cand, slot_node, slot_cat,
+                       cand_service);
+    GNNPN_CHECK_LAUNCH(who);
+    return GNNPN_OK;
+}
+
 }  // namespace
+
+extern "C" int gnnpn_woa_candidates_replicas_services(int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr,
+                                                      const int32_t* cat_ptr, const void* actions, int32_t actions_f64,
+                                                      int32_t actions_T, const int32_t* action_ids, int32_t max_cat_size,
+                                                      const void* workspace, int64_t workspace_bytes, const int32_t* status,
+                                                      const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* slot_node,
+                                                      int32_t* slot_cat, int32_t* cand_service, void* stream) {
+    return services_launch("woa_candidates_replicas_services", B, R, n_nodes, seg_ptr, cat_ptr, actions, actions_f64, actions_T, action_ids,
+                           max_cat_size, workspace, workspace_bytes, status, prob_ptr, n_lists, n_cand, slot_node, slot_cat, cand_service,
+                           stream);
+}
+
+extern "C" int gnnpn_woa_candidates_services(int32_t B, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr,
+                                             const void* actions, int32_t actions_f64, int32_t actions_T, const int32_t* action_ids,
+                                             int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status,
+                                             const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* slot_node,
+                                             int32_t* slot_cat, int32_t* cand_service, void* stream) {
+    return services_launch("woa_candidates_services", B, 1, n_nodes, seg_ptr, cat_ptr, actions, actions_f64, actions_T, action_ids,
+                           max_cat_size, workspace, workspace_bytes, status, prob_ptr, n_lists, n_cand, slot_node, slot_cat, cand_service,
+                           stream);
+}
 
 extern "C" int64_t gnnpn_woa_candidates_replicas_workspace_bytes(int32_t B, int32_t R, int32_t n_nodes, int32_t max_cat_size) {
     if (B < 0 || R < 1 || n_nodes < 0 || max_cat_size < 0 || !rows_fit(B, R, n_nodes)) return -1;

@@ -1146,6 +1146,34 @@ class SearchTables(dict):
                             self["start_pos"] if start_pos is None else start_pos, pop, max_iter, seeds,
                             max_slots=self["max_slots"], max_cand=self["max_cand"], wide=wide)
 
+    def services(self, res, seg_ptr, n_nodes, start_index=None):
+        """The services a search result over these tables names (gnnpn_search_services; the tables are woa_candidates_named's or
+        woa_candidates_replicas_named's).  ``res``: a mapping with best_fitness [B] f64 and best_pos [B, ld] i32 — a descent's dict,
+        descend_select's, or ES-WOA's pair under those keys (negative positions are Python's); ``start_index`` [B] i32: over
+        replica tables, the row of every problem that ``res`` speaks of (descend_select's; None: replica 0, and the only row of
+        tables without replicas).  seg_ptr [B+1] i32, ``n_nodes``: the rows of batch.x.  Returns {best_services [B, ld] i32,
+        node_services [n_nodes] i32}: -1 past a problem's slots, for request nodes, tasks without a list, positions outside their
+        list and throughout for a problem whose best_fitness is NaN."""
+        if "cand_service" not in self:
+            raise GnnpnError("SearchTables.services: tables without ids (woa_candidates_named / woa_candidates_replicas_named build them)")
+        fit, pos = res["best_fitness"], res["best_pos"].contiguous()
+        R = int(self.get("replicas", 1))
+        B = seg_ptr.numel() - 1
+        if fit.numel() != B or pos.dim() != 2 or pos.shape[0] != B or self["prob_ptr"].numel() != B * R + 1 or \
+                (start_index is not None and start_index.numel() != B):
+            raise GnnpnError(f"SearchTables.services: {B} problems x {R} rows expected in res, start_index and the tables")
+        dev = pos.device
+        out = {"best_services": torch.empty(B, pos.shape[1], dtype=I32, device=dev),
+               "node_services": torch.full((int(n_nodes),), -1, dtype=I32, device=dev)}
+        check(_lib.load().gnnpn_search_services(
+            B, R, dev_ptr(start_index, I32, "start_index", allow_none=True), dev_ptr(fit, F64, "best_fitness"),
+            dev_ptr(pos, I32, "best_pos"), pos.shape[1], dev_ptr(self["prob_ptr"], I32, "prob_ptr"), self["slot_node"].numel(),
+            dev_ptr(self["cand_ptr"], I32, "cand_ptr"), self["cand_service"].numel(), dev_ptr(self["cand_service"], I32, "cand_service"),
+            dev_ptr(self["slot_node"], I32, "slot_node"), dev_ptr(seg_ptr, I32, "seg_ptr"), int(n_nodes),
+            dev_ptr(out["best_services"], I32, "best_services"), dev_ptr(out["node_services"], I32, "node_services"), stream_ptr()),
+            "gnnpn_search_services")
+        return out
+
     def flat(self, best_pos):
         """A [B, max_slots] i32 ``best_pos`` as flat [n_lists] positions (what start_pos is): a problem's slots are rows
         prob_ptr[p] .. of the flat tables and the first n_slots[p] entries of its best_pos row."""
@@ -1153,9 +1181,12 @@ class SearchTables(dict):
         return best_pos[slots].contiguous()
 
 
-def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches, check_status):
+def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches, check_status,
+                named=False, action_ids=None):
     """woa_candidates (``replicas`` None: the per-problem entries) and woa_candidates_replicas (``replicas`` True: the per-replica
-    ones over B * R rows, R read from the actions)."""
+    ones over B * R rows, R read from the actions).  ``named``: the *_named wrappers — one launch more on the same workspace
+    (gnnpn_woa_candidates_services / _replicas_services) adds slot_node, slot_cat and cand_service; ``action_ids``: the rows of qos
+    the action rows are (actions' leading shape, int32), or None."""
     lib = _lib.load()
     dev = x.device
     B = seg_ptr.numel() - 1
@@ -1223,6 +1254,18 @@ def _woa_tables(who, replicas, cat_ptr, qos, x, seg_ptr, local_bounds, global_bo
                         bounds=bounds, status=status, max_slots=max_slots, max_cand=max_cand)
     if replicas is not None:
         tabs["replicas"] = R
+    if named:
+        if action_ids is not None and (not isinstance(action_ids, torch.Tensor) or tuple(action_ids.shape) != tuple(actions.shape[:-1])):
+            raise GnnpnError(f"{who}: action_ids {tuple(actions.shape[:-1])} int32 expected (one id per action row), got "
+                             f"{tuple(getattr(action_ids, 'shape', ()))}")
+        names = {k: torch.empty(n, dtype=I32, device=dev) for k, n in (("slot_node", n_lists), ("slot_cat", n_lists), ("cand_service", n_cand))}
+        services = lib.gnnpn_woa_candidates_services if replicas is None else lib.gnnpn_woa_candidates_replicas_services
+        check(services(*lead, dev_ptr(seg_ptr, I32, "seg_ptr"), dev_ptr(cat_ptr, I32, "cat_ptr"),
+                       dev_ptr(actions, actions.dtype, "actions"), int(actions.dtype == F64), aT,
+                       dev_ptr(action_ids, I32, "action_ids", allow_none=True), max_cat, dev_ptr(ws, torch.int64, "workspace"),
+                       ws.numel() * 8, dev_ptr(status, I32, "status"), dev_ptr(prob_ptr, I32, "prob_ptr"), n_lists, n_cand,
+                       *(dev_ptr(t, I32, k) for k, t in names.items()), stream_ptr()), entry + "_services")
+        tabs.update(names)
     return tabs
 
 
@@ -1246,6 +1289,49 @@ def woa_candidates_replicas(cat_ptr, qos, x, seg_ptr, local_bounds, global_bound
     dict over the B * R rows (prob_ptr [B*R+1], n_slots, status [B*R], bounds [B*R,4], ...) plus ``replicas`` = R."""
     return _woa_tables("woa_candidates_replicas", True, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions_all, reduct,
                        patches, check_status)
+
+
+def woa_candidates_named(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct=0, patches=(), check_status=True,
+                         action_ids=None):
+    """woa_candidates, and which services its tables consist of (gnnpn_woa_candidates_services, one launch more on the same
+    workspace): the same SearchTables — every shared key bit for bit — plus slot_node [n] i32 (a list's task node: its position
+    inside its workflow graph, >= 1), slot_cat [n] i32 (the node's category, 0-based) and cand_service [m] i32 (the row of ``qos``
+    a candidate was read from; for an appended foreign row the id ``action_ids`` gives for the action row paired with the list, -1
+    without).  ``action_ids`` [B, T'] i32: the rows of ``qos`` that ``actions`` are (ML2PNPipeline.run: candidate_ids gathered by
+    idx_high), or None.  ``SearchTables.services`` maps a search result over these tables to services."""
+    return _woa_tables("woa_candidates_named", None, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions, reduct, patches,
+                       check_status, named=True, action_ids=action_ids)
+
+
+def woa_candidates_replicas_named(cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions_all, reduct=0, patches=(),
+                                  check_status=True, action_ids=None):
+    """woa_candidates_replicas with woa_candidates_named's three keys over the B * R rows (gnnpn_woa_candidates_replicas_services);
+    ``action_ids`` [B, R, T'] i32 or None."""
+    return _woa_tables("woa_candidates_replicas_named", True, cat_ptr, qos, x, seg_ptr, local_bounds, global_bounds, actions_all, reduct,
+                       patches, check_status, named=True, action_ids=action_ids)
+
+
+def services_merit(seg_ptr, node_services, qos, bounds, rounded, max_slots=None, wide=None):
+    """The figure of merit of compositions given as service ids (gnnpn_services_merit_f64): problem b's rows are ``qos[id]`` of its
+    nodes seg_ptr[b] .. seg_ptr[b+1]-1 with id = node_services[node] >= 0, in node order, through round(v, 5) where ``rounded``;
+    the merit is violate + objFunc of those rows under bounds [B, 4], as the searches evaluate it.  seg_ptr [B+1] i32,
+    node_services [N] i32, qos [S, 4] f64.  ``max_slots``: the most rows a problem may have (None: its most nodes, one small copy
+    to the host); ``wide``: the workgroup form for every problem (taken anyway above 64).  Returns (merit [B] f64, n_rows [B]
+    i32).  Not scored, merit NaN: no rows (n_rows 0); more rows than max_slots or an id outside [-1, S) (n_rows -1)."""
+    B = seg_ptr.numel() - 1
+    dev = qos.device
+    if qos.dim() != 2 or qos.shape[1] != 4 or tuple(bounds.shape) != (B, 4) or node_services.dim() != 1:
+        raise GnnpnError("services_merit: seg_ptr [B+1], node_services [N], qos [S, 4], bounds [B, 4] expected")
+    if max_slots is None:
+        max_slots = int((seg_ptr[1:] - seg_ptr[:-1]).max().item()) if B else 1
+    merit = torch.empty(B, dtype=F64, device=dev)
+    n_rows = torch.empty(B, dtype=I32, device=dev)
+    check(_lib.load().gnnpn_services_merit_f64(B, dev_ptr(seg_ptr, I32, "seg_ptr"), node_services.numel(),
+                                               dev_ptr(node_services, I32, "node_services"), dev_ptr(qos, F64, "qos"), qos.shape[0],
+                                               dev_ptr(bounds, F64, "bounds"), int(bool(rounded)), max(int(max_slots), 1), int(bool(wide)),
+                                               dev_ptr(merit, F64, "merit"), dev_ptr(n_rows, I32, "n_rows"), stream_ptr()),
+          "gnnpn_services_merit_f64")
+    return merit, n_rows
 
 
 def _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand):

@@ -318,8 +318,61 @@ def refine(services, batch, out, popSize, MAX_Iter, reduct=0, seeds=None, min_co
     return _quality(res, min_cost, dev)
 
 
+def action_ids_of(out):
+    """The rows of the service table that ``out["actions"]`` are, [B, T] i32, where ``out`` is ``run``'s or ``best_of``'s result:
+    candidate_ids (select.hip writes the row ``s`` of ``qos`` a candidate was read from, -1 for a dummy row) gathered by idx_high
+    (the decoder's picks, positions in the candidate sequence).  None where ``out`` does not carry both."""
+    if not hasattr(out, "keys") or "candidate_ids" not in out or "idx_high" not in out:
+        return None
+    return out["candidate_ids"].gather(1, out["idx_high"].long()).to(torch.int32).contiguous()
+
+
+def _start_action_ids(starts, start_index):
+    """action_ids_of for the winning start of a multi-start result: idx_all [B, N, T] (``best_of(..., return_all=True)``) read at
+    start_index in idx_high's place.  None where ``starts`` does not carry it."""
+    if not hasattr(starts, "keys") or "candidate_ids" not in starts or "idx_all" not in starts:
+        return None
+    idx_all = starts["idx_all"]
+    idx = idx_all.gather(1, start_index.long()[:, None, None].expand(-1, 1, idx_all.shape[2]))[:, 0]
+    return starts["candidate_ids"].gather(1, idx.long()).to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def name_services(services, batch, out, res, reduct=0, patches=()):
+    """Which services the composition of a search result consists of.  ``res``: what ``descend``, the three ``descend_pairs*``,
+    the three ``descend_starts*`` or ``refine`` returned for ``out`` with the same ``reduct`` and ``patches``.  The tables are
+    rebuilt with their ids (ops.woa_candidates_named: deterministic, the tables the search ran on) — of ``res["actions"]`` for a
+    multi-start result (the winner's start rows), else of ``out["actions"]`` — and ``res["best_pos"]`` is mapped through them
+    (gnnpn_search_services; ``refine``'s positions are ES-WOA's, negative ones Python's).  Where ``out`` carries candidate_ids and
+    idx_high (``run``'s result; for a multi-start result idx_all, read at the winner), an appended foreign row is named by
+    ``action_ids_of(out)``; else foreign rows are -1.  Returns ``res``'s keys plus best_services [B, max_slots] i32, node_services [N] i32 (one entry per row
+    of batch.x, -1 where the node has no service) and action_ids_used (a bool).  An id s >= 0 means: row s of the service table,
+    rounded where the tables were seeded, equals best_rows there, absent a patch on that row."""
+    multi = "start_index" in res and "actions" in res
+    actions = res["actions"] if multi else out["actions"]
+    ids = _start_action_ids(out, res["start_index"]) if multi else action_ids_of(out)
+    tabs = ops.woa_candidates_named(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
+                                    actions, reduct=reduct, patches=patches, action_ids=ids)
+    named = tabs.services(res, batch.seg_ptr, batch.x.shape[0])
+    return {**res, **named, "action_ids_used": ids is not None}
+
+
+@torch.no_grad()
+def score_services(services, batch, node_services, rounded=True):
+    """The figure of merit (violate + objFunc under the batch's global bounds) of compositions given as service ids, one entry of
+    ``node_services`` per row of batch.x (-1: no service): ops.services_merit over the service table.  ``rounded``: the rows go
+    through round(v, 5), as the tables of a search that started from action rows hold them — then scoring ``name_services``'
+    node_services gives that search's best_fitness bit for bit (no patches; foreign rows named).  Returns (merit [B] f64,
+    n_rows [B] i32)."""
+    return ops.services_merit(batch.seg_ptr, node_services, services.qos, batch.global_bounds, rounded)
+
+
 class ML2PNPipeline:
     """net: modelML.Net; low/high: modelPN.CombinatorialRL (levels "Low"/"High")."""
+
+    def name_services(self, services, batch, out, res, reduct=0, patches=()):
+        """Module-level ``name_services`` (it needs no network)."""
+        return name_services(services, batch, out, res, reduct=reduct, patches=patches)
 
     def __init__(self, net, low, high, n_per, precision=None):
         from .modelPN import default_precision

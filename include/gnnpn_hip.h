@@ -958,6 +958,54 @@ int gnnpn_woa_candidates_replicas_fill(int32_t B, int32_t R, int32_t n_nodes, co
                                        int32_t* cand_ptr, int32_t* len_init, double* cand, int32_t* start_pos, void* stream);
 int gnnpn_debug_round5_f64(const double* x, double* y, int64_t n, void* stream);
 
+/* Which services the candidate tables consist of (csrc/woa_prep.hip).  New: the reference keeps rows, never ids.  Behind
+ * gnnpn_woa_candidates_count (or _replicas_count), on its workspace and with the n_lists / n_cand the fill takes, independent of
+ * the fill: slot_node [n_lists] — for list j = prob_ptr[q] + l the position of its task node inside its workflow graph
+ * (g - seg_ptr[b] >= 1: node 0 is the request node); slot_cat [n_lists] — that node's category, 0-based; cand_service [n_cand] —
+ * for candidate i < len_init[j] the row of qos it was read from (cat_ptr[cat] + its position in the category), for the appended
+ * foreign row (i == len_init[j], where the list is one longer) the id given for the action row paired with the list, or -1.
+ * action_ids [rows, actions_T] i32 or NULL: the rows of qos the action rows are; compacted as the count kernel compacts the rows
+ * (entries whose action row is a dummy, float64 sum == 3, dropped; the l-th remaining id pairs with list l).  actions is read for
+ * that alone (NULL allowed with action_ids NULL).  Rows with a non-zero status write nothing.  One wavefront per row, plain stores.
+ * Errors as the fill's; GNNPN_E_UNSUP above 1024 action rows. */
+int gnnpn_woa_candidates_services(int32_t B, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr, const void* actions,
+                                  int32_t actions_f64, int32_t actions_T, const int32_t* action_ids, int32_t max_cat_size,
+                                  const void* workspace, int64_t workspace_bytes, const int32_t* status, const int32_t* prob_ptr,
+                                  int32_t n_lists, int32_t n_cand, int32_t* slot_node, int32_t* slot_cat, int32_t* cand_service,
+                                  void* stream);
+int gnnpn_woa_candidates_replicas_services(int32_t B, int32_t R, int32_t n_nodes, const int32_t* seg_ptr, const int32_t* cat_ptr,
+                                           const void* actions, int32_t actions_f64, int32_t actions_T, const int32_t* action_ids,
+                                           int32_t max_cat_size, const void* workspace, int64_t workspace_bytes, const int32_t* status,
+                                           const int32_t* prob_ptr, int32_t n_lists, int32_t n_cand, int32_t* slot_node,
+                                           int32_t* slot_cat, int32_t* cand_service, void* stream);
+
+/* From the positions a search stage returns to services (csrc/services.hip).  Problem b reads the tables of row q = b * R +
+ * start_index[b] (start_index NULL: replica 0; the winner of gnnpn_descend_select_f64; R = 1: the problem itself): slot l's
+ * position p = best_pos[b * pos_ld + l], p < 0 meaning the Python position p + len of its list, names cand_service[cand_ptr[j] +
+ * p]; a position outside its list after that yields -1.  A problem whose best_fitness is NaN (not searched, not sized for, failed in
+ * the builder), whose row has no lists or more than pos_ld, or whose start_index is outside 0 .. R-1 yields -1 throughout: the test
+ * is the merit, because a not-searched row holds positions of -1 and that is a valid Python position.  Outputs: best_services
+ * [B, pos_ld] (-1 past the problem's slot count) and node_services [n_nodes], one entry per node of the batch: the service of a task
+ * node, -1 for request nodes, for tasks whose list was empty and for problems that yield -1 (nodes outside every segment are not
+ * written).  n_lists / n_cand: the entries of slot_node / cand_service (bounds of every read).  One wavefront per problem, plain
+ * stores, every node written once. */
+int gnnpn_search_services(int32_t B, int32_t R, const int32_t* start_index, const double* best_fitness, const int32_t* best_pos,
+                          int32_t pos_ld, const int32_t* prob_ptr, int32_t n_lists, const int32_t* cand_ptr, int32_t n_cand,
+                          const int32_t* cand_service, const int32_t* slot_node, const int32_t* seg_ptr, int32_t n_nodes,
+                          int32_t* best_services, int32_t* node_services, void* stream);
+
+/* The figure of merit of compositions given as service ids (csrc/services.hip): problem b's rows are qos[id] of its nodes
+ * seg_ptr[b] .. seg_ptr[b+1]-1 with id = node_services[node] >= 0, in node order, every value through Python's round(v, 5) where
+ * rounded == 1 (the rows of a seeded table); merit[b] = violate + objFunc of those rows under bounds [B,4], evaluated by the
+ * statements the searches use (csrc/woa_eval.h) — scoring what gnnpn_search_services names gives the search's best_fitness bit for
+ * bit, absent patches and foreign rows without an id.  n_rows[b] = the row count.  Not scored, merit NaN: no rows (n_rows 0:
+ * objFunc divides by the count); more rows than max_slots, an id outside [-1, n_services) or a bad segment (n_rows -1).  Lane form
+ * (one wavefront per problem) for max_slots <= 64, workgroup form above or with wide != 0; both give the same bits.
+ * GNNPN_E_UNSUP where max_slots rows exceed a CU's LDS. */
+int gnnpn_services_merit_f64(int32_t B, const int32_t* seg_ptr, int32_t n_nodes, const int32_t* node_services, const double* qos,
+                             int32_t n_services, const double* bounds, int32_t rounded, int32_t max_slots, int32_t wide, double* merit,
+                             int32_t* n_rows, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training step of the GNN candidate-ranking model.  Replaces the autograd graph of
  * src/models/trainML.py:39-45 over src/models/modelML.py:131-176 (model.train(): BatchNorm1d on batch statistics).  The

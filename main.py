@@ -201,6 +201,9 @@ def main(argv):
         if rounds is not None and (sweeps is None or int(rounds) < 1):
             print("--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round")
             return 1
+        if "--services" in flags and sweeps is None and "--woa" not in flags:
+            print("--services: needs --descend[=SWEEPS] or --woa (the services of a searched composition)")
+            return 1
         span = next((a.split("=", 1)[1] for a in flags if a.startswith("--span=")), "" if "--span" in flags else None)
         top = next((a.split("=", 1)[1] for a in flags if a.startswith("--top=")), "" if "--top" in flags else None)
         if top is not None:
@@ -243,7 +246,11 @@ def main(argv):
             best["pair_rounds"] = int(rounds)
         if span is not None:                                        # ... at any slot count, over slots at most N apart
             best["pair_span"] = int(span)
-        if top is not None:                                         # ... over the M best candidates of each slot (refused beside --woa)
+        if "--services" in flags:                                   # the same run, plus ML+2PN+services.txt: which services it found
+            if top is not None:
+                best["pair_rank"] = int(top)
+            ML2PN.infer_services(ds, net, low, high, K, epoch, woa=woa, **best)
+        elif top is not None:                                       # ... over the M best candidates of each slot (refused beside --woa)
             ML2PN.infer_pairs_shortlist(ds, net, low, high, K, epoch, pair_rank=int(top), **best)
         elif "pair_span" in best:                                   # (refused above beside --woa and --all-starts)
             ML2PN.infer_pairs_windowed(ds, net, low, high, K, epoch, **best)
