@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_decode_reference as adr
 from conftest import golden
 from oracle import pn as opn
 from parity import LOGIT_ATOL, R_ATOL, assert_index_parity, assert_R_parity, prefix_parity, robust_problems
@@ -825,3 +826,154 @@ def test_empty_and_degenerate_shapes(dev):
         # the reference-style call on the same shape
         R, probs, actions, idxs, _ = nets[1](x, None, nets[0](x, None, sample="greedy", training="SL")[4], sample="greedy")
         assert R.shape == (B,) and len(idxs) == T and idxs[0].shape == (B,)
+
+
+# ---- the general attention decoder (pointer_decode_glimpse_kernel<H, BAHDANAU>), build by build, against a float64 replay of its
+# own path: tests/attn_decode_reference.py holds the reference, the seeded inputs, the cases and the decision rules;
+# tests/test_attn_decode_host.py holds the cases to what gives these rules their bite, on the CPU
+_ATTN_REC = None
+
+
+def _attn_recorder():
+    global _ATTN_REC
+    if _ATTN_REC is None:
+        from kernel_checks import Recorder
+        _ATTN_REC = Recorder("attn_decode")
+    return _ATTN_REC
+
+
+def _attn_decode_run(dev, w, c, repeat=True):
+    """ops.pointer_decode_attn on the operands ``w`` of case ``c``, twice (the same bits in every output; once without ``repeat``),
+    status clean; the outputs on the host."""
+    from gnnpn_sc_amd import ops
+    from kernel_checks import twice
+    H = c.H
+    d = {k: v.to(dev) for k, v in w.items() if v is not None}
+    net = {k: d[k] for k in ("embedded", "enc_out", "h0", "c0", "start", "bih", "bhh")}
+    net.update(wih=ops.pack_lstm_weight(d["wih"]), whh=ops.pack_lstm_weight(d["whh"]), latent_win=d.get("latent"))
+    if c.sample_seed is not None:
+        net.update(sample=True, sample_seed=c.sample_seed)
+
+    def side(tag):
+        if f"{tag}_wq" not in d:
+            return None
+        return {"wq": d[f"{tag}_wq"], "bq": d[f"{tag}_bq"], "v": d[f"{tag}_v"], "bref": torch.zeros(H, device=dev),
+                "wref": torch.eye(H, device=dev) * adr.W_REF_SCALE[tag]}
+    run = lambda: ops.pointer_decode_attn(net, d["inputs"], c.T, c.K, "Bahdanau" if c.bah else "Dot", c.G, pointer=side("p"),   # noqa: E731
+                                          glimpse=side("g"), tanh_c=c.C, use_tanh=bool(c.use_tanh), want_queries=True)
+    out = twice(run) if repeat else run()
+    ops.check_status(dev)
+    return {k: out[k].cpu() for k in ("idx", "win_logits", "pick_prob", "actions", "queries")}
+
+
+def _attn_decode_check(dev, w, c, kernel, floor_rel=2e-6, pick_prob=True, repeat=True, bite=True):
+    """The statement of test_attention_decode_build_vs_float64_replay for one case.  -> (outputs, float64 replay, eps)."""
+    from kernel_checks import same_bits
+    B, T, K = c.B, c.T, c.K
+    got = _attn_decode_run(dev, w, c, repeat)
+    # exact: every pick inside its step's window, every action row the input row of the pick
+    idx = got["idx"].long()
+    lo = torch.arange(T) * K
+    assert bool(((idx >= lo) & (idx < lo + K)).all()), "a pick outside its window"
+    assert same_bits(got["actions"], w["inputs"][torch.arange(B).unsqueeze(1), idx]), "an action row is not the pick's input row"
+    pick = idx - lo
+    # numeric: the kernel's own path replayed in float64 and in float32
+    r64, r32 = adr.replay(w, c, adr.D, idx=idx), adr.replay(w, c, adr.F32, idx=idx)
+    at = lambda r: torch.gather(r["probs"], 2, pick.unsqueeze(2)).squeeze(2)      # noqa: E731
+    rec = _attn_recorder()
+    quantities = [("win_logits", got["win_logits"], r64["z0"], r32["z0"]), ("queries", got["queries"], r64["q"], r32["q"])]
+    if pick_prob:
+        quantities.append(("pick_prob", got["pick_prob"], at(r64), at(r32)))
+    failures = []
+    for what, g, a, b in quantities:
+        assert bool(torch.isfinite(g).all()), what
+        try:
+            rec.yardstick(kernel, what, g, a, b, floor_rel=floor_rel)
+        except AssertionError as e:                                               # every quantity is measured before the test fails
+            failures.append(str(e))
+    print(f"{kernel} [{c.id}]:", {k: f"{v:.3g}" for k, v in rec.worst[kernel].items()})
+    assert not failures, failures
+    # decisions: every one of them, none left out
+    eps = adr.allowance(r64, r32)
+    if c.sample_seed is None:
+        adr.check_greedy(pick, r64["z"], eps)
+    else:
+        adr.check_sampled(pick, r64["probs"], c.sample_seed)
+    if bite:
+        adr.assert_bite(c, r64, eps)                                              # what gives the rule its bite, from float64 alone
+    return got, r64, eps
+
+
+def _attn_kernel_name(c):
+    return f"pointer_decode_glimpse_{c.H}_{'bahdanau' if c.bah else 'dot'}"
+
+
+@pytest.mark.parametrize("c", adr.CASES, ids=[c.id for c in adr.CASES])
+def test_attention_decode_build_vs_float64_replay(dev, c):
+    """pointer_decode_glimpse_kernel<H, BAHDANAU> (ops.pointer_decode_attn; 'Dot' and 'Bahdanau' at H = 32 and 256) at the shapes
+    and switch settings where its loops change shape: T beyond one stride of the mask loop, sequences shorter than a workgroup and
+    than its wave count, full / forced / odd windows, 0 to 8 glimpse rounds, no tanh, other tanh_c, with and without the latent,
+    drawn picks, 300 workgroups.  The kernel's own picks are replayed through the reference in float64 and float32.
+    Exact: two runs give the same bits; every pick lies in its window; every action row is the pick's input row; clean status.
+    Numeric (kernel_checks.Recorder.yardstick, its defaults): the error of win_logits, queries and pick_prob against float64 is
+    at most four times torch's own fp32 error plus 2e-6 of the scale.  The longest sums here run over 259 positions (one fmaf chain
+    per query element): sqrt(259) * 2^-24 < 1e-6, so the default floor stands for every quantity.
+    Decisions, every one: eps = 4 max|z32 - z64| + 2e-6 max|z64| is what the logits themselves are allowed; a greedy pick's
+    float64 logit is within 2 eps of the window's float64 maximum; a drawn pick is the draw rule's on the float64 cdf (a neighbour
+    where u is within parity.TAU_DRAW of the boundary).  The shares that give these rules their bite (margins above 2 eps in
+    >= 98 % of the decisions; >= 30 % of the drawn picks not the argmax, <= 2 % of the draws near a boundary) are asserted from
+    float64 alone, here and on the CPU (test_attn_decode_host.py)."""
+    _attn_decode_check(dev, adr.decode_inputs(c), c, _attn_kernel_name(c))
+
+
+@pytest.mark.parametrize("c", adr.FIRST_MAX_CASES, ids=[c.id for c in adr.FIRST_MAX_CASES])
+def test_attention_decode_first_maximum_on_equal_rows(dev, c):
+    """Equal rows of enc_out (and so of ref) with equal latents give logits equal bit for bit, and the pick is the FIRST maximum
+    (torch.max on the CPU): a window of K copies is picked at its first position; a window with copies at positions 1 and 4 only,
+    which stand above the rest by more than 2 eps in float64, is picked at position 1.  Exact assertions."""
+    from kernel_checks import same_bits
+    K, pw, ew = c.K, adr.PAIR_WINDOW, adr.EQUAL_WINDOW
+    w = adr.equal_rows_inputs(c)
+    got, r64, eps = _attn_decode_check(dev, w, c, _attn_kernel_name(c) + "_ties", bite=False)   # half of the windows are ties on purpose
+    win = got["win_logits"]
+    assert same_bits(win[:, ew], win[:, ew, :1].expand(-1, K).contiguous()), "equal rows, different logits"
+    assert torch.equal(got["idx"][:, ew].long(), torch.full((c.B,), ew * K)), got["idx"]
+    assert same_bits(win[:, pw, adr.PAIR[0]], win[:, pw, adr.PAIR[1]])
+    assert float(adr.pair_margin(r64).min()) > 2 * eps
+    assert torch.equal(got["idx"][:, pw].long(), torch.full((c.B,), pw * K + adr.PAIR[0])), got["idx"]
+
+
+def test_attention_decode_lds_limit(dev, monkeypatch):
+    """The dynamic-LDS limit of the launch, (L + T) * 4 bytes <= 120 KB (H = 32, B = 1, 'Dot', one glimpse round).
+    Refused: T = 480, n_per = 64, with code -2 and before any launch — the outputs the call allocated still hold what they held.
+    Accepted and run: T = 257, n_per = 63, 65 792 bytes, the fewest steps whose dynamic LDS is still past 64 KB (the launch has to
+    ask for more than the default), held to the float64 replay of its path like every other case: win_logits and queries by
+    yardstick with its defaults, every decision by the 2 eps rule; one run.  The exact edge, T = 480 and n_per = 63 (30 720 words =
+    120 KB), was measured once on an MI355X: accepted, its picks within 2 eps of the float64 maxima, win_logits and queries within
+    0.24 and 0.38 of a yardstick with the floor 1e-5 — and 12.3 s for two runs and the two replays (one wavefront walks 30 240
+    positions in each of 480 steps), too long for this suite; the case that stays does about (257 / 480)^2 of that work, 1.8 s."""
+    from gnnpn_sc_amd import ops
+    c = adr.LDS_EDGE
+    assert 64 * 1024 < (c.T * c.K + c.T) * 4 <= 120 * 1024
+    _attn_decode_check(dev, adr.decode_inputs(c), c, "pointer_decode_glimpse_32_dot_lds_past_64k", pick_prob=False, repeat=False)
+    over = c._replace(T=adr.LDS_REFUSED[0], K=adr.LDS_REFUSED[1])
+    w = adr.decode_inputs(over)
+    made, outputs = [], ops._decode_outputs
+
+    def sentinel_outputs(*a):
+        out = outputs(*a)
+        out["idx"].fill_(-7)
+        for k in ("win_logits", "pick_prob", "actions"):
+            out[k].fill_(-7.0)
+        made.append(out)
+        return out
+    monkeypatch.setattr(ops, "_decode_outputs", sentinel_outputs)
+    d = {k: v.to(dev) for k, v in w.items() if v is not None}
+    net = {k: d[k] for k in ("embedded", "enc_out", "h0", "c0", "start", "bih", "bhh")}
+    net.update(wih=ops.pack_lstm_weight(d["wih"]), whh=ops.pack_lstm_weight(d["whh"]), latent_win=d["latent"])
+    with pytest.raises(ops.GnnpnError, match=r"\(-2\).*does not fit the LDS buffer"):
+        ops.pointer_decode_attn(net, d["inputs"], over.T, over.K, "Dot", 1)
+    torch.cuda.synchronize()
+    ops.check_status(dev)
+    assert len(made) == 1
+    assert bool((made[0]["idx"] == -7).all()) and all(bool((made[0][k] == -7.0).all()) for k in ("win_logits", "pick_prob", "actions"))
