@@ -8,12 +8,7 @@
 #include <vector>
 
 #include "common.h"
-
-// float_order_key puts -0 below +0; a ranking must not: score + (+0), rounded to nearest, is +0 for either zero and the score itself
-// for every other value (denormals are kept; a NaN stays a NaN and still sorts above +inf).
-__device__ __forceinline__ unsigned long long rank_key(float score, uint32_t id) {
-    return ((unsigned long long)float_order_key(__fadd_rn(score, 0.0f)) << 32) | (0xffffffffu - id);
-}
+#include "select_keys.h"   // rank_key, row16_max_u64, row8_max_u64
 
 __global__ __launch_bounds__(256) void select_candidates_kernel(
     const float* __restrict__ scores, int64_t ld_scores, const int32_t* __restrict__ cat_ptr,
@@ -75,24 +70,7 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(
 // The same reduction with 16 lanes per (problem, category) segment, four segments per wave, for n_per <= 16: the row-wide
 // maximum is four DPP rotations instead of six cross-wave shuffles on each key half, and a category of 5 services (the
 // 1000-task shapes) no longer occupies a whole wave.  Same keys, same order of picks, same emitted rows.
-__device__ __forceinline__ unsigned long long row16_max_u64(unsigned long long v) {
-#define GNNPN_MAX_STEP(CTRL)                                                                                       \
-    {                                                                                                              \
-        const unsigned lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xF, 0xF, true);                \
-        const unsigned hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xF, 0xF, true);        \
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                                          \
-        v = o > v ? o : v;                                                                                         \
-    }
-    GNNPN_MAX_STEP(0x121) GNNPN_MAX_STEP(0x122) GNNPN_MAX_STEP(0x124) GNNPN_MAX_STEP(0x128)   // row_ror:1, 2, 4, 8
-    return v;
-}
-// ... and over groups of 8 lanes: the neighbour, the other pair (quad_perm), the other quad (row_half_mirror); a maximum does
-// not depend on the order it is formed in
-__device__ __forceinline__ unsigned long long row8_max_u64(unsigned long long v) {
-    GNNPN_MAX_STEP(0xB1) GNNPN_MAX_STEP(0x4E) GNNPN_MAX_STEP(0x141)
-    return v;
-#undef GNNPN_MAX_STEP
-}
+// (row16_max_u64 / row8_max_u64: select_keys.h)
 
 // W = 16 or 8 lanes per segment; 8 (n_per <= 8, categories of about 8 services or fewer: the 1000-task shapes have 5) puts eight
 // segments into a wave — the kernel is bound by its vector instructions, which are per wave.

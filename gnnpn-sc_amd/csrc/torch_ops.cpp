@@ -223,6 +223,32 @@ std::tuple<Tensor, Tensor> segment_topk_feasible(const Tensor& scores, const Ten
     return {rows, ids};
 }
 
+// plan_host / plan: the words of score_plan.ScorePlan on the host and on the device -> scores, rows, ids
+std::tuple<Tensor, Tensor, Tensor> score_select(const Tensor& xr, const Tensor& emb_packed, const Tensor& plan_host, const Tensor& plan,
+                                                const Tensor& qos, const Tensor& local_bounds, const Tensor& present,
+                                                const Tensor& global_bounds, int64_t n_per) {
+    GNNPN_ON_DEVICE_OF(xr);
+    rows2d(xr, "score_select.xr");
+    TORCH_CHECK(plan_host.is_cpu() && plan_host.scalar_type() == at::kInt && plan_host.is_contiguous() && plan_host.numel() >= 4,
+                "score_select: plan_host must be a contiguous int32 host tensor");
+    TORCH_CHECK(plan.numel() == plan_host.numel(), "score_select: plan and plan_host differ in length");
+    const int32_t* ph = static_cast<const int32_t*>(plan_host.data_ptr());
+    const int64_t B = xr.size(0), T = ph[0], n_tiles = ph[2], S = ph[3];
+    TORCH_CHECK(T > 0 && S > 0 && n_tiles > 0 && n_per >= 1, "score_select: bad plan header");
+    TORCH_CHECK(emb_packed.numel() == n_tiles * 8 * 64 * 4, "score_select: emb_packed has ", emb_packed.numel(), " elements, the plan's ", n_tiles,
+                " tiles need ", n_tiles * 8 * 64 * 4);
+    TORCH_CHECK(qos.sizes() == at::IntArrayRef({S, 4}) && local_bounds.sizes() == at::IntArrayRef({B, T, 4}) &&
+                    present.sizes() == at::IntArrayRef({B, T}) && global_bounds.sizes() == at::IntArrayRef({B, 4}),
+                "score_select: inconsistent shapes");
+    Tensor scores = new_f32(xr, {B, S}), rows = new_f32(xr, {B, T * n_per, 8}), ids = new_i32(xr, {B, T * n_per});
+    check_rc(gnnpn_score_select_f32(f32(xr, "xr"), xr.size(1), f32(emb_packed, "emb_packed"), ph, i32(plan, "plan"), (int32_t)plan_host.numel(),
+                                    cptr<double>(qos, at::kDouble, "qos"), cptr<double>(local_bounds, at::kDouble, "local_bounds"),
+                                    cptr<uint8_t>(present, at::kByte, "present"), cptr<double>(global_bounds, at::kDouble, "global_bounds"),
+                                    out_f32(scores), S, out_f32(rows), static_cast<int32_t*>(ids.data_ptr()), (int32_t)B, (int32_t)xr.size(1),
+                                    (int32_t)n_per, cur_stream()), "gnnpn_score_select_f32");
+    return {scores, rows, ids};
+}
+
 Tensor rank_rows(const Tensor& scores) {
     GNNPN_ON_DEVICE_OF(scores);
     rows2d(scores, "rank_rows.scores");
@@ -425,6 +451,8 @@ TORCH_LIBRARY(gnnpn, m) {
           "Tensor w2, Tensor i2, Tensor? b2, Tensor? a2, Tensor? s2, Tensor? w3=None, Tensor? i3=None, Tensor? b3=None) -> Tensor");
     m.def("segment_topk_feasible(Tensor scores, Tensor cat_ptr, Tensor qos, Tensor local_bounds, Tensor present, Tensor global_bounds, "
           "int n_per) -> (Tensor, Tensor)");
+    m.def("score_select(Tensor xr, Tensor emb_packed, Tensor plan_host, Tensor plan, Tensor qos, Tensor local_bounds, Tensor present, "
+          "Tensor global_bounds, int n_per) -> (Tensor, Tensor, Tensor)");
     m.def("rank_rows(Tensor scores) -> Tensor");
     m.def("precision_at_k(Tensor ranking, Tensor labels, int[] ks) -> Tensor");
     m.def("attention_logits(Tensor enc_out, Tensor queries, int step, Tensor idx, float tanh_c, bool use_tanh) -> Tensor");
@@ -448,6 +476,7 @@ TORCH_LIBRARY_IMPL(gnnpn, CUDA, m) {
     m.impl("gin_layer", gin_layer);
     m.impl("gin_layer_split", gin_layer_split);
     m.impl("segment_topk_feasible", segment_topk_feasible);
+    m.impl("score_select", score_select);
     m.impl("rank_rows", rank_rows);
     m.impl("precision_at_k", precision_at_k);
     m.impl("attention_logits", attention_logits);

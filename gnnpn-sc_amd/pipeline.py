@@ -17,7 +17,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, custom_ops, graph, ops   # noqa: F401  (custom_ops registers torch.ops.gnnpn.*)
+from . import _lib, custom_ops, graph, ops, score_plan   # noqa: F401  (custom_ops registers torch.ops.gnnpn.*)
 from .modelPN import two_level_best_of, two_level_greedy
 
 
@@ -29,6 +29,7 @@ class DeviceServices:
     cat_ptr: torch.Tensor        # i32 [T+1]
     qos: torch.Tensor            # f64 [S,4]
     emb_cache: tuple = None      # (prepared-weights object, [S,hidden] service embedding): see ML2PNPipeline.service_embedding
+    score_cache: dict = None     # the fused score + select kernel's operands for emb_cache's embedding: see ML2PNPipeline.score_select_operands
 
     @staticmethod
     def from_table(table, device):
@@ -410,6 +411,52 @@ class ML2PNPipeline:
                                                      batch.present, batch.global_bounds, self.n_per)
 
     @torch.no_grad()
+    def score_select_operands(self, services, batch):
+        """(packed service embedding, plan_host, plan) of the one-launch score product + candidate reduction
+        (torch.ops.gnnpn.score_select, csrc/score_select.hip), or None where the two launches stay: GNNPN_UNFUSED_FRONT=1, the
+        service embedding not cached, or a shape the kernel is not built for (score_plan.applies: hidden 128, n_per <= 16, mean
+        category >= 16 services, largest <= 256 — the 1000- and 2000-task shapes with 5 or 10 services per category keep
+        select.hip's 8-lane form).  The packed embedding follows the service embedding (one per (weights, table)); the chunk plan
+        depends on the table only and is kept per chunk count — about one workgroup per CU for this batch's tiles of 16 problems."""
+        if score_plan.unfused_front() or not self.cache_service_embedding:
+            return None
+        hidden = self.net.nodeLin.weight.shape[0]
+        c = services.score_cache
+        if c is None:
+            cat = services.cat_ptr.cpu().numpy()
+            c = services.score_cache = {"cat_ptr": cat, "applies": {}, "plans": {}, "emb": None, "packed": None}
+        key = (int(hidden), int(self.n_per))
+        if key not in c["applies"]:
+            c["applies"][key] = score_plan.applies(c["cat_ptr"], *key)
+        if not c["applies"][key]:
+            return None
+        dev = services.qos.device
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        n_chunks = min(len(c["cat_ptr"]) - 1, max(1, n_cu // max(1, (batch.n_problems + 15) // 16)))
+        if n_chunks not in c["plans"]:
+            plan = score_plan.plan_chunks(c["cat_ptr"], n_chunks)
+            c["plans"][n_chunks] = None if plan is None else (plan, *plan.tensors(dev))
+        if c["plans"][n_chunks] is None:
+            return None
+        plan, plan_host, plan_dev = c["plans"][n_chunks]
+        emb = self.service_embedding(services)
+        if c["emb"] is not emb:
+            c["emb"], c["packed"] = emb, score_plan.pack_embedding(emb, plan)      # (the tile layout is the same in every plan)
+        return c["packed"], plan_host, plan_dev
+
+    @torch.no_grad()
+    def front(self, services, batch):
+        """scores [B,S], pn_inputs rows [B, T*n_per, 8], candidate_ids: ``scores`` then ``candidates``, or the one launch that
+        computes the same three (``score_select_operands``) behind the request branch."""
+        fused = self.score_select_operands(services, batch)
+        if fused is None:
+            scores = self.scores(services, batch)
+            return (scores, *self.candidates(services, batch, scores))
+        xr = self.net.request_embedding(batch.x, batch.wf_csr, batch.seg_ptr, batch.max_nodes,
+                                        "split" if self.precision == "split" else "f32")
+        return torch.ops.gnnpn.score_select(xr, *fused, services.qos, batch.local_bounds, batch.present, batch.global_bounds, self.n_per)
+
+    @torch.no_grad()
     def run(self, services, batch, decode_impl=0, lds_kb=0, ws=None, paired_start=False, write_through=False):
         """One pass.  decode_impl / lds_kb / paired_start / ws: launch options of the recurrent kernels (modelPN.two_level_greedy;
         paired_start: the caller starts these launches together with a partner's — half-batches do by construction).
@@ -417,8 +464,7 @@ class ML2PNPipeline:
         stream (fork / join, capturable) — the problems are independent, and two cooperative launches of one workgroup
         per CU each share every CU for their whole length (encoder beside encoder, decoder beside decoder), which two
         whole batches in flight on two slots do only where their timelines happen to line up."""
-        scores = self.scores(services, batch)
-        rows, ids = self.candidates(services, batch, scores)
+        scores, rows, ids = self.front(services, batch)
         if isinstance(ws, (tuple, list)):
             B = rows.shape[0]
             half = half_batch_split(B)
@@ -462,8 +508,7 @@ class ML2PNPipeline:
         winners) plus sample_index, R_all and idx_all.  seed None: fresh OS entropy.  A separate call: run / capture are
         unchanged; not capturable (it checks the cooperative launches' status before it returns).  ``return_all``: also actions_all
         [B, samples, T, 8|9], every replica's rows (replica 0 the greedy ones): the starts of ``descend_starts``."""
-        scores = self.scores(services, batch)
-        rows, ids = self.candidates(services, batch, scores)
+        scores, rows, ids = self.front(services, batch)
         out = two_level_best_of(self.low, self.high, rows, samples, seed=seed, precision=self.precision, decode_impl=decode_impl,
                                 lds_kb=lds_kb, write_through=write_through, ws=ws, return_all=return_all)
         out.update(scores=scores, pn_inputs=rows, candidate_ids=ids)

@@ -246,6 +246,35 @@ int gnnpn_select_candidates(const float* scores, int64_t ld_scores, const int32_
                             const uint8_t* present, const double* global_bounds, float* out_rows,
                             int32_t* out_ids, int32_t B, int32_t T, int32_t n_per, void* stream);
 
+/* The score product and the candidate reduction in ONE launch: scores = sigmoid(xr . emb^T) as gnnpn_linear_f32 with
+ * GNNPN_ACT_SIGMOID writes them, out_rows / out_ids as gnnpn_select_candidates derives them from those scores — the same bits
+ * in all three (the product is the same k-ascending fp32 fma chain per element; the keys and the tie rule are select's).
+ * Built for hidden = 128, 1 <= n_per <= 16, categories of at most GNNPN_SCORE_SELECT_MAX_CATEGORY services (GNNPN_E_UNSUP
+ * otherwise: use the two calls).  Worth it where a category has 16 services or more on average; any plan gives the same result.
+ *   xr          [B, ldx] fp32 request embedding, 16-byte aligned, ldx >= 128 and a multiple of 4
+ *   emb_packed  the [S, 128] service embedding as v_mfma_f32_16x16x4_f32 B-fragments, every category its own run of 16-column
+ *               tiles: [n_tiles][8][64][4], element [t][kb][lane][j] = emb[first service of tile t + lane % 16][16 kb + 4 j + lane / 16],
+ *               0 behind the category's last service (a layout change, once per service table)
+ *   plan_host / plan_dev  the same plan_words int32 words in host and in device memory: T, n_chunks, n_tiles, S, cat_ptr [T+1],
+ *               tile_ptr [T+1] (first tile of a category: ceil(size / 16) tiles each), chunk_ptr [n_chunks+1] (first category of
+ *               a chunk; chunks are runs of whole categories, empty ones allowed, of at most GNNPN_SCORE_SELECT_MAX_TILES tiles
+ *               and GNNPN_SCORE_SELECT_MAX_CHUNK_CATEGORIES categories), chunk_info [n_chunks][8] (per chunk: first category,
+ *               end category, first tile, tiles, first service, end service, 0, 0 — the pointers above, repeated so that a
+ *               workgroup reads its chunk with one load).
+ *               The host copy is checked before the launch (GNNPN_E_ARG); the grid is ceil(B / 16) x n_chunks workgroups.
+ *   qos, local_bounds, present, global_bounds, out_rows, out_ids, n_per: as gnnpn_select_candidates (qos 16-byte aligned)
+ *   scores      [B, ld_scores] fp32, ld_scores >= S; columns >= S are not written
+ * Replaces: the score product of Net.forward (src/models/modelML.py:173-176) + the per-row sort of TrainML.test
+ * (src/models/trainML.py:60-68) + loadDataPN (src/loadData.py:101-149) + SCDataset's column drop (src/models/trainPNHigh.py:23-31).
+ */
+#define GNNPN_SCORE_SELECT_MAX_CATEGORY 256
+#define GNNPN_SCORE_SELECT_MAX_TILES 24
+#define GNNPN_SCORE_SELECT_MAX_CHUNK_CATEGORIES 16
+int gnnpn_score_select_f32(const float* xr, int64_t ldx, const float* emb_packed, const int32_t* plan_host,
+                           const int32_t* plan_dev, int32_t plan_words, const double* qos, const double* local_bounds,
+                           const uint8_t* present, const double* global_bounds, float* scores, int64_t ld_scores,
+                           float* out_rows, int32_t* out_ids, int32_t B, int32_t hidden, int32_t n_per, void* stream);
+
 /* Full descending ranking of every score row (ties: lowest id first; -0.0 and +0.0 tie, as in a stable descending sort):
  * ranking [B,S] int32, contiguous; ld_scores >= S is the row stride of scores.
  * S <= 32768 (one LDS bitonic sort per row: 64-bit keys up to 16384, service ids with keys formed on the fly above).
