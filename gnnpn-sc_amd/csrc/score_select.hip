@@ -11,8 +11,8 @@
 //      epilogue_element(sigmoid) unchanged; the tile goes to `scores` AND stays in LDS.
 //   2. selection: one 16-lane DPP row per (problem, category), so the workgroup reduces 16 segments at once.  The chunk's QoS
 //      rows were staged in LDS once for all 16 problems; a lane forms the rank_key of its services ONCE (0: infeasible)
-//      and the n_per rounds are row16_max_u64 over those registers under the `key < last` filter.  Rows and ids are emitted
-//      exactly as select_candidates16_kernel emits them (cyclic repetition, dummy rows, the global bounds at category 0, -1 ids).
+//      and the n_per rounds (pick_rounds) are row16_max_u64 over those registers under the `key < last` filter.  Rows and ids
+//      leave through select.hip's writer too (select_keys.h: cyclic_pick, emit_row).
 #include "common.h"
 #include "select_keys.h"
 
@@ -59,7 +59,7 @@ struct ScoreSelectArgs {
 template <int NK>
 __device__ __forceinline__ int select_row(const float* srow, const double* q4, const double* lb, bool pres, int s_begin, int n, int sub,
                                           int n_per, int& my_pick) {
-    const double lo_c = lb[0], hi_c = lb[1], lo_q = lb[2], hi_q = lb[3];
+    const CellBounds bounds = cell_bounds(lb);
     double cost[NK], qual[NK];
     float score[NK];
 #pragma unroll
@@ -70,26 +70,20 @@ __device__ __forceinline__ int select_row(const float* srow, const double* q4, c
     unsigned long long key[NK];
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
-        const bool ok = pres && sub + 16 * j < n && lo_c <= cost[j] && cost[j] <= hi_c && lo_q <= qual[j] && qual[j] <= hi_q;
+        const bool ok = pres && sub + 16 * j < n && feasible(cost[j], qual[j], bounds);
         const unsigned long long k = rank_key(score[j], (uint32_t)(s_begin + sub + 16 * j));
         key[j] = ok ? k : 0ull;
     }
-    unsigned long long last = ~0ull;
-    int n_found = 0;
-    for (int r = 0; r < n_per; ++r) {
+    auto local_best = [&](unsigned long long last) {
         unsigned long long best = 0ull;
 #pragma unroll
         for (int j = 0; j < NK; ++j) {
             const unsigned long long k = key[j] < last ? key[j] : 0ull;
             best = k > best ? k : best;
         }
-        best = row16_max_u64(best);
-        if (best == 0ull) break;
-        if (sub == r) my_pick = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffu));
-        last = best;
-        ++n_found;
-    }
-    return n_found;
+        return best;
+    };
+    return pick_rounds(n_per, sub, my_pick, local_best, [](unsigned long long v) { return row16_max_u64(v); });
 }
 }  // namespace
 
@@ -147,10 +141,7 @@ __global__ __launch_bounds__(NT) void score_select_kernel(ScoreSelectArgs a) {
         *reinterpret_cast<double2*>(lbs + (cl * PT + pp) * 4 + 2 * h) = v;
     }
     float4 tail0 = make_float4(0.f, 0.f, 0.f, 0.f);                     // the global bounds: the tail of category 0's rows
-    if (c0 == 0 && b0 + ((tid >> 4) & 15) < a.B) {
-        const double* g = a.global_bounds + (int64_t)(b0 + ((tid >> 4) & 15)) * 4;
-        tail0 = make_float4((float)g[0], (float)g[1], (float)g[2], (float)g[3]);
-    }
+    if (c0 == 0 && b0 + ((tid >> 4) & 15) < a.B) tail0 = qos_row_f32(a.global_bounds + (int64_t)(b0 + ((tid >> 4) & 15)) * 4);
     __syncthreads();
 
     // ---- 1. product: this wave's tiles; accumulator register r = problem 4*kq + r, column c16
@@ -213,21 +204,11 @@ __global__ __launch_bounds__(NT) void score_select_kernel(ScoreSelectArgs a) {
             else if (nk <= 8) n_found = select_row<8>(srow, q4, lb, pres, s_begin, n, sub, n_per, my_pick);
             else n_found = select_row<KPL>(srow, q4, lb, pres, s_begin, n, sub, n_per, my_pick);
         }
-        // emit n_per rows: picks repeated cyclically (loadData.py:137-141), dummy rows otherwise (:148)
-        const int src_lane = (lane & ~15) + (n_found > 0 ? sub % n_found : 0);
-        const int id = __shfl(my_pick, src_lane, 64);
-        float4 q = make_float4(0.f, 1.f, 1.f, 1.f);
-        if (n_found > 0 && sub < n_per) {
-            const double* qs = qs4 + (id - s0) * 4;                     // the same doubles select.hip reads from qos + id * 4
-            q = make_float4((float)qs[0], (float)qs[1], (float)qs[2], (float)qs[3]);
-        }
-        if (valid && sub < n_per) {
-            const int64_t pos = (int64_t)b * T * n_per + (int64_t)c * n_per + sub;
-            float4* dst = reinterpret_cast<float4*>(a.out_rows + pos * 8);
-            dst[0] = q;
-            dst[1] = c == 0 ? tail0 : make_float4(0.f, 0.f, 0.f, 0.f);
-            a.out_ids[pos] = n_found > 0 ? id : -1;
-        }
+        const int id = cyclic_pick(my_pick, n_found, lane & ~15, sub);
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n_found > 0 && sub < n_per) q = qos_row_f32(qs4 + (id - s0) * 4);          // the LDS copy of qos + id * 4
+        if (valid && sub < n_per)
+            emit_row(n_found, id, q, c, tail0, (int64_t)b * T * n_per + (int64_t)c * n_per + sub, a.out_rows, a.out_ids);
     }
 }
 

@@ -8,7 +8,25 @@
 #include <vector>
 
 #include "common.h"
-#include "select_keys.h"   // rank_key, row16_max_u64, row8_max_u64
+#include "select_keys.h"   // rank_key, feasible, pick_rounds, cyclic_pick, emit_row: the reduction's rules
+
+// A lane's best key below `last` among the feasible services s_first, s_first + stride, ... of a category: the rescan of the
+// score row and the QoS table that a round of the memory forms makes.
+__device__ __forceinline__ unsigned long long rescan_best(const float* __restrict__ srow, const double* __restrict__ qos, const CellBounds& lb,
+                                                          int s_first, int s_end, int stride, unsigned long long last) {
+    unsigned long long best = 0ull;
+    for (int s = s_first; s < s_end; s += stride) {
+        const bool feas = feasible(qos[(int64_t)s * 4 + 2], qos[(int64_t)s * 4 + 3], lb);
+        const unsigned long long key = rank_key(srow[s], (uint32_t)s);
+        if (feas && key < last && key > best) best = key;
+    }
+    return best;
+}
+
+// Problem b's global bounds for emit_row, loaded only where it writes them: at category 0.
+__device__ __forceinline__ float4 global_tail(int c, const double* __restrict__ global_bounds, int b) {
+    return c == 0 ? qos_row_f32(global_bounds + (int64_t)b * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
 
 __global__ __launch_bounds__(256) void select_candidates_kernel(
     const float* __restrict__ scores, int64_t ld_scores, const int32_t* __restrict__ cat_ptr,
@@ -21,57 +39,25 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(
     const int b = (int)(seg / T), c = (int)(seg - (int64_t)b * T);
     const int s_begin = cat_ptr[c], s_end = cat_ptr[c + 1];
     const bool pres = present[seg] != 0;
-    const double* lb = local_bounds + seg * 4;
-    const double lo_c = lb[0], hi_c = lb[1], lo_q = lb[2], hi_q = lb[3];
+    const CellBounds lb = cell_bounds(local_bounds + seg * 4);
     const float* srow = scores + (int64_t)b * ld_scores;
 
-    unsigned long long last = ~0ull;
     int my_pick = -1;   // lane r keeps the r-th pick
     int n_found = 0;
-    if (pres) {
-        for (int r = 0; r < n_per; ++r) {
-            unsigned long long best = 0ull;
-            for (int s = s_begin + lane; s < s_end; s += 64) {
-                const double cost = qos[(int64_t)s * 4 + 2], qual = qos[(int64_t)s * 4 + 3];
-                const bool feas = lo_c <= cost && cost <= hi_c && lo_q <= qual && qual <= hi_q;
-                const unsigned long long key = rank_key(srow[s], (uint32_t)s);
-                if (feas && key < last && key > best) best = key;
-            }
-            best = wave_max_u64(best);
-            if (best == 0ull) break;
-            if (lane == r) my_pick = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffu));
-            last = best;
-            ++n_found;
-        }
-    }
-    // emit n_per rows: picks repeated cyclically (loadData.py:137-141), dummy rows otherwise (:148)
-    const int src_lane = n_found > 0 ? lane % n_found : 0;
-    const int id = __shfl(my_pick, src_lane, 64);
+    if (pres)
+        n_found = pick_rounds(n_per, lane, my_pick, [&](unsigned long long last) { return rescan_best(srow, qos, lb, s_begin + lane, s_end, 64, last); },
+                              [](unsigned long long v) { return wave_max_u64(v); });
+    const int id = cyclic_pick(my_pick, n_found, 0, lane);
     if (lane < n_per) {
-        const int64_t pos = (int64_t)b * T * n_per + (int64_t)c * n_per + lane;
-        float4 q, tail = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n_found > 0) {
-            const double* qs = qos + (int64_t)id * 4;
-            q = make_float4((float)qs[0], (float)qs[1], (float)qs[2], (float)qs[3]);
-        } else {
-            q = make_float4(0.f, 1.f, 1.f, 1.f);
-        }
-        if (c == 0) {
-            const double* g = global_bounds + (int64_t)b * 4;
-            tail = make_float4((float)g[0], (float)g[1], (float)g[2], (float)g[3]);
-        }
-        float4* dst = reinterpret_cast<float4*>(out_rows + pos * 8);
-        dst[0] = q;
-        dst[1] = tail;
-        out_ids[pos] = n_found > 0 ? id : -1;
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n_found > 0) q = qos_row_f32(qos + (int64_t)id * 4);
+        emit_row(n_found, id, q, c, global_tail(c, global_bounds, b), (int64_t)b * T * n_per + (int64_t)c * n_per + lane, out_rows, out_ids);
     }
 }
 
 // The same reduction with 16 lanes per (problem, category) segment, four segments per wave, for n_per <= 16: the row-wide
 // maximum is four DPP rotations instead of six cross-wave shuffles on each key half, and a category of 5 services (the
-// 1000-task shapes) no longer occupies a whole wave.  Same keys, same order of picks, same emitted rows.
-// (row16_max_u64 / row8_max_u64: select_keys.h)
-
+// 1000-task shapes) no longer occupies a whole wave.  Same keys, same rounds, same writer (select_keys.h).
 // W = 16 or 8 lanes per segment; 8 (n_per <= 8, categories of about 8 services or fewer: the 1000-task shapes have 5) puts eight
 // segments into a wave — the kernel is bound by its vector instructions, which are per wave.
 template <int W>
@@ -80,23 +66,21 @@ __global__ __launch_bounds__(256) void select_candidates16_kernel(
     const double* __restrict__ qos, const double* __restrict__ local_bounds, const uint8_t* __restrict__ present,
     const double* __restrict__ global_bounds, float* __restrict__ out_rows, int32_t* __restrict__ out_ids,
     int32_t B, int32_t T, int32_t n_per) {
-    const int lane = threadIdx.x & 63, sub = lane & (W - 1);
+    const int lane = threadIdx.x & 63, sub = lane & (W - 1), group = lane & ~(W - 1);
     const int64_t seg = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / W) + lane / W;
     if (seg >= (int64_t)B * T) return;                                  // whole W-lane groups leave together
     const int b = (int64_t)B * T <= 0x7fffffffll ? (int)((unsigned)seg / (unsigned)T) : (int)(seg / T);   // (a 64-bit division per lane is ~100 instructions)
     const int c = (int)(seg - (int64_t)b * T);
     const int s_begin = cat_ptr[c], s_end = cat_ptr[c + 1];
     const bool pres = present[seg] != 0;
-    const double* lb = local_bounds + seg * 4;
-    const double lo_c = lb[0], hi_c = lb[1], lo_q = lb[2], hi_q = lb[3];
+    const CellBounds lb = cell_bounds(local_bounds + seg * 4);
     const float* srow = scores + (int64_t)b * ld_scores;
 
     auto group_max = [](unsigned long long v) { return W == 16 ? row16_max_u64(v) : row8_max_u64(v); };
-    unsigned long long last = ~0ull;
-    int my_pick = -1;   // lane r of the row keeps the r-th pick
+    int my_pick = -1;   // lane r of the group keeps the r-th pick
     int n_found = 0;
     const bool small = s_end - s_begin <= W;
-    float4 own = make_float4(0.f, 1.f, 1.f, 1.f);                      // this lane's service's QoS row (small categories)
+    float4 own = dummy_row();                                          // this lane's service's QoS row (small categories; a lane without one is nobody's owner)
     if (pres && small) {
         // a category of at most W services (the 1000-task shapes: 5): every lane forms its ONE key once — 0 if the service is
         // infeasible or absent — and the rounds are max-reductions over registers (no re-read of the scores and bounds per pick);
@@ -106,56 +90,23 @@ __global__ __launch_bounds__(256) void select_candidates16_kernel(
         const int s = s_begin + sub;
         if (s < s_end) {
             const double* qs = qos + (int64_t)s * 4;
-            const double q0 = qs[0], q1 = qs[1], cost = qs[2], qual = qs[3];
-            own = make_float4((float)q0, (float)q1, (float)cost, (float)qual);
-            if (lo_c <= cost && cost <= hi_c && lo_q <= qual && qual <= hi_q) key = rank_key(srow[s], (uint32_t)s);
+            own = qos_row_f32(qs);
+            if (feasible(qs[2], qs[3], lb)) key = rank_key(srow[s], (uint32_t)s);
         }
-        for (int r = 0; r < n_per; ++r) {
-            const unsigned long long best = group_max(key < last ? key : 0ull);
-            if (best == 0ull) break;
-            if (sub == r) my_pick = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffu));
-            last = best;
-            ++n_found;
-        }
+        n_found = pick_rounds(n_per, sub, my_pick, [&](unsigned long long last) { return key < last ? key : 0ull; }, group_max);
     } else if (pres) {
-        for (int r = 0; r < n_per; ++r) {
-            unsigned long long best = 0ull;
-            for (int s = s_begin + sub; s < s_end; s += W) {
-                const double cost = qos[(int64_t)s * 4 + 2], qual = qos[(int64_t)s * 4 + 3];
-                const bool feas = lo_c <= cost && cost <= hi_c && lo_q <= qual && qual <= hi_q;
-                const unsigned long long key = rank_key(srow[s], (uint32_t)s);
-                if (feas && key < last && key > best) best = key;
-            }
-            best = group_max(best);
-            if (best == 0ull) break;
-            if (sub == r) my_pick = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffu));
-            last = best;
-            ++n_found;
-        }
+        n_found = pick_rounds(n_per, sub, my_pick, [&](unsigned long long last) { return rescan_best(srow, qos, lb, s_begin + sub, s_end, W, last); }, group_max);
     }
-    // emit n_per rows: picks repeated cyclically (loadData.py:137-141), dummy rows otherwise (:148)
-    const int src_lane = (lane & ~(W - 1)) + (n_found > 0 ? sub % n_found : 0);
-    const int id = __shfl(my_pick, src_lane, 64);
-    float4 q = make_float4(0.f, 1.f, 1.f, 1.f);
+    const int id = cyclic_pick(my_pick, n_found, group, sub);
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
     if (small) {                                                       // (the whole group of W lanes takes this branch together)
-        const int owner = n_found > 0 ? (lane & ~(W - 1)) + (id - s_begin) : lane;
-        const float4 g = make_float4(__shfl(own.x, owner, 64), __shfl(own.y, owner, 64), __shfl(own.z, owner, 64), __shfl(own.w, owner, 64));
-        if (n_found > 0) q = g;
+        const int owner = n_found > 0 ? group + (id - s_begin) : lane;
+        q = make_float4(__shfl(own.x, owner, 64), __shfl(own.y, owner, 64), __shfl(own.z, owner, 64), __shfl(own.w, owner, 64));
     } else if (n_found > 0 && sub < n_per) {
-        const double* qs = qos + (int64_t)id * 4;
-        q = make_float4((float)qs[0], (float)qs[1], (float)qs[2], (float)qs[3]);
+        q = qos_row_f32(qos + (int64_t)id * 4);
     }
     if (sub < n_per) {
-        const int64_t pos = (int64_t)b * T * n_per + (int64_t)c * n_per + sub;
-        float4 tail = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c == 0) {
-            const double* g = global_bounds + (int64_t)b * 4;
-            tail = make_float4((float)g[0], (float)g[1], (float)g[2], (float)g[3]);
-        }
-        float4* dst = reinterpret_cast<float4*>(out_rows + pos * 8);
-        dst[0] = q;
-        dst[1] = tail;
-        out_ids[pos] = n_found > 0 ? id : -1;
+        emit_row(n_found, id, q, c, global_tail(c, global_bounds, b), (int64_t)b * T * n_per + (int64_t)c * n_per + sub, out_rows, out_ids);
     }
 }
 
@@ -169,20 +120,14 @@ extern "C" int gnnpn_select_candidates(const float* scores, int64_t ld_scores, c
                   "select_candidates: null operand");
     GNNPN_REQUIRE(n_per >= 1 && n_per <= 64, "select_candidates: n_per must be in [1,64], got %d", n_per);
     GNNPN_REQUIRE(gnnpn_aligned(out_rows, 16), "select_candidates: out_rows must be 16-byte aligned");
-    if (B == 0) return GNNPN_OK;
     const int64_t n_seg = (int64_t)B * T;
-    if (n_per <= 8 && ld_scores <= 8ll * T)                            // (ld_scores >= the number of services: mean category <= 8)
-        hipLaunchKernelGGL(select_candidates16_kernel<8>, dim3((unsigned)((n_seg + 31) / 32)), dim3(256), 0,
-                           (hipStream_t)stream, scores, ld_scores, cat_ptr, qos, local_bounds, present, global_bounds,
-                           out_rows, out_ids, B, T, n_per);
-    else if (n_per <= 16)
-        hipLaunchKernelGGL(select_candidates16_kernel<16>, dim3((unsigned)((n_seg + 15) / 16)), dim3(256), 0,
-                           (hipStream_t)stream, scores, ld_scores, cat_ptr, qos, local_bounds, present, global_bounds,
-                           out_rows, out_ids, B, T, n_per);
-    else
-        hipLaunchKernelGGL(select_candidates_kernel, dim3((unsigned)((n_seg + 3) / 4)), dim3(256), 0,
-                           (hipStream_t)stream, scores, ld_scores, cat_ptr, qos, local_bounds, present, global_bounds,
-                           out_rows, out_ids, B, T, n_per);
+    auto launch = [&](auto kernel, int segs_per_workgroup) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n_seg + segs_per_workgroup - 1) / segs_per_workgroup)), dim3(256), 0, (hipStream_t)stream,
+                           scores, ld_scores, cat_ptr, qos, local_bounds, present, global_bounds, out_rows, out_ids, B, T, n_per);
+    };
+    if (n_per <= 8 && ld_scores <= 8ll * T) launch(select_candidates16_kernel<8>, 32);      // (ld_scores >= the number of services: mean category <= 8)
+    else if (n_per <= 16) launch(select_candidates16_kernel<16>, 16);
+    else launch(select_candidates_kernel, 4);
     GNNPN_CHECK_LAUNCH("select_candidates");
     return GNNPN_OK;
 }
@@ -218,7 +163,7 @@ __global__ __launch_bounds__(1024) void rank_rows_kernel(const float* __restrict
     __syncthreads();
     bitonic_sort_desc(keys, P, [](unsigned long long a, unsigned long long b) { return a < b; });
     int32_t* out = ranking + (int64_t)blockIdx.x * S;
-    for (int i = threadIdx.x; i < S; i += blockDim.x) out[i] = (int32_t)(0xffffffffu - (uint32_t)(keys[i] & 0xffffffffu));
+    for (int i = threadIdx.x; i < S; i += blockDim.x) out[i] = key_id(keys[i]);
 }
 
 // Rows of 16385..32768 services (BASELINE configs[4]: S = 20000): the 64-bit keys no longer fit the LDS, so the

@@ -29,7 +29,7 @@ class DeviceServices:
     cat_ptr: torch.Tensor        # i32 [T+1]
     qos: torch.Tensor            # f64 [S,4]
     emb_cache: tuple = None      # (prepared-weights object, [S,hidden] service embedding): see ML2PNPipeline.service_embedding
-    score_cache: dict = None     # the fused score + select kernel's operands for emb_cache's embedding: see ML2PNPipeline.score_select_operands
+    score_cache: score_plan.OperandCache = None   # the fused score + select kernel's operands for emb_cache's embedding: see ML2PNPipeline.score_select_operands
 
     @staticmethod
     def from_table(table, device):
@@ -420,29 +420,17 @@ class ML2PNPipeline:
         depends on the table only and is kept per chunk count — about one workgroup per CU for this batch's tiles of 16 problems."""
         if score_plan.unfused_front() or not self.cache_service_embedding:
             return None
-        hidden = self.net.nodeLin.weight.shape[0]
         c = services.score_cache
         if c is None:
-            cat = services.cat_ptr.cpu().numpy()
-            c = services.score_cache = {"cat_ptr": cat, "applies": {}, "plans": {}, "emb": None, "packed": None}
-        key = (int(hidden), int(self.n_per))
-        if key not in c["applies"]:
-            c["applies"][key] = score_plan.applies(c["cat_ptr"], *key)
-        if not c["applies"][key]:
+            c = services.score_cache = score_plan.OperandCache(services.cat_ptr.cpu().numpy(), services.qos.device)
+        if not c.applies(self.net.nodeLin.weight.shape[0], self.n_per):
             return None
-        dev = services.qos.device
-        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-        n_chunks = min(len(c["cat_ptr"]) - 1, max(1, n_cu // max(1, (batch.n_problems + 15) // 16)))
-        if n_chunks not in c["plans"]:
-            plan = score_plan.plan_chunks(c["cat_ptr"], n_chunks)
-            c["plans"][n_chunks] = None if plan is None else (plan, *plan.tensors(dev))
-        if c["plans"][n_chunks] is None:
+        n_cu = torch.cuda.get_device_properties(c.device).multi_processor_count
+        planned = c.plan(score_plan.chunk_count(c.n_categories, batch.n_problems, n_cu))
+        if planned is None:
             return None
-        plan, plan_host, plan_dev = c["plans"][n_chunks]
-        emb = self.service_embedding(services)
-        if c["emb"] is not emb:
-            c["emb"], c["packed"] = emb, score_plan.pack_embedding(emb, plan)      # (the tile layout is the same in every plan)
-        return c["packed"], plan_host, plan_dev
+        plan, plan_host, plan_dev = planned
+        return c.packed(self.service_embedding(services), plan), plan_host, plan_dev
 
     @torch.no_grad()
     def front(self, services, batch):

@@ -1,6 +1,6 @@
 """Host side of the fused score product + candidate reduction (csrc/score_select.hip, gnnpn_score_select_f32): where it applies,
 the chunk plan of a service table and the B-fragment-packed service embedding.  All three depend on the service table (and the
-weights) only, so pipeline.py builds them once per ``DeviceServices`` and keeps them beside the service embedding.
+weights) only, so pipeline.py builds them once per ``DeviceServices`` and keeps them beside the service embedding (``OperandCache``).
 
 The kernel's grid is (tiles of 16 problems) x (chunks of whole categories); a chunk is a contiguous run of categories, and the
 chunks are balanced by service count.  Numpy only up to ``pack_embedding`` / ``ScorePlan.to``: the planner runs without a GPU.
@@ -95,6 +95,12 @@ def plan_chunks(cat_ptr, n_chunks):
         n = T if n > T else min(T, n + max(1, n // 4))
 
 
+def chunk_count(n_categories, n_problems, n_cu):
+    """The chunks to ask ``plan_chunks`` for: about one workgroup per CU over the batch's tiles of 16 problems — at least one, and
+    no more than there are categories."""
+    return min(int(n_categories), max(1, int(n_cu) // max(1, (int(n_problems) + 15) // 16)))
+
+
 def pack_embedding(emb, plan):
     """[S, 128] service embedding -> v_mfma_f32_16x16x4_f32 B-fragments [n_tiles, 8, 64, 4], every category its own run of
     16-column tiles: packed[t][kb][lane][j] = emb[first service of tile t + lane % 16][16 kb + 4 j + lane // 16], 0 behind the
@@ -112,3 +118,31 @@ def pack_embedding(emb, plan):
     padded = torch.cat([emb, torch.zeros((1, K), dtype=emb.dtype, device=emb.device)])
     v = padded[torch.from_numpy(rows.reshape(-1)).to(emb.device)].view(plan.n_tiles, 16, K // 16, 4, 4)   # [t, c, kb, j, kq]
     return v.permute(0, 2, 4, 1, 3).reshape(plan.n_tiles, K // 16, 64, 4).contiguous()                    # [t, kb, (kq, c), j]
+
+
+class OperandCache:
+    """The kernel's operands for one service table, kept beside it (``DeviceServices.score_cache``): whether the kernel applies per
+    (hidden, n_per), the plan and its two tensors per chunk count, and the packed embedding, which follows the embedding object it
+    was packed from (one per (weights, table))."""
+
+    def __init__(self, cat_ptr, device):
+        self.cat_ptr, self.device, self.n_categories = cat_ptr, device, len(cat_ptr) - 1
+        self._applies, self._plans, self._emb, self._packed = {}, {}, None, None
+
+    def applies(self, hidden, n_per):
+        key = (int(hidden), int(n_per))
+        if key not in self._applies:
+            self._applies[key] = applies(self.cat_ptr, *key)
+        return self._applies[key]
+
+    def plan(self, n_chunks):
+        """(ScorePlan, plan_host, plan) for about ``n_chunks`` chunks, or None where no plan fits."""
+        if n_chunks not in self._plans:
+            plan = plan_chunks(self.cat_ptr, n_chunks)
+            self._plans[n_chunks] = None if plan is None else (plan, *plan.tensors(self.device))
+        return self._plans[n_chunks]
+
+    def packed(self, emb, plan):
+        if self._emb is not emb:
+            self._emb, self._packed = emb, pack_embedding(emb, plan)                 # (the tile layout is the same in every plan)
+        return self._packed

@@ -28,7 +28,8 @@ Every reinterpret_cast to a 16-byte vector type on a CALLER's pointer in csrc/, 
   gin_layer_split.hip:184       out                                  ldo % 4 and gnnpn_aligned(out, 16) at :447:
                                                                       test_gin_layer_split_refusals
   gin_layer_split.hip:404,405,410   the packer's image               gnnpn_aligned(packed, 16) at :425
-  select.hip:68,177       out_rows                                   GNNPN_REQUIRE at select.hip:193: test_select_candidates_refusal
+  select_keys.h:76        emit_row (every select build), out_rows    GNNPN_REQUIRE at select.hip:122 (score_select.hip:255 for the
+                                                                      fused launch): test_select_candidates_refusal
   decode.hip:295,296      attention_logits, enc_out / queries        H % 4, ld_q % 4 at decode.hip:337 and gnnpn_aligned at :341:
                                                                       test_attention_logits_refusals
   decode.hip:390          qos_reward_kernel, actions                 NO host check.  A plain 16-byte global load into registers (no

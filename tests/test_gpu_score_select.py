@@ -10,6 +10,9 @@ service-embedding rows (bit-equal scores whatever the product does), and from ro
 that the sigmoid gives +0.0 for different services; the reference's own rule (lowest id) decides both.  A -0.0 score cannot be
 produced: both paths form the scores themselves and 1 / (1 + exp(-v)) is never negative — the zero canonicalisation of
 rank_key is the same function in both kernels (csrc/select_keys.h) and is tested on given scores in test_gpu_abi_layout.py.
+
+A second, small table (categories of 65, 100, 128 and 3 services) runs the size class of 8 keys per lane, which the first table's
+categories skip, and is held to the rule written out on the CPU as well: both launches now share the rule's code (select_keys.h).
 """
 import numpy as np
 import pytest
@@ -163,3 +166,121 @@ def test_shape_outside_the_fused_conditions_takes_the_two_launches(dev):
     want = pipe.scores(svc, batch)
     want_rows, want_ids = pipe.candidates(svc, batch, want)
     assert scores.shape == (Bp, S) and torch.equal(scores, want) and torch.equal(rows, want_rows) and torch.equal(ids, want_ids)
+
+
+# ---- a second, small table: categories of 65, 100 and 128 services hold 5, 7 and 8 keys per lane, the size class of 8 that the
+# table above (1, 1, 1, 2, 4, 4 and 16 keys) never reaches; 21 tiles and 4 categories, so ONE chunk holds them all
+SIZES8 = (65, 100, 128, 3)
+B8, N_PER8 = 3, (1, 16)
+# (lower, upper) service ids with the same embedding row; in-category positions (10, 64), (5, 70), (80, 99), (63, 127), (64, 100):
+# the upper one always in a key slot j >= 4, the lower one of three pairs below position 64.  The first pair scores highest in
+# category 0 and service 165 + 90 (unduplicated, position 90) highest in category 2: what n_per = 1 picks in the open cells
+DUPLICATES8 = ((10, 64), (70, 135), (145, 164), (228, 292), (229, 265))
+TOP8 = 165 + 90
+# per (problem, category): "open", a cost window of that many services, 0 = an empty window, None = the category is absent
+CELLS8 = (("open", 9, 0, "open"), (15, "open", 1, None), (0, 4, "open", 2))
+
+
+def _inputs8():
+    g = torch.Generator().manual_seed(11)
+    cat = np.concatenate([[0], np.cumsum(SIZES8)]).astype(np.int32)
+    S, T = int(cat[-1]), len(SIZES8)
+    xr = torch.randn(B8, K, generator=g)
+    xr[:, 0] = 8.0
+    emb = torch.randn(S, K, generator=g) * 0.1
+    emb[DUPLICATES8[0][0], 0] = 1.0                        # + 8 in the product: above everything else of its category
+    emb[TOP8, 0] = 1.0
+    for src, dst in DUPLICATES8:
+        emb[dst] = emb[src]
+    qos = torch.rand(S, 4, generator=g, dtype=torch.float64)
+    lb = torch.empty(B8, T, 4, dtype=torch.float64)
+    present = torch.ones(B8, T, dtype=torch.uint8)
+    for b in range(B8):
+        for c in range(T):
+            cell = CELLS8[b][c]
+            cost = qos[int(cat[c]):int(cat[c + 1]), 2].sort().values
+            if cell == "open" or cell is None:
+                lb[b, c] = torch.tensor([0.0, 1.0, 0.0, 1.0])
+                present[b, c] = 0 if cell is None else 1
+            elif cell == 0:
+                lb[b, c] = torch.tensor([0.7, 0.3, 0.0, 1.0])
+            else:                                          # exactly `cell` services inside: the costs are distinct doubles
+                first = (b + c) % (len(cost) - cell + 1)
+                lb[b, c] = torch.tensor([float(cost[first]), float(cost[first + cell - 1]), 0.0, 1.0], dtype=torch.float64)
+    gb = torch.rand(B8, 4, generator=g, dtype=torch.float64)
+    return {"cat": cat, "xr": xr, "emb": emb, "qos": qos, "lb": lb, "present": present, "gb": gb, "S": S, "T": T}
+
+
+def _cpu_picks(scores, h, n_per):
+    """The rule itself, from given scores: per cell the feasible services by (score descending, -0 = +0; id ascending), the first
+    n_per repeated cyclically, -1 and the dummy row where there is none; the global bounds behind category 0's rows.  Returns
+    rows [B, T * n_per, 8], ids [B, T * n_per], the number of feasible services [B, T] and the distinct picks per cell."""
+    cat, qos, lb, present, gb = h["cat"], h["qos"].numpy(), h["lb"].numpy(), h["present"].numpy(), h["gb"].numpy()
+    nb, T = present.shape
+    rows = np.zeros((nb, T, n_per, 8), np.float32)
+    ids = np.full((nb, T, n_per), -1, np.int32)
+    n_feasible = np.zeros((nb, T), np.int64)
+    picked = {}
+    for b in range(nb):
+        for c in range(T):
+            s = np.arange(cat[c], cat[c + 1])
+            lo_c, hi_c, lo_q, hi_q = lb[b, c]
+            ok = (present[b, c] != 0) & (lo_c <= qos[s, 2]) & (qos[s, 2] <= hi_c) & (lo_q <= qos[s, 3]) & (qos[s, 3] <= hi_q)
+            f = s[ok]
+            order = f[np.lexsort((f, -(scores[b, f] + np.float32(0.0))))]
+            n_feasible[b, c], picked[b, c] = len(f), order[:n_per]
+            rows[b, c, :, :4] = (0.0, 1.0, 1.0, 1.0)
+            if len(order):
+                ids[b, c] = order[:n_per][np.arange(n_per) % min(n_per, len(order))]
+                rows[b, c, :, :4] = qos[ids[b, c]].astype(np.float32)
+            if c == 0:
+                rows[b, c, :, 4:] = gb[b].astype(np.float32)
+    return rows.reshape(nb, T * n_per, 8), ids.reshape(nb, T * n_per), n_feasible, picked
+
+
+@pytest.fixture(scope="module")
+def case8(dev):
+    from gnnpn_sc_amd import custom_ops, ops   # noqa: F401
+    h = _inputs8()
+    d = {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v).to(dev) for k, v in h.items() if k not in ("S", "T")}
+    scores = torch.ops.gnnpn.linear(d["xr"], d["emb"], act=ops.ACT_SIGMOID)
+    ref = {n: (scores, *torch.ops.gnnpn.segment_topk_feasible(scores, d["cat"], d["qos"], d["lb"], d["present"], d["gb"], n)) for n in N_PER8}
+    torch.cuda.synchronize()
+    return h, d, ref
+
+
+@pytest.mark.parametrize("n_chunks", [1, 4])
+@pytest.mark.parametrize("n_per", N_PER8)
+def test_categories_of_five_to_eight_keys_per_lane(case8, n_per, n_chunks):
+    """Categories of 65, 100 and 128 services (and one of 3) in one chunk and in one chunk each, B = 3 (one ragged tile of problems):
+    the same bits as the two launches, and the same picks and rows as the rule written out on the CPU from the returned scores.
+    Before either comparison the CPU side shows that the case holds what it is for: a cell without a feasible service, one with
+    fewer than 16, a pick at an in-category position >= 64 and a tie decided between positions on both sides of 64."""
+    from gnnpn_sc_amd import score_plan
+    h, d, ref = case8
+    assert [(n + 15) // 16 for n in SIZES8] == [5, 7, 8, 1]
+    plan = score_plan.plan_chunks(h["cat"], n_chunks)
+    assert plan is not None and plan.n_chunks == n_chunks and plan.fits() and score_plan.applies(h["cat"], K, n_per)
+    packed = score_plan.pack_embedding(d["emb"], plan)
+    plan_host, plan_dev = plan.tensors(d["emb"].device)
+    scores, rows, ids = torch.ops.gnnpn.score_select(d["xr"], packed, plan_host, plan_dev, d["qos"], d["lb"], d["present"], d["gb"], n_per)
+
+    want_rows, want_ids, n_feasible, picked = _cpu_picks(scores.cpu().numpy(), h, n_per)
+    cat = h["cat"]
+    for b in range(B8):
+        for c in range(h["T"]):
+            cell = CELLS8[b][c]
+            assert n_feasible[b, c] == (SIZES8[c] if cell == "open" else 0 if cell is None else cell)
+    assert int((n_feasible[h["present"].numpy() != 0] == 0).sum()) > 0 and int(((n_feasible > 0) & (n_feasible < 16)).sum()) > 0
+    assert any(int(s) - int(cat[c]) >= 64 for (b, c), p in picked.items() for s in p)
+    sc = scores.cpu().numpy()
+    decided = [(b, lo, hi) for (b, c), p in picked.items() for lo, hi in DUPLICATES8
+               if lo in p and lo - cat[c] < 64 <= hi - cat[c] < SIZES8[c] and n_feasible[b, c] == SIZES8[c] and sc[b, lo] == sc[b, hi]]
+    assert decided                                         # both feasible (an open cell), equal scores, the lower id among the picks
+
+    want = ref[n_per]
+    assert torch.equal(scores, want[0])
+    assert torch.equal(ids, want[2])
+    assert torch.equal(rows, want[1])
+    assert np.array_equal(ids.cpu().numpy(), want_ids)
+    assert np.array_equal(rows.cpu().numpy(), want_rows)

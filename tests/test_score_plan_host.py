@@ -1,5 +1,5 @@
 """-m "not gpu": the chunk planner of the fused score product + candidate reduction (gnnpn-sc_amd/score_plan.py): every category
-in exactly one chunk, chunks contiguous, balance within one category's size; where the kernel applies; and the entry point's
+in exactly one chunk, chunks contiguous, balance within one category's size; where the kernel applies; the chunk count asked of the planner; and the entry point's
 refusals, which return before any launch."""
 import ctypes
 
@@ -57,6 +57,24 @@ def test_where_the_fused_kernel_applies():
     assert not score_plan.applies(np.arange(0, 20001, 10), 128, 5)                   # the 2000-task shape: 10
     assert not score_plan.applies(np.array([0, 257, 600]), 128, 5)                   # above the cap
     assert score_plan.applies(np.array([0, 256, 300]), 128, 5)
+
+
+def test_chunk_count_rule():
+    """About one workgroup per CU over the tiles of 16 problems: n_cu // ceil(B / 16), at least 1, at most one chunk per category."""
+    assert score_plan.chunk_count(47, 256, 256) == 16                                # 16 tiles of problems on 256 CUs
+    assert score_plan.chunk_count(47, 257, 256) == 15 and score_plan.chunk_count(47, 272, 256) == 15      # a ragged 17th tile counts
+    assert score_plan.chunk_count(47, 16, 256) == 47 and score_plan.chunk_count(47, 1, 256) == 47         # capped by the categories
+    assert score_plan.chunk_count(300, 16, 256) == 256 and score_plan.chunk_count(300, 17, 256) == 128
+    assert score_plan.chunk_count(47, 16 * 256, 256) == 1 and score_plan.chunk_count(47, 100000, 256) == 1    # never below one
+    assert score_plan.chunk_count(47, 0, 256) == 47 and score_plan.chunk_count(1, 256, 256) == 1          # an empty batch; one category
+    for T in (1, 7, 47, 300):
+        for B in (0, 1, 15, 16, 17, 255, 256, 4096, 5000):
+            for n_cu in (1, 64, 256, 304):
+                n = score_plan.chunk_count(T, B, n_cu)
+                tiles = max(1, -(-B // 16))
+                assert 1 <= n <= T and isinstance(n, int)
+                assert n == T or n * tiles <= max(n_cu, tiles)                       # below the cap: the grid stays within the CUs
+                assert n == T or (n + 1) * tiles > n_cu                              # ... and one more chunk would leave them
 
 
 def test_unfused_switch(monkeypatch):
