@@ -612,12 +612,159 @@ def _has_collective_stream():
         return True
 
 
+def _hw_queues(env=None):
+    """The number of in-order hardware queues the HIP runtime deals this process's streams onto (unset or empty: its default, 4)."""
+    return int((os.environ if env is None else env).get("GPU_MAX_HW_QUEUES", "4") or 4)
+
+
+def _separate_priority(n_streams, collective_stream, env=None):
+    """The priority PipelinedRunner's slot streams get where nobody names one: -1, a priority of their own, for free-running slots
+    in a rank of an RCCL process group that has fewer than 8 hardware queues, else 0 (runner_plan says why)."""
+    return -1 if n_streams > 1 and collective_stream and _hw_queues(env) < 8 else 0
+
+
+def _pinned_host(arena):
+    """Whether a packed batch's arena is pinned host memory (``PipelinedRunner.pack_host``): one asynchronous host-to-device copy."""
+    return arena.device.type == "cpu" and arena.is_pinned()
+
+
+@dataclass(frozen=True)
+class RunnerPlan:
+    """The mode of a PipelinedRunner: every decision ``runner_plan`` makes, under the names of the runner's attributes."""
+    n_slots: int                 # static input / output sets = the reuse distance of submit()'s outputs
+    halves: bool                 # ONE batch in flight, its recurrent part as two half-batches side by side
+    n_streams: int               # steps in flight (1 or 2)
+    n_workspaces: int
+    stream_priority: int
+    priority_chosen: bool        # neither the argument nor GNNPN_PIPE_STREAM_PRIORITY named the priority: runner_plan chose it
+    decode_impl: int
+    lds_kb: tuple                # LDS footprint of the cooperative launches, per slot
+    front_lds_kb: int            # ... and of the ordinary LDS-using kernels in front of them
+    lockstep: bool               # the two slots' replays start in pairs
+    common_start_us: float       # > 0: the first replays of a burst are held behind a gate, at most this long
+    write_through: bool
+
+
+def runner_plan(n_problems, slots, precision, seq_len, *, halves=None, stream_priority=None, write_through=None, env=os.environ,
+                collective_stream=False):
+    """The mode of a PipelinedRunner over batches of ``n_problems`` with ``slots`` slots, for a pipeline of ``precision`` whose
+    recurrences run ``seq_len`` steps per problem (T * K): a pure function of its arguments and ``env``.  ``halves``,
+    ``stream_priority``, ``write_through``: the constructor's arguments (None: decided here); ``collective_stream``: this process
+    is a rank of an RCCL process group (``_has_collective_stream``).  The environment variables it reads, each with its default:
+
+        GNNPN_PIPE_HALVES            "0": never pair half-batches (default: pair them from 512 problems on, with more than one slot)
+        GNNPN_PIPE_STREAM_PRIORITY   the slot streams' priority (default: -1 for free-running slots beside a collective stream with
+                                     fewer than 8 hardware queues — ``_hw_queues`` —, else 0); the argument wins
+        GNNPN_PIPE_DECODE_IMPL       the decoder build (default: 4 where two cooperative launches share every CU, else 0 = auto)
+        GNNPN_SLOT_LDS_KB            the cooperative launches' LDS footprint in KB, one entry per slot, comma-separated (default: 78
+                                     each with the exact split where launches share CUs, else 0 = the kernel's own)
+        GNNPN_PIPE_FRONT_LDS_KB      the footprint of the ordinary kernels in front of them (default: the same 78 for two
+                                     free-running slots, else 0)
+        GNNPN_PIPE_LOCKSTEP          "1" / "0": two slots start their replays in pairs (default: from 2000 recurrent steps on)
+        GNNPN_PIPE_COMMON_START_US   the longest hold of a burst's first replays behind the common-start gate (default:
+                                     COMMON_START_US = 0, no gate); two free-running slots without lockstep only
+
+    (GNNPN_PIPE_WRITE_THROUGH and GNNPN_HOST_COPY_INLINE are read once, when this module is imported: DEFAULT_WRITE_THROUGH and
+    HOST_COPY_ON_ITS_OWN_STREAM above.)  A GNNPN_SLOT_LDS_KB list shorter than the slots raises GnnpnError."""
+    # Batches of 512 problems and more: ONE batch in flight, its recurrent part as two half-batches side by side
+    # (ML2PNPipeline.run with a pair of workspaces).  A cooperative launch has one workgroup per CU and two of them
+    # fill a CU's registers, so nothing else runs beside a co-resident pair; with two WHOLE batches in flight on two
+    # slots the pairing is left to chance — one slot's front half waits for the other's 25 ms encoder, encoders meet
+    # decoders — and the 1000-task shape ran 28.3 ms per batch where its recurrent kernels, always paired, need 21.1
+    # (tools/bench_slot_parts.py).  Below 512 problems a half-batch launch no longer fills the chip: two slots.
+    halves = bool(halves) if halves is not None else (n_problems >= 512 and int(slots) > 1 and env.get("GNNPN_PIPE_HALVES", "1") != "0")
+    # ``n_slots`` = the number of static input / output sets = the reuse distance of submit()'s outputs, in EVERY mode
+    # (ADVICE r3: the half-batch mode used to collapse to one slot, and a caller following the documented rule read
+    # outputs the next replay was already overwriting).  ``n_streams`` = steps in flight: the half-batch mode keeps ONE
+    # step in flight, so its slots' graphs replay one after the other on one stream.
+    n_slots = max(1, int(slots))
+    # ... and never more than TWO: a CU holds two cooperative workgroups, so two replays in flight are what the chip has room for —
+    # a third free-running stream put three launches in front of those two slots and ended in half-staffed launches and
+    # bounded-wait time-outs (round 6, tools/probes/dbg_three_slots.py: slots=3 ran 24 k problems/s with status 0x13).  More slots
+    # than two are more static input / output sets (a longer reuse distance), dealt onto the two streams in turn.
+    n_streams = 1 if halves else min(n_slots, 2)
+    # Stream priority of the slots: HIP deals a process's streams onto a few in-order hardware queues (_hw_queues,
+    # default 4) round robin, PER PRIORITY.  In a rank of an RCCL process group the collective's stream waits for one slot's
+    # step; when that wait shares a hardware queue with the other slot's stream it sits in front of that slot's launches
+    # (forced world-1 all-gather at the QWS shape: 449 k problems/s against 480 k without a process group).  Slot streams of a
+    # priority of their own never share a queue with the process group's (normal-priority) stream: 470 k, the same as 8
+    # hardware queues give (467 k) but without an environment variable that has to be set before the runtime starts — and
+    # the two do NOT add up (8 queues AND high priority: 367-378 k).  Without a process group high priority costs 0.35 %
+    # (477.8-478.2 k against 479.5-479.7 k), so it is used only where a collective stream exists.  profiles/LOG_r06.md §9.
+    # (a process started with 8 or more hardware queues has the separation already — and must not get both)
+    # Only for free-running slots on streams of their own: the half-batch mode keeps ONE step in flight on one stream (nothing of
+    # another slot for the collective's wait to sit in front of), and there high priority COSTS — Normal shape, forced RCCL:
+    # 199 k problems/s against 234-238 k at normal priority (238 k without a process group); 1000-task shape 22.8 k against 23.8 k
+    # (tools/r06/dist_priority_shapes.sh)
+    named = env.get("GNNPN_PIPE_STREAM_PRIORITY")
+    priority_chosen = stream_priority is None and named is None
+    if stream_priority is None:
+        stream_priority = int(named) if named is not None else _separate_priority(n_streams, collective_stream, env)
+    # decoder form beside another slot's kernels: the 8-member build sized for two workgroups per CU (decode_impl 4).  Measured at QWS B=256 against the 16-member form (3):
+    # 228 k vs 221 k problems/s in fp32, 353 k vs 316 k with the split precision.
+    shared = 4
+    paired = n_streams > 1 or halves    # two cooperative launches share every CU
+    decode_impl = int(env.get("GNNPN_PIPE_DECODE_IMPL", shared if paired else 0))
+    # Placement: the cooperative kernels claim one CU per workgroup at run time (csrc/coop_common.h, coop_place), so
+    # the two slots' launches share every CU one workgroup each whatever the dispatcher does; the LDS-footprint
+    # padding round 1 steered the dispatcher with (100 / 56 KB) is no longer needed and stays as an option only.
+    # Exact-split precision: the recurrent kernels hold the third weight piece in LDS (60 KB encoder, 69 KB decoder).  Two
+    # such workgroups fit a CU's 160 KB, but LDS is allocated in CONTIGUOUS ranges: with unequal footprints a freed 60 KB
+    # hole does not take the next 69 KB workgroup while the neighbour's range sits in the middle, the launch stays
+    # under-staffed, and two launches can starve each other until the bounded spins give up (seen: bench.py, precision
+    # split, two slots: members missing at the first sweep, 20 of 32 seats of an XCD staffed after 0.3 s).  Every
+    # cooperative launch of a multi-slot runner is therefore padded to ONE footprint, 78 KB: any freed range fits any
+    # waiting workgroup.  (f32: 19 / 27 KB — nothing to equalise.)
+    named = env.get("GNNPN_SLOT_LDS_KB")
+    equal = 78 if (precision == "split" and paired) else 0
+    lds_kb = tuple(int(v) for v in named.split(",")) if named else (equal,) * n_slots
+    if len(lds_kb) < n_slots:            # (used to end in an IndexError in the middle of the captures)
+        raise ops.GnnpnError(f"GNNPN_SLOT_LDS_KB={named!r} has {len(lds_kb)} entries for {n_slots} slots: one footprint per slot")
+    # ... and so are the ORDINARY kernels of a step that use LDS in front of the encoder (the one-launch GIN branch, the score
+    # product: ops.lds_footprint / gnnpn_lds_footprint_kb).  A cooperative workgroup that lands above such a kernel's few KB
+    # keeps its 78 KB in the middle of the CU when the small kernel has gone, and the OTHER slot's encoder workgroup for that
+    # CU finds no contiguous 78 KB until this encoder has finished: the two free-running slots slipped apart by 0.5 ms in
+    # every 20-step round (round 4 held the slots of a burst behind a common-start gate against it: 455 k problems/s with 4-8
+    # slow rounds of 89; with the front half at the same footprint 460 k and no slow round in 270, gate off —
+    # profiles/r05_slip_front_lds.jsonl).  Two free-running slots only: the half-batch mode runs its front half alone.
+    named = env.get("GNNPN_PIPE_FRONT_LDS_KB")
+    front_lds_kb = int(named) if named is not None else (equal if (n_streams == 2 and not halves) else 0)
+    # Two slots, long recurrent kernels: start the two replays of a pair TOGETHER (a submission joins the leader that is
+    # still waiting for a partner, else it leads).  Free-running slots drift apart by the difference of their step
+    # times, and a cooperative launch that starts under the OTHER slot's front half finds every CU's LDS occupied by
+    # short-lived neighbours: its workgroups land above them (coop_place gives such seats back, up to a few hundred times
+    # per launch), seats are taken off their canonical CUs, and from there on both slots' launches run at the speed of
+    # one — the 2000-task shape alternated between 41 and 62 ms per step (spread 37-48 % over rounds; tools/slot_overlap.py).
+    # Started together, the two front halves run side by side and are gone when the encoders arrive.  The wait costs the
+    # tail by which the two replays differ (2 % at that shape); short steps (QWS, Normal) keep running free.
+    named = env.get("GNNPN_PIPE_LOCKSTEP")
+    long_steps = int(seq_len) >= 2000          # recurrent steps per problem (T * K)
+    lockstep = n_slots == 2 and n_streams == 2 and (named == "1" or (named is None and long_steps))
+    # Common start of a burst (two free-running slots only).  Two slots that begin a burst a host enqueue apart (~0.1 ms:
+    # the second replay is not in its queue yet when the first starts) run in step for a few steps and then slip apart ONCE
+    # — one slot's step takes 1.7 instead of 1.2 ms at the QWS shape — which costs a 20-step burst 0.5 ms (4 %); slots
+    # released TOGETHER stay in step (tools/probes/stagger_probe.py: 11.50 against 12.01 ms per 20 steps, the hold included;
+    # 30 and 60 us are too short, 90 and more work).  So the first replay after the runner has been idle is held behind a
+    # gate on another stream, and so is the other slot's first one; later replays are not.  The gate (gnnpn_gate_wait: one
+    # wavefront polling a word in pinned host memory) is opened by the HOST the moment the second replay is in its queue —
+    # or by synchronize / poll, or after COMMON_START_US at the latest (a burst of one replay that is waited for some other way).
+    # "Idle" = since the last synchronize() / poll() of this runner: a caller that works in bursts waits for them that way.
+    common_start_us = float(env.get("GNNPN_PIPE_COMMON_START_US", COMMON_START_US)) \
+        if (n_slots == 2 and n_streams == 2 and not lockstep) else 0.0
+    # write_through: the placement-independent hand-off form (agent-scope write-through granule stores) in every cooperative
+    # launch of this runner — the degraded mode bench.py falls back to when a launch reported a failed hand-off
+    write_through = DEFAULT_WRITE_THROUGH if write_through is None else bool(write_through)
+    return RunnerPlan(n_slots=n_slots, halves=halves, n_streams=n_streams, n_workspaces=2 if halves else n_slots,
+                      stream_priority=int(stream_priority), priority_chosen=priority_chosen, decode_impl=decode_impl, lds_kb=lds_kb,
+                      front_lds_kb=front_lds_kb, lockstep=bool(lockstep), common_start_us=common_start_us, write_through=write_through)
+
+
 class PipelinedRunner:
     """Throughput mode: ``slots`` independent batches in flight on ``slots`` HIP streams — or, for batches of 512 problems
     and more, ONE batch in flight whose recurrent part runs as two half-batches side by side (``halves``: the ``slots``
     static input / output sets then take turns on one stream); two slots with recurrences of 2000 steps and more start
     their replays in pairs (``lockstep``).  In every mode ``n_slots`` is the reuse distance of ``submit``'s outputs.
-    See __init__.
+    See runner_plan.
 
     The recurrent kernels are step-latency-bound and leave most of the machine idle, so consecutive
     (independent) batches are overlapped: every slot owns one captured HIP graph of the whole pass, its
@@ -630,121 +777,42 @@ class PipelinedRunner:
 
     def __init__(self, pipe, services, example_batch, slots=2, halves=None, write_through=None, auto_degrade=True,
                  stream_priority=None):
-        # Batches of 512 problems and more: ONE batch in flight, its recurrent part as two half-batches side by side
-        # (ML2PNPipeline.run with a pair of workspaces).  A cooperative launch has one workgroup per CU and two of them
-        # fill a CU's registers, so nothing else runs beside a co-resident pair; with two WHOLE batches in flight on two
-        # slots the pairing is left to chance — one slot's front half waits for the other's 25 ms encoder, encoders meet
-        # decoders — and the 1000-task shape ran 28.3 ms per batch where its recurrent kernels, always paired, need 21.1
-        # (tools/bench_slot_parts.py).  Below 512 problems a half-batch launch no longer fills the chip: two slots.
-        n = example_batch.n_problems
-        self.halves = bool(halves) if halves is not None else (n >= 512 and int(slots) > 1 and
-                                                               os.environ.get("GNNPN_PIPE_HALVES", "1") != "0")
-        # ``n_slots`` = the number of static input / output sets = the reuse distance of submit()'s outputs, in EVERY mode
-        # (the half-batch mode used to collapse to one slot, and a caller following the documented rule read
-        # outputs the next replay was already overwriting).  ``n_streams`` = steps in flight: the half-batch mode keeps ONE
-        # step in flight, so its slots' graphs replay one after the other on one stream.
-        self.pipe, self.services, self.n_slots = pipe, services, max(1, int(slots))
-        # ... and never more than TWO: a CU holds two cooperative workgroups, so two replays in flight are what the chip has room for —
-        # a third free-running stream put three launches in front of those two slots and ended in half-staffed launches and
-        # bounded-wait time-outs (round 6, tools/probes/dbg_three_slots.py: slots=3 ran 24 k problems/s with status 0x13).  More slots
-        # than two are more static input / output sets (a longer reuse distance), dealt onto the two streams in turn.
-        self.n_streams = 1 if self.halves else min(self.n_slots, 2)
-        # Stream priority of the slots: HIP deals a process's streams onto a few in-order hardware queues (GPU_MAX_HW_QUEUES,
-        # default 4) round robin, PER PRIORITY.  In a rank of an RCCL process group the collective's stream waits for one slot's
-        # step; when that wait shares a hardware queue with the other slot's stream it sits in front of that slot's launches
-        # (forced world-1 all-gather at the QWS shape: 449 k problems/s against 480 k without a process group).  Slot streams of a
-        # priority of their own never share a queue with the process group's (normal-priority) stream: 470 k, the same as 8
-        # hardware queues give (467 k) but without an environment variable that has to be set before the runtime starts — and
-        # the two do NOT add up (8 queues AND high priority: 367-378 k).  Without a process group high priority costs 0.35 %
-        # (477.8-478.2 k against 479.5-479.7 k), so it is used only where a collective stream exists.  profiles/LOG_r06.md §9.
-        self._priority_chosen = stream_priority is None and os.environ.get("GNNPN_PIPE_STREAM_PRIORITY") is None
-        if stream_priority is None:
-            env = os.environ.get("GNNPN_PIPE_STREAM_PRIORITY")
-            # (a process started with 8 or more hardware queues has the separation already — and must not get both)
-            many_queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 8
-            # Only for free-running slots on streams of their own: the half-batch mode keeps ONE step in flight on one stream (nothing of
-            # another slot for the collective's wait to sit in front of), and there high priority COSTS — Normal shape, forced RCCL:
-            # 199 k problems/s against 234-238 k at normal priority (238 k without a process group); 1000-task shape 22.8 k against 23.8 k
-            # (tools/r06/dist_priority_shapes.sh)
-            free_running = self.n_streams > 1
-            stream_priority = int(env) if env is not None else (-1 if free_running and _has_collective_stream() and not many_queues else 0)
-        self.stream_priority = int(stream_priority)
+        plan = self.plan = runner_plan(example_batch.n_problems, slots, getattr(pipe, "precision", "f32"),
+                                       int(getattr(pipe.low.actor, "seq_len", 0)), halves=halves, stream_priority=stream_priority,
+                                       write_through=write_through, collective_stream=_has_collective_stream())
+        self.pipe, self.services = pipe, services
+        self.halves, self.n_slots, self.n_streams, self.stream_priority = plan.halves, plan.n_slots, plan.n_streams, plan.stream_priority
+        self.decode_impl, self.lds_kb, self.front_lds_kb = plan.decode_impl, list(plan.lds_kb), plan.front_lds_kb
+        self.lockstep, self.common_start_us, self.write_through = plan.lockstep, plan.common_start_us, plan.write_through
         self.streams = [torch.cuda.Stream(priority=self.stream_priority) for _ in range(self.n_streams)]
-        # decoder form beside another slot's kernels: the 8-member build sized for two workgroups per CU (decode_impl 4).  Measured at QWS B=256 against the 16-member form (3):
-        # 228 k vs 221 k problems/s in fp32, 353 k vs 316 k with the split precision.
-        shared = 4
-        paired = self.n_streams > 1 or self.halves    # two cooperative launches share every CU
-        self.decode_impl = int(os.environ.get("GNNPN_PIPE_DECODE_IMPL", shared if paired else 0))
-        # Placement: the cooperative kernels claim one CU per workgroup at run time (csrc/coop_common.h, coop_place), so
-        # the two slots' launches share every CU one workgroup each whatever the dispatcher does; the LDS-footprint
-        # padding round 1 steered the dispatcher with (100 / 56 KB) is no longer needed and stays as an option only.
-        # Exact-split precision: the recurrent kernels hold the third weight piece in LDS (60 KB encoder, 69 KB decoder).  Two
-        # such workgroups fit a CU's 160 KB, but LDS is allocated in CONTIGUOUS ranges: with unequal footprints a freed 60 KB
-        # hole does not take the next 69 KB workgroup while the neighbour's range sits in the middle, the launch stays
-        # under-staffed, and two launches can starve each other until the bounded spins give up (seen: bench.py, precision
-        # split, two slots: members missing at the first sweep, 20 of 32 seats of an XCD staffed after 0.3 s).  Every
-        # cooperative launch of a multi-slot runner is therefore padded to ONE footprint, 78 KB: any freed range fits any
-        # waiting workgroup.  (f32: 19 / 27 KB — nothing to equalise.)
-        env = os.environ.get("GNNPN_SLOT_LDS_KB")
-        equal = 78 if (getattr(pipe, "precision", "f32") == "split" and paired) else 0
-        self.lds_kb = [int(v) for v in env.split(",")] if env else [equal] * self.n_slots
-        # ... and so are the ORDINARY kernels of a step that use LDS in front of the encoder (the one-launch GIN branch, the score
-        # product: ops.lds_footprint / gnnpn_lds_footprint_kb).  A cooperative workgroup that lands above such a kernel's few KB
-        # keeps its 78 KB in the middle of the CU when the small kernel has gone, and the OTHER slot's encoder workgroup for that
-        # CU finds no contiguous 78 KB until this encoder has finished: the two free-running slots slipped apart by 0.5 ms in
-        # every 20-step round (round 4 held the slots of a burst behind a common-start gate against it: 455 k problems/s with 4-8
-        # slow rounds of 89; with the front half at the same footprint 460 k and no slow round in 270, gate off —
-        # profiles/r05_slip_front_lds.jsonl).  Two free-running slots only: the half-batch mode runs its front half alone.
-        env = os.environ.get("GNNPN_PIPE_FRONT_LDS_KB")
-        self.front_lds_kb = int(env) if env is not None else (equal if (self.n_streams == 2 and not self.halves) else 0)
         self.count = 0
-        # Two slots, long recurrent kernels: start the two replays of a pair TOGETHER (a submission joins the leader that is
-        # still waiting for a partner, else it leads).  Free-running slots drift apart by the difference of their step
-        # times, and a cooperative launch that starts under the OTHER slot's front half finds every CU's LDS occupied by
-        # short-lived neighbours: its workgroups land above them (coop_place gives such seats back, up to a few hundred times
-        # per launch), seats are taken off their canonical CUs, and from there on both slots' launches run at the speed of
-        # one — the 2000-task shape alternated between 41 and 62 ms per step (spread 37-48 % over rounds; tools/slot_overlap.py).
-        # Started together, the two front halves run side by side and are gone when the encoders arrive.  The wait costs the
-        # tail by which the two replays differ (2 % at that shape); short steps (QWS, Normal) keep running free.
-        env = os.environ.get("GNNPN_PIPE_LOCKSTEP")
-        long_steps = int(getattr(pipe.low.actor, "seq_len", 0)) >= 2000          # recurrent steps per problem (T * K)
-        self.lockstep = self.n_slots == 2 and self.n_streams == 2 and (env == "1" or (env is None and long_steps))
-        self._open_leader, self._last_done = None, [None] * max(2, self.n_slots)
-        self._slot_done = [None] * self.n_slots
-        self._deferred = None                    # (slot, after): a leader whose replay waits for its partner's submission (submit)
         self._copy_streams = [torch.cuda.Stream() for _ in range(self.n_slots)]   # host-to-device transfers of pinned arenas (submit)
-        # Common start of a burst (two free-running slots only).  Two slots that begin a burst a host enqueue apart (~0.1 ms:
-        # the second replay is not in its queue yet when the first starts) run in step for a few steps and then slip apart ONCE
-        # — one slot's step takes 1.7 instead of 1.2 ms at the QWS shape — which costs a 20-step burst 0.5 ms (4 %); slots
-        # released TOGETHER stay in step (tools/probes/stagger_probe.py: 11.50 against 12.01 ms per 20 steps, the hold included;
-        # 30 and 60 us are too short, 90 and more work).  So the first replay after the runner has been idle is held behind a
-        # gate on another stream, and so is the other slot's first one; later replays are not.  The gate (gnnpn_gate_wait: one
-        # wavefront polling a word in pinned host memory) is opened by the HOST the moment the second replay is in its queue —
-        # or by synchronize / poll, or after COMMON_START_US at the latest (a burst of one replay that is waited for some other way).
-        # "Idle" = since the last synchronize() / poll() of this runner: a caller that works in bursts waits for them that way.
-        self.common_start_us = float(os.environ.get("GNNPN_PIPE_COMMON_START_US", COMMON_START_US)) \
-            if (self.n_slots == 2 and self.n_streams == 2 and not self.lockstep) else 0.0
-        self._gate = None                        # [event, slots still to be held behind it]
         self._gate_flag = torch.zeros(1, dtype=torch.int32).pin_memory() if self.common_start_us > 0 else None   # the word the gate polls
         self._gate_seq = 0                       # value that opens the current gate (one more per burst)
-        self._drained = True                     # nothing in flight: set by synchronize / poll, cleared by the next replay
         # (the gate's spin runs on slot 0's transfer stream, idle whenever the batches are resident: one more stream of its own
         # changed which streams share a hardware queue and cost the pinned-host path 1.7 %)
         self._gate_stream = self._copy_streams[0] if self.common_start_us > 0 else None
+        self._idle()
         # gnnpn_launch_opts_t.paired_start: half-batches (set inside ML2PNPipeline.run) and slots started in pairs begin together
         self.batches = [self._clone(example_batch) for _ in range(self.n_slots)]   # never alias caller tensors
-        self.workspaces = [ops.new_workspaces(example_batch.x.device) for _ in range(2 if self.halves else self.n_slots)]
+        self.workspaces = [ops.new_workspaces(example_batch.x.device) for _ in range(plan.n_workspaces)]
         # (every graph keeps its OWN memory pool, also the half-batch mode's two that never run together: in a shared pool
         # the second capture places its outputs where the first keeps intermediates, and the first graph's next replay
         # writes over them — measured: garbage in a slot's outputs one submission later)
-        # write_through: the placement-independent hand-off form (agent-scope write-through granule stores) in every cooperative
-        # launch of this runner — the degraded mode bench.py falls back to when a launch reported a failed hand-off
-        self.write_through = DEFAULT_WRITE_THROUGH if write_through is None else bool(write_through)
         # auto_degrade: the first poll / synchronize that finds a failed launch (any status code, the shortfall of finished
         # workgroup-tiles included) re-captures every slot with the write-through hand-off; ``degraded`` keeps the status that
         # caused it.  The batches since the previous poll are invalid either way and the caller submits them again.
         self.auto_degrade, self.degraded = bool(auto_degrade), None
         self._capture_graphs()
+
+    def _idle(self):
+        """The start coordination (pairs of ``lockstep``, the deferred leader, the common-start gate) with nothing in flight and
+        nobody waiting: a new runner's, and that of one whose graphs are captured anew (``_degrade``, behind ``_wait``)."""
+        self._open_leader, self._last_done = None, [None] * max(2, self.n_slots)
+        self._slot_done = [None] * self.n_slots
+        self._deferred = None                    # (slot, after): a leader whose replay waits for its partner's submission (submit)
+        self._gate = None                        # [event, slots still to be held behind it]
+        self._drained = True                     # nothing in flight: set by synchronize / poll, cleared by the next replay
 
     def _capture_graphs(self):
         with ops.lds_footprint(self.front_lds_kb):            # captured launches keep the footprint (a per-launch attribute)
@@ -762,8 +830,7 @@ class PipelinedRunner:
         warnings.warn(f"gnnpn: PipelinedRunner: cooperative launches reported status {word:#x}; switching this runner to the "
                       f"write-through hand-off (the batches since the last poll / synchronize must be submitted again)", RuntimeWarning)
         self.write_through, self.degraded = True, word
-        self._open_leader, self._last_done = None, [None] * max(2, self.n_slots)
-        self._slot_done = [None] * self.n_slots
+        self._idle()
         self._capture_graphs()
 
     @staticmethod
@@ -814,8 +881,8 @@ class PipelinedRunner:
         (each replay waits for both), so that the pair still starts together; ``after`` of the leader runs at that moment.
         Touching ``stream(slot)``, ``poll`` or ``synchronize`` enqueues a waiting leader at once (alone)."""
         s = self.count % self.n_slots
-        if self.count == 0 and self._priority_chosen and self.stream_priority == 0 and self.n_streams > 1 and _has_collective_stream() \
-                and int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) < 8:
+        if self.count == 0 and self.plan.priority_chosen and self.stream_priority == 0 and \
+                _separate_priority(self.n_streams, _has_collective_stream()) != 0:
             import warnings                                # the process group came AFTER this runner: its streams were created at normal priority
             warnings.warn("PipelinedRunner was created before the RCCL process group: its slots' streams share hardware queues with the "
                           "collective's stream (about 6 % slower with one all-gather per 8 steps at the QWS shape); create the runner after "
@@ -824,37 +891,7 @@ class PipelinedRunner:
         self.count += 1
         if self._deferred is not None and self._deferred[0] == s:
             self._flush_deferred()
-        staged = False                                   # a transfer of this batch is on the slot's copy stream
-        st = self._stream(s)
-        with torch.cuda.stream(st):
-            if batch is not None:
-                dst = self.batches[s]
-                lim = ops.REQUEST_BRANCH_MAX_NODES        # the captured graph holds the one-launch GIN branch (small
-                if 0 < dst.max_nodes <= lim and not 0 < batch.max_nodes <= lim:   # workflow graphs) or the layered kernels
-                    raise ops.GnnpnError(f"PipelinedRunner: the captured graph holds the one-launch GIN branch (graphs of <= "
-                                         f"{lim} nodes); this batch has max_nodes = {batch.max_nodes}")
-                if getattr(batch, "_layout", None) is not None and batch._layout == dst._layout and \
-                        (batch._arena.device == dst._arena.device or (batch._arena.device.type == "cpu" and batch._arena.is_pinned())):
-                    if batch._arena.device.type == "cpu" and HOST_COPY_ON_ITS_OWN_STREAM:
-                        # pinned host arena: the copy engine's transfer goes on a stream of its own, behind the replay that last read
-                        # this slot's static inputs and in front of its next one (events) — in half-batch mode the next batch then
-                        # crosses PCIe under the current batch's kernels
-                        cs = self._copy_streams[s]
-                        if self._slot_done[s] is not None:
-                            cs.wait_event(self._slot_done[s])      # the replay that last read this slot's static inputs
-                        else:
-                            cs.wait_stream(st)
-                        with torch.cuda.stream(cs):
-                            dst._arena.copy_(batch._arena, non_blocking=True)
-                        st.wait_stream(cs)
-                        staged = True
-                    else:
-                        dst._arena.copy_(batch._arena, non_blocking=True)      # packed alike: one copy (device-to-device, or pinned host to device)
-                else:
-                    for a, b in zip(self._fields(dst), self._fields(batch)):
-                        if a.shape != b.shape:
-                            raise ops.GnnpnError(f"PipelinedRunner: batch shape {tuple(b.shape)} != captured {tuple(a.shape)}")
-                        a.copy_(b, non_blocking=True)
+        staged = batch is not None and self._load(s, batch)
         if self.lockstep and staged:
             # Pairs and transfers: two transfers of a pair run one after the other on the copy engine (0.7 ms each at the 2000-task
             # shape), so a leader that starts behind ITS transfer is that far ahead of its partner, its encoder arrives while the
@@ -866,8 +903,7 @@ class PipelinedRunner:
             lead, after_lead = self._deferred
             self._deferred = None
             return self._replay_pair(lead, after_lead, s, after), s
-        if self._deferred is not None:
-            self._flush_deferred()
+        self._flush_deferred()
         if batch is not None and self.common_start_us > 0:
             arena = getattr(batch, "_arena", None)
             if (arena if arena is not None else batch.x).device.type == "cpu":
@@ -875,42 +911,80 @@ class PipelinedRunner:
                 #                                      engine, slots in step wait for each other's: 436 against 442 k problems/s)
         return self._replay(s, after), s
 
+    def _load(self, s, batch):
+        """Copy ``batch`` into slot ``s``'s static inputs, in front of the slot's next replay.  Returns True where the transfer was
+        staged on the slot's copy stream (a pinned host arena), which is what a pair of ``lockstep`` defers its leader for."""
+        dst, st = self.batches[s], self._stream(s)
+        lim = ops.REQUEST_BRANCH_MAX_NODES        # the captured graph holds the one-launch GIN branch (small
+        if 0 < dst.max_nodes <= lim and not 0 < batch.max_nodes <= lim:   # workflow graphs) or the layered kernels
+            raise ops.GnnpnError(f"PipelinedRunner: the captured graph holds the one-launch GIN branch (graphs of <= "
+                                 f"{lim} nodes); this batch has max_nodes = {batch.max_nodes}")
+        packed_alike = getattr(batch, "_layout", None) is not None and batch._layout == dst._layout
+        from_host = packed_alike and _pinned_host(batch._arena)
+        with torch.cuda.stream(st):
+            if from_host and HOST_COPY_ON_ITS_OWN_STREAM:
+                # pinned host arena: the copy engine's transfer goes on a stream of its own, behind the replay that last read
+                # this slot's static inputs and in front of its next one (events) — in half-batch mode the next batch then
+                # crosses PCIe under the current batch's kernels
+                cs = self._copy_streams[s]
+                if self._slot_done[s] is not None:
+                    cs.wait_event(self._slot_done[s])      # the replay that last read this slot's static inputs
+                else:
+                    cs.wait_stream(st)
+                with torch.cuda.stream(cs):
+                    dst._arena.copy_(batch._arena, non_blocking=True)
+                st.wait_stream(cs)
+                return True
+            if from_host or (packed_alike and batch._arena.device == dst._arena.device):
+                dst._arena.copy_(batch._arena, non_blocking=True)      # packed alike: one copy (device-to-device, or pinned host to device)
+            else:
+                for a, b in zip(self._fields(dst), self._fields(batch)):
+                    if a.shape != b.shape:
+                        raise ops.GnnpnError(f"PipelinedRunner: batch shape {tuple(b.shape)} != captured {tuple(a.shape)}")
+                    a.copy_(b, non_blocking=True)
+        return False
+
     def _replay(self, s, after=None):
         """One slot's replay, with the pairing of ``lockstep`` for submissions that come one at a time."""
+        st, started = self._stream(s), None
+        if self.lockstep:
+            # A submission joins the leader that is waiting for a partner (and starts with it) if that leader has not
+            # finished yet — the host runs ahead of the device, so back-to-back submissions always pair —; otherwise it
+            # leads a new pair, behind whatever the other slot ran last.
+            lead = self._open_leader
+            if lead is not None and lead[0] != s and not lead[2].query():
+                st.wait_event(lead[1])
+                self._open_leader = None
+            else:
+                if self._last_done[1 - s] is not None:
+                    st.wait_event(self._last_done[1 - s])
+                started = torch.cuda.Event()
+                started.record(st)
+        last_held = self.common_start_us > 0 and self._hold_for_common_start(s, st)
+        return self._enqueue(s, after, started, opens_gate=last_held)
+
+    def _enqueue(self, s, after, started=None, opens_gate=False):
+        """Slot ``s``'s graph replayed on its stream, ``done`` recorded behind it and booked for the slot, ``after`` called.
+        ``started``: this replay leads a pair (``_replay``) that began with that event.  ``opens_gate``: this replay completes the
+        burst held behind the common-start gate, which the host opens the moment the replay is enqueued."""
         st = self._stream(s)
         with torch.cuda.stream(st):
-            leader = False
-            if self.lockstep:
-                # A submission joins the leader that is waiting for a partner (and starts with it) if that leader has not
-                # finished yet — the host runs ahead of the device, so back-to-back submissions always pair —; otherwise it
-                # leads a new pair, behind whatever the other slot ran last.
-                lead = self._open_leader
-                if lead is not None and lead[0] != s and not lead[2].query():
-                    st.wait_event(lead[1])
-                    self._open_leader = None
-                else:
-                    leader = True
-                    if self._last_done[1 - s] is not None:
-                        st.wait_event(self._last_done[1 - s])
-                    started = torch.cuda.Event()
-                    started.record(st)
-            last_held = self.common_start_us > 0 and self._hold_for_common_start(s, st)
             out = self.graphs[s]()
-            if last_held:
+            if opens_gate:
                 self._open_gate()                   # both held replays are in their queues: they start now, together
             done = torch.cuda.Event()
             done.record(st)
             self._slot_done[s] = done               # what the next transfer into this slot's static inputs waits for
             if self.lockstep:
                 self._last_done[s] = done
-                if leader:
+                if started is not None:
                     self._open_leader = (s, started, done)
             if after is not None:
                 after(out, s)
         return out
 
     def _hold_for_common_start(self, s, st):
-        """First replay after the runner was waited for: a gate (see __init__) in front of this replay and the other slot's next
+        """First replay after the runner was waited for: a gate (see runner_plan) in front of this replay and the other slot's next
         one.  Returns True if this replay completes the pair — the caller opens the gate once the replay is enqueued."""
         if self._gate is None and self._drained:
             # (Deliberately NOT "whenever the streams happen to be empty": a host-paced caller whose device catches up now and
@@ -946,17 +1020,10 @@ class PipelinedRunner:
         started = torch.cuda.Event()
         started.record(st_l)
         st_f.wait_event(started)
-        outs = {}
-        for slot, stream, cb in ((lead, st_l, after_lead), (s, st_f, after)):
-            with torch.cuda.stream(stream):
-                outs[slot] = self.graphs[slot]()
-                done = torch.cuda.Event()
-                done.record(stream)
-                self._slot_done[slot] = self._last_done[slot] = done
-                if cb is not None:
-                    cb(outs[slot], slot)
+        self._enqueue(lead, after_lead)
+        out = self._enqueue(s, after)
         self._open_leader = None
-        return outs[s]
+        return out
 
     def _flush_deferred(self):
         if self._deferred is not None:
@@ -1001,14 +1068,18 @@ class PipelinedRunner:
         """The same kernels on ONE stream, nothing overlapped (used to check an overlapped result)."""
         return self.pipe.run(self.services, self.batches[slot], decode_impl=self.decode_impl, write_through=self.write_through)   # one launch per kernel, whole batch
 
-    def poll(self):
-        """Wait for every slot's stream; the OR of the slots' sticky status words since the last poll / check, cleared — 0: no
-        launch reported a failed hand-off.  The non-raising form of ``synchronize(check=True)``."""
+    def _wait(self):
+        """Everything this runner has been given is enqueued (a waiting leader, alone), released (a pending gate) and finished."""
         self._flush_deferred()
         self._open_gate()
         for st in self.streams:
             st.synchronize()
         self._drained = True
+
+    def poll(self):
+        """Wait for every slot's stream; the OR of the slots' sticky status words since the last poll / check, cleared — 0: no
+        launch reported a failed hand-off.  The non-raising form of ``synchronize(check=True)``."""
+        self._wait()
         word = 0
         for w in self.workspaces:
             word |= w.poll()
@@ -1023,11 +1094,7 @@ class PipelinedRunner:
     def synchronize(self, check=True):
         """Wait for every slot's stream; with ``check`` raise if any launch of any slot since the last call reported a
         failed inter-workgroup hand-off (its outputs would be garbage) — the sticky status words of the slots."""
-        self._flush_deferred()
-        self._open_gate()
-        for st in self.streams:
-            st.synchronize()
-        self._drained = True
+        self._wait()
         if check:
             err = None
             for w in self.workspaces:

@@ -755,6 +755,40 @@ def test_more_than_two_slots_still_two_in_flight(dev):
             assert torch.equal(idx, refs[j]["idx_high"]) and torch.equal(R, refs[j]["R"])
 
 
+def test_runner_follows_its_plan(dev):
+    """A PipelinedRunner is built as ``runner_plan`` of its arguments says — two free-running slots, half-batches, three slots on two
+    streams: ``plan`` is that plan, every public attribute its field, the workspaces and streams its counts — and one batch through
+    each equals the single-stream run (tests/test_runner_plan_host.py has the plan's table, test_runner_schedule_host.py the order of
+    the stream operations)."""
+    import gnnpn_sc_amd.synth as synth
+    from bench import build_models
+    from gnnpn_sc_amd.pipeline import DeviceBatch, DeviceServices, ML2PNPipeline, PipelinedRunner, _has_collective_stream, runner_plan
+    T, S, K, B = 47, 940, 5, 48
+    table = synth.make_service_table(T, S, seed=0, degree=16)
+    net, low, high = build_models(T, S, K, dev)
+    pipe = ML2PNPipeline(net, low, high, K)
+    svc = DeviceServices.from_table(table, dev)
+    batch = DeviceBatch.from_problems(synth.make_problem_batch(table, B, seed=40, tasks_per_problem=10), dev)
+    refs = {}
+    for kw in ({"slots": 2}, {"slots": 2, "halves": True}, {"slots": 3}):
+        runner = PipelinedRunner(pipe, svc, batch, **kw)
+        plan = runner_plan(B, kw["slots"], pipe.precision, low.actor.seq_len, halves=kw.get("halves"),
+                           collective_stream=_has_collective_stream())
+        assert runner.plan == plan and low.actor.seq_len == T * K
+        for name in ("halves", "n_slots", "n_streams", "stream_priority", "decode_impl", "front_lds_kb", "lockstep", "common_start_us",
+                     "write_through"):
+            assert getattr(runner, name) == getattr(plan, name), name
+        assert runner.lds_kb == list(plan.lds_kb) and runner.auto_degrade is True and runner.degraded is None and runner.count == 0
+        assert len(runner.workspaces) == plan.n_workspaces and len(runner.streams) == plan.n_streams
+        assert len(runner.batches) == len(runner.graphs) == plan.n_slots
+        out, slot = runner.submit(batch)
+        runner.synchronize()
+        if runner.decode_impl not in refs:
+            refs[runner.decode_impl] = eager_reference(pipe, svc, batch, decode_impl=runner.decode_impl)
+        ref = refs[runner.decode_impl]
+        assert slot == 0 and torch.equal(out["idx_high"], ref["idx_high"]) and torch.equal(out["R"], ref["R"]), kw
+
+
 def test_two_runners_take_turns(dev):
     """Two PipelinedRunners of one process, fed alternately (round 6, tools/probes/dbg_two_runners.py): four cooperative launches in front
     of the two workgroup slots of every CU used to end in half-staffed launches and bounded-wait time-outs (status 0x13, 18 ms per step).
