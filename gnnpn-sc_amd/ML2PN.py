@@ -105,6 +105,21 @@ def infer_pairs_shortlist(dataset, net, low, high, n_per, epoch=-1, device="cuda
                   pair_rounds, pair_span, pair_rank)
 
 
+def infer_tabu(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1, sample_seed=None,
+               descend=16, all_starts=False, tabu_steps=32, tenure=None):
+    """``infer`` with ``descend`` whose one-swap optimum is left by a tabu walk of up to ``tabu_steps`` steps (>= 0; ``tenure`` >= 0,
+    None: ops.DEFAULT_TENURE; pipeline.descend_tabu): ``ML+2PN+tabu.txt`` in ``infer``'s format plus the per-problem ``steps``,
+    ``best_step`` and ``stalled``, and ``tabu_steps`` / ``tenure``.  With ``all_starts`` (and samples > 1) the walk runs from every
+    replica (pipeline.descend_starts_tabu): ``ML+2PN+multistart+tabu.txt``.  Without ``woa`` and without pair sweeps.  A function of
+    its own because ``infer``'s parameter list is pinned by the host tests."""
+    from . import ops
+    tenure = ops.DEFAULT_TENURE if tenure is None else tenure
+    if descend is None or tabu_steps is None or tabu_steps < 0 or tenure < 0:
+        raise ValueError("ML2PN.infer_tabu: tabu_steps needs descend, a number of steps >= 0 and a tenure >= 0")
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts,
+                  None, None, tabu=(int(tabu_steps), int(tenure)))
+
+
 def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
                    sample_seed=None, descend=None, all_starts=False, pair_rounds=None, pair_span=None, pair_rank=None):
     """``infer`` (with ``pair_span`` / ``pair_rank``: ``infer_pairs_windowed`` / ``infer_pairs_shortlist``) whose last search stage
@@ -124,7 +139,7 @@ def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", ba
 
 
 def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, pair_rounds,
-           pair_span, pair_rank=None, services=False):
+           pair_span, pair_rank=None, services=False, tabu=None):
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
@@ -187,7 +202,7 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
         _refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
                             **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds, pair_span=pair_span,
                             pair_rank=pair_rank, action_ids=np.concatenate(test_ids).astype(np.int32) if services and test_ids else None,
-                            services=services,
+                            services=services, tabu=tabu,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
@@ -206,8 +221,11 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
 
 
 def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, pair_rounds=None,
-                         pair_span=None, pair_rank=None, services=False, action_ids=None):
-    """refine_test_quarter; ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
+                         pair_span=None, pair_rank=None, services=False, action_ids=None, tabu=None):
+    """refine_test_quarter; ``tabu`` = (steps, tenure) (with ``descend``, without pair options and ES-WOA): pipeline.descend_tabu
+    (with ``starts``: descend_starts_tabu) in place of the descent, written as ``ML+2PN+tabu.txt`` / ``ML+2PN+multistart+tabu.txt``
+    with the per-problem steps, best_step and stalled and the two settings.
+    ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
     with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``.  ``pair_rank`` (>= 0, with ``pair_span``, without
     ES-WOA): pipeline.descend_pairs_shortlist (with ``starts``: descend_starts_pairs_shortlist) with that span and rank, and the file
     gains ``top`` too.  ``services``: the last stage's compositions also go to ``ML+2PN+services.txt`` (write_services);
@@ -245,11 +263,18 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
                   (True, 3): pl.descend_starts_pairs_shortlist}[multi, given]
         names = ("pair_rounds", "pair_span", "pair_rank") if multi else ("max_rounds", "max_span", "max_rank")
         kw.update(zip(names[:given], (pair_rounds, pair_span, pair_rank)))
+        if tabu is not None:                         # the tabu walk in the descent's place: its own function, file and counters
+            search = pl.descend_starts_tabu if multi else pl.descend_tabu
+            name = "ML+2PN+multistart+tabu.txt" if multi else "ML+2PN+tabu.txt"
+            kw.update(max_steps=tabu[0], tenure=tabu[1])
         res = search(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev) if multi else out, **kw)
         quality = res["quality"].cpu().tolist()
-        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name,
-                                  extra=({**counters(res), **({} if pair_span is None else {"span": pair_span}),
-                                         **({} if pair_rank is None else {"top": pair_rank})}) if pairs else None)
+        if tabu is not None:
+            extra = {**{k: res[k].cpu().tolist() for k in ("steps", "best_step", "stalled")}, "tabu_steps": tabu[0], "tenure": tabu[1]}
+        else:
+            extra = ({**counters(res), **({} if pair_span is None else {"span": pair_span}),
+                      **({} if pair_rank is None else {"top": pair_rank})}) if pairs else None
+        written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name, extra=extra)
         if multi:
             if services and action_ids is not None:  # the winner's ids, as its rows
                 win = res["start_index"].long()[:, None, None]

@@ -22,6 +22,12 @@
 // max_rank candidates whose single swap into the current composition has the lowest merit — the one-swap sweep's own evaluation
 // (slot_path, one_swap_merit), ranked by counting in LDS — and the sweep tries only pairs of kept candidates
 // (tests/pair_shortlist_reference.py).  The four builds without shortlists compile none of it.
+//
+// The tabu walk (descend_tabu_kernel, descend_tabu_wide_kernel) leaves the one-swap optimum on purpose: every step takes the best
+// single swap of the whole composition — the shortlist pass's slot loop over slot_path / one_swap_merit, one (value, key) argmin per
+// step — whether or not it lowers the merit, bars the position the slot left for `tenure` steps unless the swap beats the best merit
+// seen, and remembers the best composition; the one-swap sweeps polish it where the walk was cut there (tests/tabu_reference.py).
+// No draws: a pure function of the tables.  The six descent builds compile none of it.
 #include "woa_eval.h"
 
 #include <climits>
@@ -647,6 +653,167 @@ __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const
         o.converged[p] = still && settled;
     }
 }
+
+// ---- tabu walk: leave the one-swap optimum by the best single swap, improving or not ----------------------------------------------------
+// What the walk keeps beside DescendMem, both in LDS: expire [n_cand] (candidate base[j] + c may not return to slot j at steps
+// t <= expire; 0 = never left) and best [T], the best composition seen.
+struct TabuMem {
+    int* expire;
+    int* best;
+};
+struct TabuOut {
+    double* best_fitness; double* start_fitness; int32_t* best_pos; double* history; int32_t* sweeps; int32_t* moves;
+    double* walk; int32_t* steps; int32_t* best_step; int32_t* stalled;
+};
+
+// One step's evaluation, form_shortlists' slot loop: for every slot j in order, thread = one candidate c != cur[j] of its list (chunks
+// beyond the workgroup, lowest position first), the single-swap merit f by slot_path / one_swap_merit with pre2 / pre3 carried across
+// the slots and S.cr constant.  (j, c) is admissible where expire[base[j] + c] < t, or f < best_f (aspiration).  A thread keeps its
+// best admissible (f, base[j] + c) under strict < — its keys only grow, so the lowest stays among equals, and a NaN never enters —
+// and ONE (value, key) argmin over the workgroup follows the last slot.  key = INT_MAX: no admissible move.  Nothing moves here.
+// Bounded by T and list lengths; j and every barrier are workgroup-uniform.
+template <int NT>
+__device__ __forceinline__ void tabu_step(const DescendMem& M, const DescendState& S, const int* expire, int t, double best_f, double& f_out,
+                                          int& key_out) {
+    const WideLds& L = M.L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = S.T;
+    const double* cand = S.cand;
+    double pre2 = 1.0, pre3 = 1.0;                                    // np.cumprod of columns 2 and 3 up to slot j - 1
+    double bf = INFINITY;
+    int bk = INT_MAX;
+    for (int j = 0; j < T; ++j) {
+        const SlotPath sp = slot_path<NT>(M, T, j);
+        const int bj = L.base[j], lj = L.len[j], cj = M.cur[j];
+        const double old0 = L.col0[j];
+        for (int c = tid; c < lj; c += NT) {
+            if (c == cj) continue;
+            const double f = one_swap_merit<NT>(M, S.cr, cand + (size_t)(bj + c) * 4, T, j, sp, old0, pre2, pre3);
+            if ((expire[bj + c] < t || f < best_f) && f < bf) {
+                bf = f;
+                bk = bj + c;
+            }
+        }
+        if constexpr (NT > 64)
+            if (sp.depth > 0) __syncthreads();                        // sib is free for slot j + 1
+        pre2 = j == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[j]);
+        pre3 = j == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[j]);
+    }
+    wave_argmin(bf, bk, lane);
+    if constexpr (NT > 64) {
+        if (lane == 0) {
+            L.red[wave] = bf;
+            L.cnt[wave] = bk;
+        }
+        __syncthreads();
+        bf = L.red[0];
+        bk = L.cnt[0];
+        for (int w = 1; w < NT / 64; ++w) take_better(bf, bk, L.red[w], L.cnt[w]);
+    }
+    f_out = bf;
+    key_out = bk;
+}
+
+// The tabu walk of one problem, both forms (tests/tabu_reference.py is its Python restatement).  Phase 0 = the one-swap sweeps.  Step
+// t = 1 .. max_steps: tabu_step's move is taken whether or not it is below the current merit, and the position the slot leaves is
+// tabu through step t + tenure; no admissible move ends the walk (stalled, the step is not counted).  best / best_f / best_step
+// follow the walk under strict <.  Then best goes back into cur and the columns, and where the walk was cut at its best (the last
+// step taken is best_step, and it did not stall) the one-swap sweeps run once more from there: best need not be a one-swap optimum.
+// history[t - 1] = the best merit after step t (past the last step the last such value, before the polish; max_steps = 0: phase
+// 0's merit), walk[t - 1] = the current merit after step t, NaN past the last step.
+template <int NT, bool TABLE_IN_LDS>
+__device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const TabuMem& K, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+                                                     const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                     const int32_t* __restrict__ start_pos, int32_t max_sweeps, int32_t max_steps,
+                                                     int32_t tenure, const TabuOut& o) {
+    const WideLds& L = M.L;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int ld = max_steps > 1 ? max_steps : 1;                  // history and walk have at least one entry per problem
+    double* hist = o.history + (size_t)p * ld;
+    double* walk = o.walk + (size_t)p * ld;
+    DescendState S;
+    if (!descend_load<NT, TABLE_IN_LDS>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, o.start_fitness, S)) {
+        not_searched(p, tid, NT, o.best_fitness, o.start_fitness, o.history, ld, o.sweeps, o.moves);
+        for (int s = tid; s < ld; s += NT) walk[s] = NAN;
+        if (tid == 0) {
+            o.steps[p] = -1;
+            o.best_step[p] = 0;
+            o.stalled[p] = 0;
+        }
+        return;
+    }
+    const int T = S.T;
+    const double* cand = S.cand;
+    const int n_cand = L.base[T - 1] + L.len[T - 1];               // the lists are contiguous (descend_load checked them)
+    for (int i = tid; i < n_cand; i += NT) K.expire[i] = 0;
+    __syncthreads();
+    int sweeps = 0, moves = 0, steps = 0, best_step = 0, stalled = 0;
+    bool settled = false;
+    one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+    double best_f = S.fit;
+    for (int j = tid; j < T; j += NT) K.best[j] = M.cur[j];
+    for (int t = 1; t <= max_steps; ++t) {
+        double f;
+        int key;
+        tabu_step<NT>(M, S, K.expire, t, best_f, f, key);
+        if (key == INT_MAX) {                                         // workgroup-uniform
+            stalled = 1;
+            break;
+        }
+        for (int j = tid; j < T; j += NT) {                            // the one thread whose slot owns the key moves
+            const int c = key - L.base[j];
+            if (c < 0 || c >= L.len[j]) continue;
+            const double* r = cand + (size_t)key * 4;
+            K.expire[L.base[j] + M.cur[j]] = tenure > INT_MAX - t ? INT_MAX : t + tenure;
+            M.cur[j] = c;
+            L.col0[j] = r[0];
+            M.col1[j] = r[1];
+            L.col2[j] = r[2];
+            L.col3[j] = r[3];
+        }
+        S.fit = f;
+        steps = t;
+        __syncthreads();
+        S.cr.scan(L.col0, M.col1, T);
+        if (f < best_f) {
+            best_f = f;
+            best_step = t;
+            for (int j = tid; j < T; j += NT) K.best[j] = M.cur[j];
+        }
+        if (tid == 0) {
+            hist[t - 1] = best_f;
+            walk[t - 1] = f;
+        }
+    }
+    for (int s = steps + tid; s < ld; s += NT) {
+        hist[s] = best_f;
+        walk[s] = NAN;
+    }
+    __syncthreads();                                                  // best stands
+    if (best_step < steps) {                                          // the walk went on past its best: back to it
+        for (int j = tid; j < T; j += NT) {
+            const int c = K.best[j];
+            const double* r = cand + (size_t)(L.base[j] + c) * 4;
+            M.cur[j] = c;
+            L.col0[j] = r[0];
+            M.col1[j] = r[1];
+            L.col2[j] = r[2];
+            L.col3[j] = r[3];
+        }
+        S.fit = best_f;
+        __syncthreads();
+        S.cr.scan(L.col0, M.col1, T);
+    } else if (steps > 0 && !stalled) {                               // cut at its best: the polish
+        one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
+    }
+    descend_store<NT, TABLE_IN_LDS>(M, sh, S, o.best_fitness, o.best_pos);
+    if (tid == 0) {
+        o.sweeps[p] = sweeps;
+        o.moves[p] = moves;
+        o.steps[p] = steps;
+        o.best_step[p] = best_step;
+        o.stalled[p] = stalled;
+    }
+}
 }  // namespace
 
 // ---- lane form: one wavefront per problem (<= 64 slots) --------------------------------------------------------------------------------
@@ -746,6 +913,33 @@ __global__ __launch_bounds__(WNT) void descend_pairs_shortlist_wide_kernel(Shape
     descend_pairs_problem<WNT, false, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o, so);
 }
 
+// ---- tabu walk, lane form: descend_kernel's LDS layout, then expire [max_cand] and best [64] i32 (descend_tabu_lds_bytes) ----------------
+// No atomics, no waits on other workgroups; loops bounded by max_steps, max_sweeps, T, list lengths.
+__global__ __launch_bounds__(64) void descend_tabu_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
+                                                          const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
+                                                          int32_t max_sweeps, int32_t max_steps, int32_t tenure, TabuOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const DescendMem M = lane_mem(lds_raw);
+    TabuMem K;
+    K.expire = reinterpret_cast<int*>(M.table + (size_t)sh.max_cand * 4);
+    K.best = K.expire + sh.max_cand;
+    descend_tabu_problem<64, true>(M, K, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
+}
+
+// Tabu walk, workgroup form: descend_wide_kernel's LDS layout with expire [max_cand] and best [T] i32 behind the base / len tables.
+__global__ __launch_bounds__(WNT) void descend_tabu_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                                const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                                const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                                int32_t max_steps, int32_t tenure, TabuOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int T = sh.count(blockIdx.x);
+    const DescendMem M = wide_mem(lds_raw, T, 1, o.best_pos + sh.out_row(blockIdx.x));
+    TabuMem K;
+    K.expire = M.L.len + T;
+    K.best = K.expire + sh.max_cand;
+    descend_tabu_problem<WNT, false>(M, K, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
+}
+
 // LDS bytes one problem needs (host side).  Lane form: the columns + bounds + base / len / cur + its candidate table.  Workgroup
 // form: four columns, red[8] + bounds[4] + sib[sib_rows][SIB_MAX], cnt[4] + base / len tables.
 static size_t descend_lds_bytes(int n_cand) { return (256 + 4 + (size_t)n_cand * 4) * sizeof(double) + 3 * 64 * sizeof(int); }
@@ -781,6 +975,40 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
     return search_launch(lds, too_large, use_wide ? descend_wide_kernel : descend_kernel, B, use_wide ? WNT : 64, stream,
                          use_wide ? "descend_ragged_f64 (workgroup form)" : "descend_ragged_f64", sh, cand_ptr, cand, bounds, start_pos,
                          max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
+}
+
+// The tabu builds: the same, plus expire [max_cand] i32 and best [64 | max_slots] i32.
+static size_t descend_tabu_lds_bytes(bool use_wide, int max_slots, int max_cand) {
+    return (use_wide ? descend_wide_lds_bytes(max_slots) : descend_lds_bytes(max_cand)) +
+           ((size_t)max_cand + (use_wide ? max_slots : 64)) * sizeof(int);
+}
+
+// Tabu walk (new: no reference counterpart).  Argument checks as descend_pairs_entry's; max_cand >= 1 in both forms: it sizes expire.
+extern "C" int gnnpn_descend_tabu_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                             const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                             int32_t max_sweeps, int32_t max_steps, int32_t tenure, int32_t wide, double* best_fitness,
+                                             double* start_fitness, int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps,
+                                             int32_t* moves, double* walk, int32_t* steps, int32_t* best_step, int32_t* stalled,
+                                             void* stream) {
+    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_steps >= 0 && tenure >= 0 && max_slots >= 1,
+                  "descend_tabu_ragged: bad argument");
+    if (B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && history && sweeps &&
+                  moves && walk && steps && best_step && stalled, "descend_tabu_ragged: null operand");
+    if (max_cand < 1)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_tabu_ragged: max_cand must be >= 1 (it sizes the tabu table, and in the lane form the candidate "
+                   "table, in LDS)");
+    const bool use_wide = wide || max_slots > 64;
+    const size_t lds = descend_tabu_lds_bytes(use_wide, max_slots, max_cand);
+    auto too_large = [&]() -> int {
+        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_tabu_ragged: %zu B of LDS per problem (%d slots, %d candidates) exceed a CU (160 KB)%s", lds,
+                   max_slots, max_cand, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
+    };
+    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, n_lists, best_rows};
+    const TabuOut o{best_fitness, start_fitness, best_pos, history, sweeps, moves, walk, steps, best_step, stalled};
+    return search_launch(lds, too_large, use_wide ? descend_tabu_wide_kernel : descend_tabu_kernel, B, use_wide ? WNT : 64, stream,
+                         use_wide ? "descend_tabu_ragged_f64 (workgroup form)" : "descend_tabu_ragged_f64", sh, cand_ptr, cand, bounds,
+                         start_pos, max_sweeps, max_steps, tenure, o);
 }
 
 // The arguments of a pair entry: the shortlist entry's parameter list in include/gnnpn_hip.h, name for name and in its order, so an

@@ -1119,6 +1119,11 @@ def woa_status_error(status, first, replicas=None):
                       f"{_WOA_STATUS.get(status, 'unknown status')}")
 
 
+# The tabu walk's default tenure: the value of tools/bench_tabu.py's sweep over {1, 2, 4, 8, 16} at max_steps = 32 with the lowest mean
+# merit over §4.8's two configurations, the smaller one on a tie (profiles/r13_tabu_bench.json holds the sweep).
+DEFAULT_TENURE = 16
+
+
 class SearchTables(dict):
     """The candidate tables of a batch as woa_candidates / woa_candidates_replicas return them: a dict of their keys whose
     methods pass its own operands to the search wrappers below (nothing but forwarding: the wrappers do the checking)."""
@@ -1139,6 +1144,9 @@ class SearchTables(dict):
 
     def descend_pairs_shortlist(self, max_sweeps=16, max_rounds=4, max_span=0, max_rank=0, wide=None):
         return self._to(descend_pairs_shortlist_ragged, max_sweeps, max_rounds, max_span, max_rank, wide=wide)
+
+    def descend_tabu(self, max_sweeps=16, max_steps=32, tenure=None, wide=None):
+        return self._to(descend_tabu_ragged, max_sweeps, max_steps, DEFAULT_TENURE if tenure is None else tenure, wide=wide)
 
     def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
         """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
@@ -1387,7 +1395,8 @@ def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max
     """What every descent entry shares: the operand checks, the largest problem, descend_ragged's seven fields (the history with
     ``hist_ld`` columns) and the call of the C entry ``entry`` — the ten leading operands, ``scalars`` (the ints behind max_sweeps,
     none negative), the seven fields, then ``behind``: (key, columns) of the i32 outputs an entry has behind them, in the C order —
-    () a [B] vector, (m,) [B, max_slots, m], None a NULL pointer and no such key.  Returns the dict of all of them."""
+    () a [B] vector, (m,) [B, max_slots, m], None a NULL pointer and no such key, a callable: the output of any dtype it allocates
+    from (B, device).  Returns the dict of all of them."""
     dev = cand.device
     B = prob_ptr.numel() - 1
     n = cand_ptr.numel() - 1
@@ -1395,11 +1404,13 @@ def _descend_launch(entry, who, prob_ptr, cand_ptr, cand, bounds, start_pos, max
         raise GnnpnError(f"{who}: inconsistent operand sizes")
     max_slots, max_cand = _largest_problem(prob_ptr, cand_ptr, max_slots, max_cand)
     fields = _descent_fields(B, max_slots, hist_ld, dev, rows=torch.zeros)          # (a dict in the C order)
-    more = {k: torch.empty(B, *((max_slots, *cols) if cols else ()), dtype=I32, device=dev) for k, cols in behind if cols is not None}
+    more = {k: cols(B, dev) if callable(cols) else torch.empty(B, *((max_slots, *cols) if cols else ()), dtype=I32, device=dev)
+            for k, cols in behind if cols is not None}
     check(getattr(_lib.load(), entry)(
         B, dev_ptr(prob_ptr, I32, "prob_ptr"), n, max_slots, max_cand, dev_ptr(cand_ptr, I32, "cand_ptr"), dev_ptr(cand, F64, "cand"),
         dev_ptr(bounds, F64, "bounds"), dev_ptr(start_pos, I32, "start_pos"), int(max_sweeps), *scalars,
-        *(dev_ptr(t, t.dtype, k) for k, t in fields.items()), *(dev_ptr(more.get(k), I32, k, allow_none=True) for k, _ in behind),
+        *(dev_ptr(t, t.dtype, k) for k, t in fields.items()),
+        *(dev_ptr(more.get(k), more[k].dtype if k in more else I32, k, allow_none=True) for k, _ in behind),
         stream_ptr()), entry)
     return {**fields, **more}
 
@@ -1469,6 +1480,26 @@ def descend_pairs_shortlist_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, 
     return _descend_pairs_launch("gnnpn_descend_pairs_shortlist_ragged_f64", "descend_pairs_shortlist_ragged", prob_ptr, cand_ptr, cand, bounds,
                                  start_pos, max_sweeps, max_rounds, (int(max_span), int(max_rank), int(bool(wide))), max_slots, max_cand,
                                  shortlist=((int(max_rank),) if return_shortlist else None,))
+
+
+def descend_tabu_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_steps=32, tenure=DEFAULT_TENURE, max_slots=None,
+                        max_cand=None, wide=None):
+    """Tabu walk from the one-swap optimum, a ragged batch in ONE launch (gnnpn_descend_tabu_ragged_f64): descend_ragged's sweeps,
+    then up to ``max_steps`` steps that each take the best single swap of the whole composition — the lowest (slot, position) among
+    equals — whether or not it lowers the merit; the position a slot leaves may not come back for ``tenure`` steps unless the swap
+    beats the best merit seen (aspiration).  The best composition seen is the result; where the walk was cut at it, the one-swap
+    sweeps run once more from there.  No admissible swap ends the walk (``stalled``).  Deterministic: no draws.  Operands and
+    ``wide`` as descend_ragged (both forms give the same run; max_cand sizes the tabu table in LDS in both).  Returns descend_ragged's
+    dict with history [B, max_steps] f64 (the best merit after every step; past the last step taken the last such value) plus walk
+    [B, max_steps] f64 (the current merit after every step, NaN past the last), steps, best_step, stalled [B] i32.  max_steps = 0 is
+    descend_ragged's result in every shared field; a problem that is not searched has steps -1."""
+    ld = max(int(max_steps), 1)
+    out = _descend_launch("gnnpn_descend_tabu_ragged_f64", "descend_tabu_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
+                          (int(max_steps), int(tenure), int(bool(wide))), max_slots, max_cand, ld,
+                          (("walk", lambda B, dev: torch.empty(B, ld, dtype=F64, device=dev)), ("steps", ()), ("best_step", ()), ("stalled", ())))
+    out["history"] = out["history"][:, :int(max_steps)]
+    out["walk"] = out["walk"][:, :int(max_steps)]
+    return out
 
 
 def descend_select(res, actions_all, n_slots):

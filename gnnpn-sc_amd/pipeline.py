@@ -143,7 +143,8 @@ def _quality(res, min_cost, dev):
 # Pair-swap descent under its three public names, each the SearchTables method of the same name: what a negative argument is told.
 _PAIR_REFUSAL = {"descend_pairs": "the number of rounds must be >= 0, got {}",
                  "descend_pairs_windowed": "the number of rounds and the span must be >= 0, got {} and {}",
-                 "descend_pairs_shortlist": "the number of rounds, the span and the rank must be >= 0, got {}, {} and {}"}
+                 "descend_pairs_shortlist": "the number of rounds, the span and the rank must be >= 0, got {}, {} and {}",
+                 "descend_tabu": "the number of steps and the tenure must be >= 0, got {} and {}"}       # (the tabu walk: no pairs, the same refusal)
 
 
 def _pair_options(name, *options, who=None):
@@ -226,6 +227,31 @@ def descend_pairs_shortlist(services, batch, out, max_sweeps=16, max_rounds=4, m
 
 
 @torch.no_grad()
+def descend_tabu(services, batch, out, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, reduct=0, min_cost=None, patches=()):
+    """Tabu walk of ``out["actions"]`` on the device (gnnpn_descend_tabu_ragged_f64; all problems in one launch, deterministic: no
+    seeds): ``descend``'s tables and one-swap descent, then up to ``max_steps`` steps that each take the best single swap of the
+    composition whether or not it lowers violate + objFunc, the position a slot leaves barred for ``tenure`` steps unless the swap
+    beats the best merit seen; the best composition seen is the result (polished by the one-swap sweeps where the walk was cut at
+    it).  It leaves one-swap optima that take several coordinated swaps to leave.  Any slot count.  A negative number of steps or
+    tenure raises GnnpnError.  ``ML2PNPipeline.descend_tabu`` is this, as a method.  Returns ops.descend_tabu_ragged's dict
+    (``descend``'s keys, history per step, walk, steps, best_step, stalled) plus n_slots [B] i32 (and quality [B] f64).
+    ``max_steps`` = 0: ``descend``'s result in every shared field."""
+    return _descend_actions(services, batch, out, max_sweeps, ("descend_tabu", max_steps, tenure), reduct, min_cost, patches)
+
+
+@torch.no_grad()
+def descend_starts_tabu(services, batch, starts, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, reduct=0, min_cost=None,
+                        patches=()):
+    """``descend_starts`` whose B * N rows go through the tabu walk (gnnpn_descend_tabu_ragged_f64 in place of the descent launch);
+    the same selection (gnnpn_descend_select_f64, unchanged) picks the winner: history is the winner's walk history, steps,
+    best_step and stalled [B] i32 and walk [B, max_steps] f64 are the winner's (gathered by start_index), steps_all and
+    best_step_all are [B, N] i32.  ``max_steps`` = 0 is ``descend_starts``' result in every shared field.  A negative number of
+    steps or tenure raises GnnpnError.  ``ML2PNPipeline.descend_starts_tabu`` is this, as a method."""
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
+                           _pair_options("descend_tabu", max_steps, tenure, who="descend_starts_tabu"))
+
+
+@torch.no_grad()
 def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
     """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
     [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
@@ -279,7 +305,12 @@ def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patch
     res = ops.descend_select(per_row, all_rows, tabs["n_slots"])        # (the rounds' merits and counters too, where there are any)
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
-    if pairs is not None:
+    if pairs is not None and pairs[0] == "descend_tabu":
+        win = res["start_index"].long()[:, None, None]
+        walk = per_row["walk"].reshape(B, N, -1)
+        res.update(steps_all=per_row["steps"].view(B, N), best_step_all=per_row["best_step"].view(B, N),
+                   walk=walk.gather(1, win.expand(B, 1, walk.shape[2]))[:, 0])
+    elif pairs is not None:
         res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
     return _quality(res, min_cost, all_rows.device)
 
@@ -547,6 +578,18 @@ class ML2PNPipeline:
         """Multi-start pair-swap descent: module-level ``descend_starts_pairs`` (it needs no network).  An extra call."""
         return descend_starts_pairs(services, batch, starts, max_sweeps=max_sweeps, pair_rounds=pair_rounds, reduct=reduct,
                                     min_cost=min_cost, patches=patches)
+
+    def descend_tabu(self, services, batch, out, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, reduct=0, min_cost=None, patches=()):
+        """Tabu walk of ``out["actions"]`` from its one-swap optimum: module-level ``descend_tabu`` (it needs no network).  An extra
+        call: ``run`` / ``capture`` are unchanged."""
+        return descend_tabu(services, batch, out, max_sweeps=max_sweeps, max_steps=max_steps, tenure=tenure, reduct=reduct,
+                            min_cost=min_cost, patches=patches)
+
+    def descend_starts_tabu(self, services, batch, starts, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, reduct=0, min_cost=None,
+                            patches=()):
+        """Multi-start tabu walk: module-level ``descend_starts_tabu`` (it needs no network).  An extra call."""
+        return descend_starts_tabu(services, batch, starts, max_sweeps=max_sweeps, max_steps=max_steps, tenure=tenure, reduct=reduct,
+                                   min_cost=min_cost, patches=patches)
 
     def capture(self, services, batch, warmup=2, decode_impl=0, lds_kb=0, ws=None, paired_start=False, pool=None, write_through=False):
         """Record one whole pass over (services, batch) into a HIP graph and return a callable that

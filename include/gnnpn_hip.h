@@ -910,6 +910,36 @@ int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t* prob_ptr,
                                              double* round_history, int32_t* sweeps, int32_t* moves, int32_t* rounds, int32_t* pair_moves,
                                              int32_t* converged, int32_t* shortlist, void* stream);
 
+/* Tabu walk from the one-swap optimum (csrc/descend.hip).  New: no reference counterpart.  Operands, forms (lane form up to 64 slots
+ * with the table in LDS; workgroup form above that or with `wide`) and the seven leading outputs as gnnpn_descend_ragged_f64.
+ *   Phase 0       that entry's one-swap sweeps (up to max_sweeps).  cur = its composition, best = cur, best_step = 0, and no (slot,
+ *                 position) is tabu.
+ *   Step t        (t = 1 .. max_steps) for every slot j in order and every position c != cur[j] of its list: f = the merit of cur with
+ *                 slot j replaced by c (the one-swap evaluation, the same code).  (j, c) is tabu iff slot j left position c at a
+ *                 step s with s + tenure >= t; it is admissible iff it is not tabu or f < the best merit so far (aspiration,
+ *                 strict).  The admissible move with the smallest f under plain < is taken — the lowest (j, c) among equals, a NaN
+ *                 never — whether or not it is below the current merit; the position the slot leaves becomes tabu through step
+ *                 t + tenure.  best follows under strict <.  No admissible move: stalled = 1, the walk ends, step t is not counted.
+ *   Polish        where the last step taken is the best one (steps > 0, best_step == steps, not stalled) the one-swap sweeps run
+ *                 once more from best (up to max_sweeps; their sweeps and moves are added, their result is the result): the walk
+ *                 was cut at a composition that need not be a one-swap optimum.
+ *   history, walk [B, max(max_steps, 1)] float64: history[t-1] = the best merit after step t, past the last step the last such value
+ *                 (the polish does not enter; max_steps = 0: phase 0's merit); walk[t-1] = the current merit after step t, NaN past
+ *                 the last step.
+ *   steps, best_step, stalled  [B] int32.
+ * max_steps = 0 is gnnpn_descend_ragged_f64's run in every shared field; the result is never above that entry's.  A problem that is
+ * not searched leaves that entry's record (history NaN) plus steps -1, best_step 0, stalled 0, walk NaN.  max_cand is read in BOTH
+ * forms: the tabu table (4 B per candidate of the largest problem) and best (4 B per slot) live in LDS beside the form's own state,
+ * and a problem with more than max_cand candidates is not searched in the workgroup form either.  No atomics, no waits on other
+ * workgroups, every loop bounded by max_steps, max_sweeps, T or a list length.  GNNPN_E_ARG: a negative scalar, max_slots < 1, a
+ * null operand (best_rows may be NULL).  GNNPN_E_UNSUP, nothing launched: max_cand < 1; LDS beyond a CU (the message names slots,
+ * candidates and bytes).  B = 0 returns GNNPN_OK at once. */
+int gnnpn_descend_tabu_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                  const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                  int32_t max_sweeps, int32_t max_steps, int32_t tenure, int32_t wide, double* best_fitness,
+                                  double* start_fitness, int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps,
+                                  int32_t* moves, double* walk, int32_t* steps, int32_t* best_step, int32_t* stalled, void* stream);
+
 /* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
  * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
  * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest

@@ -43,6 +43,13 @@
                                          # --all-starts from every replica, at any slot count and span
                                          # (ML+2PN+multistart+pairs.txt).  Not with --woa
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] --tabu[=STEPS] [--tenure=N] [--samples=N --all-starts]   # tabu walk: from
+                                         # the one-swap optimum take the best single swap, improving or not, for STEPS steps (32
+                                         # unless given), a left position barred for N steps (the measured default unless given), and
+                                         # keep the best composition seen: ./solutions/WOA/<ds>/ML+2PN+tabu.txt (with --all-starts
+                                         # ML+2PN+multistart+tabu.txt), the descent format plus steps / best_step / stalled.
+                                         # Deterministic.  Not with --pairs, --woa or --services
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -221,6 +228,19 @@ def main(argv):
                 print("--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at "
                       "most 64 slots)")
                 return 1
+        tabu = next((a.split("=", 1)[1] if "=" in a else "32" for a in flags if a == "--tabu" or a.startswith("--tabu=")), None)
+        tenure = next((a.split("=", 1)[1] for a in flags if a.startswith("--tenure=")), "" if "--tenure" in flags else None)
+        if tabu is not None:
+            if sweeps is None or not tabu.lstrip("+").isdigit():
+                print("--tabu[=STEPS]: needs --descend[=SWEEPS] and STEPS >= 0 (0: the one-swap descent alone)")
+                return 1
+            if rounds is not None or "--woa" in flags or "--services" in flags:
+                print("--tabu[=STEPS]: not with --pairs, --woa or --services (the walk takes single swaps, and the ES-WOA start and the "
+                      "services artefact take the descent's result)")
+                return 1
+        if tenure is not None and (tabu is None or not tenure.lstrip("+").isdigit()):
+            print("--tenure=N: needs --tabu[=STEPS] and N >= 0 (0: a slot may go straight back)")
+            return 1
         with open(f"./data/{ds}/serviceFeature.data") as f:
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
@@ -246,7 +266,9 @@ def main(argv):
             best["pair_rounds"] = int(rounds)
         if span is not None:                                        # ... at any slot count, over slots at most N apart
             best["pair_span"] = int(span)
-        if "--services" in flags:                                   # the same run, plus ML+2PN+services.txt: which services it found
+        if tabu is not None:                                        # a tabu walk from the one-swap optimum (refused above beside --pairs, --woa)
+            ML2PN.infer_tabu(ds, net, low, high, K, epoch, tabu_steps=int(tabu), tenure=None if tenure is None else int(tenure), **best)
+        elif "--services" in flags:                                 # the same run, plus ML+2PN+services.txt: which services it found
             if top is not None:
                 best["pair_rank"] = int(top)
             ML2PN.infer_services(ds, net, low, high, K, epoch, woa=woa, **best)
