@@ -77,8 +77,8 @@ def infer(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=
     (pipeline.descend_pairs / descend_starts_pairs): ``ML+2PN+pairs.txt`` (``ML+2PN+multistart+pairs.txt`` with all_starts) in
     place of the descent artefact, its format plus the per-problem rounds, pair_moves and converged; ES-WOA starts from its result.
     ``infer_pairs_windowed`` is this run with the pair-swap descent over a window of slots."""
-    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts,
-                  pair_rounds, None)
+    stage = _stage_asked("infer", descend, pair_rounds)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, stage)
 
 
 def infer_pairs_windowed(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1,
@@ -87,10 +87,8 @@ def infer_pairs_windowed(dataset, net, low, high, n_per, epoch=-1, device="cuda:
     ``pair_span`` apart (>= 0; 0: every pair; pipeline.descend_pairs_windowed): ``ML+2PN+pairs.txt`` in ``infer``'s format plus ``span``.
     A function of its own because ``infer``'s parameter list is pinned by the host tests; without ``woa`` and ``all_starts``, which
     stay with the full sweep of at most 64 slots."""
-    if descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0:
-        raise ValueError("ML2PN.infer_pairs_windowed: pair_span needs descend, at least one round and a span >= 0")
-    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, False,
-                  pair_rounds, pair_span)
+    stage = _stage("infer_pairs_windowed", "descend_pairs_windowed", descend, pair_rounds, pair_span)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, False, stage)
 
 
 def infer_pairs_shortlist(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1,
@@ -99,10 +97,8 @@ def infer_pairs_shortlist(dataset, net, low, high, n_per, epoch=-1, device="cuda
     pipeline.descend_pairs_shortlist): ``ML+2PN+pairs.txt`` in ``infer``'s format plus ``span`` and ``top``.  With ``all_starts`` (and
     samples > 1) the descent runs from every replica (pipeline.descend_starts_pairs_shortlist): ``ML+2PN+multistart+pairs.txt``.
     Without ``woa``, whose start takes the full pair sweep of at most 64 slots."""
-    if descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0 or pair_rank is None or pair_rank < 0:
-        raise ValueError("ML2PN.infer_pairs_shortlist: pair_rank needs descend, at least one round, a span >= 0 and a rank >= 0")
-    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts,
-                  pair_rounds, pair_span, pair_rank)
+    stage = _stage("infer_pairs_shortlist", "descend_pairs_shortlist", descend, pair_rounds, pair_span, pair_rank)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts, stage)
 
 
 def infer_tabu(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1, sample_seed=None,
@@ -113,11 +109,8 @@ def infer_tabu(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_
     replica (pipeline.descend_starts_tabu): ``ML+2PN+multistart+tabu.txt``.  Without ``woa`` and without pair sweeps.  A function of
     its own because ``infer``'s parameter list is pinned by the host tests."""
     from . import ops
-    tenure = ops.DEFAULT_TENURE if tenure is None else tenure
-    if descend is None or tabu_steps is None or tabu_steps < 0 or tenure < 0:
-        raise ValueError("ML2PN.infer_tabu: tabu_steps needs descend, a number of steps >= 0 and a tenure >= 0")
-    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts,
-                  None, None, tabu=(int(tabu_steps), int(tenure)))
+    stage = _stage("infer_tabu", "descend_tabu", descend, tabu_steps, ops.DEFAULT_TENURE if tenure is None else tenure)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts, stage)
 
 
 def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
@@ -130,23 +123,69 @@ def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", ba
     count.  Needs ``descend`` or ``woa``.  A function of its own because ``infer``'s parameter list is pinned by the host tests."""
     if descend is None and woa is None:
         raise ValueError("ML2PN.infer_services: needs descend or woa (the services of a searched composition)")
-    if pair_rank is not None and (descend is None or pair_rounds is None or pair_rounds < 1 or pair_span is None or pair_span < 0 or pair_rank < 0):
-        raise ValueError("ML2PN.infer_services: pair_rank needs descend, at least one round, a span >= 0 and a rank >= 0")
-    if pair_span is not None and (descend is None or pair_rounds is None or pair_rounds < 1 or pair_span < 0):
-        raise ValueError("ML2PN.infer_services: pair_span needs descend, at least one round and a span >= 0")
-    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts,
-                  pair_rounds, pair_span, pair_rank, services=True)
+    stage = _stage_asked("infer_services", descend, pair_rounds, pair_span, pair_rank)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, stage,
+                  services=True)
 
 
-def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, pair_rounds,
-           pair_span, pair_rank=None, services=False, tabu=None):
+# What this module adds to a stage of pipeline.STAGES, by its method: the least value of each option; what a call without ``descend``, without
+# an option or with one below its least value is told; the ``infer*`` function that runs it; its part of the artefact's file name; the
+# per-problem flag the artefact lists beside the stage's row_keys; the keys under which it lists the options' values (None: not listed).
+RUNS = {
+    "descend": ((), "", "infer", "", None, ()),
+    "descend_pairs": ((1,), "pair_rounds needs descend and at least one round", "infer", "pairs", "converged", (None,)),
+    "descend_pairs_windowed": ((1, 0), "pair_span needs descend, at least one round and a span >= 0", "infer_pairs_windowed", "pairs",
+                               "converged", (None, "span")),
+    "descend_pairs_shortlist": ((1, 0, 0), "pair_rank needs descend, at least one round, a span >= 0 and a rank >= 0", "infer_pairs_shortlist",
+                                "pairs", "converged", (None, "span", "top")),
+    "descend_tabu": ((0, 0), "tabu_steps needs descend, a number of steps >= 0 and a tenure >= 0", "infer_tabu", "tabu", "stalled",
+                     ("tabu_steps", "tenure"))}
+
+
+def stage_given(pair_rounds=None, pair_span=None, pair_rank=None, tabu_steps=None):
+    """The stage (its name in pipeline.STAGES) that the options given — not None — ask for: the one that takes the last of them."""
+    return ("descend_tabu" if tabu_steps is not None else "descend_pairs_shortlist" if pair_rank is not None else
+            "descend_pairs_windowed" if pair_span is not None else "descend_pairs" if pair_rounds is not None else "descend")
+
+
+def stage_ok(name, descend, *values):
+    """The precondition of a stage with options: ``descend`` is given, and so is every option, none below its least value."""
+    return not values or (descend is not None and all(v is not None and v >= least for v, least in zip(values, RUNS[name][0])))
+
+
+def _stage(who, name, descend, *values):
+    """The stage ``name`` bound to its options' values (pipeline.Stage.bind), or ``who``'s ValueError where ``stage_ok`` says no."""
+    if not stage_ok(name, descend, *values):
+        raise ValueError(f"ML2PN.{who}: {RUNS[name][1]}")
+    from . import pipeline as pl
+    return pl.STAGES[name].bind(*values)
+
+
+def _stage_asked(who, descend, pair_rounds, pair_span=None, pair_rank=None):
+    """``infer``'s and ``infer_services``' stage, ``stage_given``'s; the full pair sweep is ``infer``'s own and refused in its name."""
+    name = stage_given(pair_rounds, pair_span, pair_rank)
+    values = (pair_rounds, pair_span, pair_rank)[:len(RUNS[name][0])]
+    return _stage(who if len(values) > 1 else "infer", name, descend, *values)
+
+
+def search_plan(stage, multi):
+    """How the test quarter goes through a (bound) stage, from every start (``multi``) or from the actions: the pipeline function, its
+    keyword arguments beside max_sweeps, reduct and min_cost, the artefact, the per-problem fields of the result it lists and the
+    settings beside them (no fields: the artefact has no ``extra``).  A pure function: no device is touched."""
+    _, _, _, part, flag, written = RUNS[stage.method]
+    function, *names = stage.starts if multi else (stage.method, *stage.options)
+    parts = [p for p in ("multistart" if multi else "", part) if p] or ["descent"]
+    return (function, dict(zip(names, stage.values)), "ML+2PN+" + "+".join(parts) + ".txt", stage.row_keys + (flag,) if flag else (),
+            {k: v for k, v in zip(written, stage.values) if k})
+
+
+def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, woa, samples, sample_seed, descend, all_starts, stage,
+           services=False):
     import torch
     from . import loadData as ld
     from .pipeline import DeviceBatch, DeviceServices, ML2PNPipeline
     if all_starts and (samples < 2 or descend is None):
         raise ValueError("ML2PN.infer: all_starts needs samples > 1 and descend")
-    if pair_rounds is not None and (descend is None or pair_rounds < 1):
-        raise ValueError("ML2PN.infer: pair_rounds needs descend and at least one round")
     d = f"./data/{dataset}/"
     ds = {k: json.load(open(d + fn)) for k, fn in (
         ("nodefeatures", "nodefeatures.data"), ("edge_indices", "edge_indices.data"), ("labels", "labels.data"),
@@ -200,9 +239,8 @@ def _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision,
     paths = write_artifacts(dataset, epoch, rankings, actions)
     if woa is not None or descend is not None:
         _refine_test_quarter(dataset, ds, pipe, svc, np.concatenate(test_actions) if test_actions else np.zeros((0, T, 8)),
-                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, pair_rounds=pair_rounds, pair_span=pair_span,
-                            pair_rank=pair_rank, action_ids=np.concatenate(test_ids).astype(np.int32) if services and test_ids else None,
-                            services=services, tabu=tabu,
+                            **(woa or {"popSize": 0, "MAX_Iter": 0, "reduct": 0}), descend=descend, stage=stage,
+                            action_ids=np.concatenate(test_ids).astype(np.int32) if services and test_ids else None, services=services,
                             starts=(np.concatenate(test_starts) if test_starts else np.zeros((0, samples, T, 8))) if all_starts else None)
     return paths
 
@@ -216,26 +254,23 @@ def refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, redu
     (pipeline.descend_starts), written as ``ML+2PN+multistart.txt`` instead; ES-WOA then starts from the winner's rows.
     ``pair_rounds`` (>= 1, with ``descend``): pair-swap descent in place of the one-swap descent in each of these, written as
     ``ML+2PN+pairs.txt`` / ``ML+2PN+multistart+pairs.txt`` with the per-problem rounds, pair_moves and converged beside the four keys."""
+    from . import pipeline as pl
     return _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=seed, descend=descend, starts=starts,
-                                pair_rounds=pair_rounds)
+                                stage=pl.ONE_SWAP if pair_rounds is None else pl.PAIRS.bind(pair_rounds))
 
 
-def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, pair_rounds=None,
-                         pair_span=None, pair_rank=None, services=False, action_ids=None, tabu=None):
-    """refine_test_quarter; ``tabu`` = (steps, tenure) (with ``descend``, without pair options and ES-WOA): pipeline.descend_tabu
-    (with ``starts``: descend_starts_tabu) in place of the descent, written as ``ML+2PN+tabu.txt`` / ``ML+2PN+multistart+tabu.txt``
-    with the per-problem steps, best_step and stalled and the two settings.
-    ``pair_span`` (>= 0, with ``pair_rounds``, without ``starts`` and ES-WOA): pipeline.descend_pairs_windowed
-    with that span in place of descend_pairs, and ``ML+2PN+pairs.txt`` gains ``span``.  ``pair_rank`` (>= 0, with ``pair_span``, without
-    ES-WOA): pipeline.descend_pairs_shortlist (with ``starts``: descend_starts_pairs_shortlist) with that span and rank, and the file
-    gains ``top`` too.  ``services``: the last stage's compositions also go to ``ML+2PN+services.txt`` (write_services);
+def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, reduct, seed=None, descend=None, starts=None, stage=None,
+                         services=False, action_ids=None):
+    """refine_test_quarter with any (bound) ``stage`` of pipeline.STAGES in the descent's place (with ``descend``): ``search_plan`` says
+    which pipeline function runs it, from the actions or from ``starts``, into which file and with which ``extra``.  ES-WOA behind it
+    starts from the one-swap descent or, where the stage has rounds, the full pair sweep with that many.
+    ``services``: the last stage's compositions also go to ``ML+2PN+services.txt`` (write_services);
     ``action_ids`` [nTest, T] (with ``starts``: [nTest, N, T]) int32: the rows of the service table the action rows are, or None."""
     import time
     import torch
     from . import loadData as ld
     from .WOA import write_ml2pn_woa
     from . import pipeline as pl
-    counters = lambda r: {k: r[k].cpu().tolist() for k in ("rounds", "pair_moves", "converged")}      # noqa: E731
     dev = svc.qos.device
     P = len(ds["nodefeatures"])
     first = P // 4 * 3
@@ -249,31 +284,14 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
     # each file books the time of its own stages: descent.txt the tables + descent, WOA.txt the tables (+ descent) + ES-WOA.  With
     # both, descent therefore runs twice (it is deterministic and costs about a hundredth of the ES-WOA run beside it).
     if descend is not None:
-        multi, pairs = starts is not None, pair_rounds is not None        # from every start or the actions; pair-swap or one-swap
-        name = {(False, False): "ML+2PN+descent.txt", (False, True): "ML+2PN+pairs.txt", (True, False): "ML+2PN+multistart.txt",
-                (True, True): "ML+2PN+multistart+pairs.txt"}[multi, pairs]
-        kw = {"max_sweeps": descend, "reduct": reduct, "min_cost": min_cost}
+        multi = starts is not None                   # from every start or the actions
+        function, options, name, fields, settings = search_plan(stage, multi)
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        # the function, chosen once by how many of (rounds, span, rank) it takes: each option needs the one before it, and a span
-        # without a rank is not for starts
-        given = 3 if pair_rank is not None else 2 if pair_span is not None and not multi else 1 if pairs else 0
-        search = {(False, 0): pl.descend, (False, 1): pl.descend_pairs, (False, 2): pl.descend_pairs_windowed,
-                  (False, 3): pl.descend_pairs_shortlist, (True, 0): pl.descend_starts, (True, 1): pl.descend_starts_pairs,
-                  (True, 3): pl.descend_starts_pairs_shortlist}[multi, given]
-        names = ("pair_rounds", "pair_span", "pair_rank") if multi else ("max_rounds", "max_span", "max_rank")
-        kw.update(zip(names[:given], (pair_rounds, pair_span, pair_rank)))
-        if tabu is not None:                         # the tabu walk in the descent's place: its own function, file and counters
-            search = pl.descend_starts_tabu if multi else pl.descend_tabu
-            name = "ML+2PN+multistart+tabu.txt" if multi else "ML+2PN+tabu.txt"
-            kw.update(max_steps=tabu[0], tenure=tabu[1])
-        res = search(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev) if multi else out, **kw)
+        res = getattr(pl, function)(svc, batch, torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float64)).to(dev) if multi else out,
+                                    max_sweeps=descend, reduct=reduct, min_cost=min_cost, **options)
         quality = res["quality"].cpu().tolist()
-        if tabu is not None:
-            extra = {**{k: res[k].cpu().tolist() for k in ("steps", "best_step", "stalled")}, "tabu_steps": tabu[0], "tenure": tabu[1]}
-        else:
-            extra = ({**counters(res), **({} if pair_span is None else {"span": pair_span}),
-                      **({} if pair_rank is None else {"top": pair_rank})}) if pairs else None
+        extra = {**{k: res[k].cpu().tolist() for k in fields}, **settings} if fields else None
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first, name=name, extra=extra)
         if multi:
             if services and action_ids is not None:  # the winner's ids, as its rows
@@ -288,7 +306,7 @@ def _refine_test_quarter(dataset, ds, pipe, svc, actions, popSize, MAX_Iter, red
             res = pipe.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost)
         else:
             res = pl.refine(svc, batch, out, popSize, MAX_Iter, reduct=reduct, seeds=seeds, min_cost=min_cost, descend=descend,
-                            pair_rounds=pair_rounds or 0)
+                            pair_rounds=dict(zip(stage.options, stage.values)).get("max_rounds", 0))
         quality = res["quality"].cpu().tolist()
         written = write_ml2pn_woa(dataset, quality, (time.time() - t0) / max(n, 1), first)
     if services:

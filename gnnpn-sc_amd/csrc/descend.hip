@@ -104,7 +104,8 @@ constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halv
 
 // Where a problem's state lives: the columns of cur (L.col0, col1, L.col2, L.col3), the base / len tables and the bounds in LDS;
 // cur, in LDS or the problem's best_pos row; the candidate table's LDS copy (lane form); red / cnt / sib (workgroup form).  The
-// shortlist builds add mer / rk (one list's single-swap merits and their ranks) and list (every slot's shortlist), all in LDS.
+// shortlist builds add mer / rk (one list's single-swap merits and their ranks) and list (every slot's shortlist), the tabu builds
+// expire and best, all in LDS.  A build fills what it uses (lane_carve, wide_carve) and reads nothing else.
 struct DescendMem {
     WideLds L;
     double* col1;      // [T] column 1 (np.min)
@@ -115,20 +116,63 @@ struct DescendMem {
     int* rk;           // [max_cand] ... and its rank in the (merit, position) order
     int* list;         // [T][rank] ... every slot's shortlist, positions ascending, -1 past its length
     int rank;          // row length of list: min(max_rank, max_cand)
+    int* expire;       // [max_cand] tabu builds: candidate base[j] + c may not return to slot j at steps t <= expire (0: never left)
+    int* best;         // [T] ... the best composition the walk has seen
 };
 
-// The lane form's carve-up (descend_lds_bytes sizes it): the four columns of cur [4][64] (figure_of_merit's layout), bounds [4],
-// base / len / cur [64] each, the problem's candidate table [n_cand][4].
-__device__ __forceinline__ DescendMem lane_mem(unsigned char* lds_raw) {
-    double* col = reinterpret_cast<double*>(lds_raw);
+// The four builds of each form, by what they search with: it decides the sibling rows and what comes on top of the search state.
+enum class Build { one_swap, pairs, shortlist, tabu };
+
+// The ints on top of a form's tables: rk [max_cand] and list [slots][rank] (shortlist), expire [max_cand] and best [slots] (tabu).
+__host__ __device__ __forceinline__ int* carve_ints(DescendMem& M, int* at, Build build, int slots, int max_cand, int rank) {
+    if (build == Build::shortlist) {
+        M.rk = at;
+        M.list = M.rk + max_cand;
+        M.rank = rank;
+        return M.list + (size_t)slots * rank;
+    }
+    if (build == Build::tabu) {
+        M.expire = at;
+        M.best = M.expire + max_cand;
+        return M.best + slots;
+    }
+    return at;
+}
+
+// The LDS layout of a problem, stated once per form: the kernels carve `raw` with it, and the host asks for the bytes it returns
+// on a null base with the launch's maxima (descend_lds_bytes), so the two cannot part.
+// Lane form: the four columns of cur [4][64] (figure_of_merit's layout), bounds [4], base / len / cur [64] each, the candidate table
+// [max_cand][4]; behind it mer [max_cand] f64, rk and list [max_slots][rank] (shortlist), or expire and best [64] (tabu).
+__host__ __device__ __forceinline__ size_t lane_carve(DescendMem& M, unsigned char* raw, Build build, int max_slots, int max_cand, int rank) {
+    double* col = reinterpret_cast<double*>(raw);
     int* tab = reinterpret_cast<int*>(col + 260);
-    DescendMem M;
     M.L = WideLds{col, col + 128, col + 192, nullptr, nullptr, tab, tab + 64, col + 256};
     M.col1 = col + 64;
     M.sib = nullptr;
     M.cur = tab + 128;
     M.table = reinterpret_cast<double*>(tab + 192);
-    return M;
+    double* top = M.table + (size_t)max_cand * 4;
+    if (build == Build::shortlist) {
+        M.mer = top;
+        top += max_cand;
+    }
+    int* end = carve_ints(M, reinterpret_cast<int*>(top), build, build == Build::tabu ? 64 : max_slots, max_cand, rank);
+    return reinterpret_cast<unsigned char*>(end) - raw;
+}
+
+// Workgroup form, T slots (the problem's own in a kernel, max_slots on the host): WideLds with column 1 [T], the sibling sums
+// [1 | 3][SIB_MAX] (one row for the one-swap sweeps, three where there is a pair sweep) and, shortlist, mer [max_cand] among its
+// doubles; behind its base / len tables rk and list [T][rank] (shortlist), or expire and best [T] (tabu).  cur is the problem's
+// best_pos row, the table stays in global memory.
+__host__ __device__ __forceinline__ size_t wide_carve(DescendMem& M, unsigned char* raw, Build build, int T, int max_cand, int rank, int32_t* cur) {
+    const int sibs = (build == Build::pairs || build == Build::shortlist ? 3 : 1) * SIB_MAX;
+    M.col1 = M.L.carve(raw, T, (size_t)T + sibs + (build == Build::shortlist ? max_cand : 0));
+    M.sib = M.col1 + T;
+    if (build == Build::shortlist) M.mer = M.sib + sibs;
+    M.cur = cur;
+    M.table = nullptr;
+    int* end = carve_ints(M, M.L.len + T, build, T, max_cand, rank);
+    return reinterpret_cast<unsigned char*>(end) - raw;
 }
 
 // A problem's search state between the three parts below, thread-uniform: its slot count, its candidate table (LDS or global), the
@@ -655,12 +699,6 @@ __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const
 }
 
 // ---- tabu walk: leave the one-swap optimum by the best single swap, improving or not ----------------------------------------------------
-// What the walk keeps beside DescendMem, both in LDS: expire [n_cand] (candidate base[j] + c may not return to slot j at steps
-// t <= expire; 0 = never left) and best [T], the best composition seen.
-struct TabuMem {
-    int* expire;
-    int* best;
-};
 struct TabuOut {
     double* best_fitness; double* start_fitness; int32_t* best_pos; double* history; int32_t* sweeps; int32_t* moves;
     double* walk; int32_t* steps; int32_t* best_step; int32_t* stalled;
@@ -721,7 +759,7 @@ __device__ __forceinline__ void tabu_step(const DescendMem& M, const DescendStat
 // history[t - 1] = the best merit after step t (past the last step the last such value, before the polish; max_steps = 0: phase
 // 0's merit), walk[t - 1] = the current merit after step t, NaN past the last step.
 template <int NT, bool TABLE_IN_LDS>
-__device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const TabuMem& K, const Shape& sh, const int32_t* __restrict__ cand_ptr,
+__device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
                                                      const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                      const int32_t* __restrict__ start_pos, int32_t max_sweeps, int32_t max_steps,
                                                      int32_t tenure, const TabuOut& o) {
@@ -744,17 +782,17 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
     const int T = S.T;
     const double* cand = S.cand;
     const int n_cand = L.base[T - 1] + L.len[T - 1];               // the lists are contiguous (descend_load checked them)
-    for (int i = tid; i < n_cand; i += NT) K.expire[i] = 0;
+    for (int i = tid; i < n_cand; i += NT) M.expire[i] = 0;
     __syncthreads();
     int sweeps = 0, moves = 0, steps = 0, best_step = 0, stalled = 0;
     bool settled = false;
     one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
     double best_f = S.fit;
-    for (int j = tid; j < T; j += NT) K.best[j] = M.cur[j];
+    for (int j = tid; j < T; j += NT) M.best[j] = M.cur[j];
     for (int t = 1; t <= max_steps; ++t) {
         double f;
         int key;
-        tabu_step<NT>(M, S, K.expire, t, best_f, f, key);
+        tabu_step<NT>(M, S, M.expire, t, best_f, f, key);
         if (key == INT_MAX) {                                         // workgroup-uniform
             stalled = 1;
             break;
@@ -763,7 +801,7 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
             const int c = key - L.base[j];
             if (c < 0 || c >= L.len[j]) continue;
             const double* r = cand + (size_t)key * 4;
-            K.expire[L.base[j] + M.cur[j]] = tenure > INT_MAX - t ? INT_MAX : t + tenure;
+            M.expire[L.base[j] + M.cur[j]] = tenure > INT_MAX - t ? INT_MAX : t + tenure;
             M.cur[j] = c;
             L.col0[j] = r[0];
             M.col1[j] = r[1];
@@ -777,7 +815,7 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
         if (f < best_f) {
             best_f = f;
             best_step = t;
-            for (int j = tid; j < T; j += NT) K.best[j] = M.cur[j];
+            for (int j = tid; j < T; j += NT) M.best[j] = M.cur[j];
         }
         if (tid == 0) {
             hist[t - 1] = best_f;
@@ -791,7 +829,7 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
     __syncthreads();                                                  // best stands
     if (best_step < steps) {                                          // the walk went on past its best: back to it
         for (int j = tid; j < T; j += NT) {
-            const int c = K.best[j];
+            const int c = M.best[j];
             const double* r = cand + (size_t)(L.base[j] + c) * 4;
             M.cur[j] = c;
             L.col0[j] = r[0];
@@ -816,9 +854,13 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
 }
 }  // namespace
 
-// ---- lane form: one wavefront per problem (<= 64 slots) --------------------------------------------------------------------------------
-// LDS: the four columns of cur [4][64] (figure_of_merit's layout), bounds [4], base / len / cur [64] each, the problem's candidate
-// table [n_cand][4].
+// ---- lane form: one wavefront per problem (<= 64 slots), LDS as lane_carve lays it out --------------------------------------------------
+__device__ __forceinline__ DescendMem lane_mem(unsigned char* lds_raw, Build build, const Shape& sh, int rank = 0) {
+    DescendMem M;
+    lane_carve(M, lds_raw, build, sh.stride, sh.max_cand, rank);
+    return M;
+}
+
 __global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
                                                      const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
                                                      int32_t max_sweeps, double* __restrict__ best_fitness,
@@ -826,49 +868,38 @@ __global__ __launch_bounds__(64) void descend_kernel(Shape sh, const int32_t* __
                                                      double* __restrict__ history, int32_t* __restrict__ sweeps_out,
                                                      int32_t* __restrict__ moves_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    descend_problem<64, true>(lane_mem(lds_raw), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness,
-                              best_pos_out, history, sweeps_out, moves_out);
+    descend_problem<64, true>(lane_mem(lds_raw, Build::one_swap, sh), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness,
+                              start_fitness, best_pos_out, history, sweeps_out, moves_out);
 }
 
-// ---- pair-swap descent, lane form: one wavefront per problem (<= 64 slots), descend_kernel's LDS layout ----------------------------------
+// ---- pair-swap descent, lane form: one wavefront per problem (<= 64 slots) ---------------------------------------------------------------
 // No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths.
 __global__ __launch_bounds__(64) void descend_pairs_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
                                                            const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
                                                            int32_t max_sweeps, int32_t max_rounds, int32_t max_span, PairOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    descend_pairs_problem<64, true>(lane_mem(lds_raw), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
+    descend_pairs_problem<64, true>(lane_mem(lds_raw, Build::pairs, sh), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds,
+                                    max_span, o);
 }
 
 // ---- pair-swap descent over shortlists, lane form: descend_pairs_kernel with the shortlist pass before every pair sweep -------------------
-// LDS: descend_kernel's layout, then mer [max_cand] f64, rk [max_cand] i32, list [stride][rank] i32 (descend_short_lds_bytes).
 // No atomics, no waits on other workgroups; loops bounded by max_rounds, max_sweeps, T, list lengths, max_rank.
 __global__ __launch_bounds__(64) void descend_pairs_shortlist_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                                      const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                                      const int32_t* __restrict__ start_pos, int32_t max_sweeps,
                                                                      int32_t max_rounds, int32_t max_span, int32_t rank, PairOut o, ShortOut so) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    DescendMem M = lane_mem(lds_raw);
-    M.mer = M.table + (size_t)sh.max_cand * 4;
-    M.rk = reinterpret_cast<int*>(M.mer + sh.max_cand);
-    M.list = M.rk + sh.max_cand;
-    M.rank = rank;
-    descend_pairs_problem<64, true, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o, so);
+    descend_pairs_problem<64, true, true>(lane_mem(lds_raw, Build::shortlist, sh, rank), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps,
+                                          max_rounds, max_span, o, so);
 }
 
-// The workgroup form's carve-up (descend_wide_lds_bytes sizes it): WideLds, column 1, `sib_rows` rows of SIB_MAX sibling sums (one
-// for the one-swap sweeps, three for the pair sweep); cur is the problem's best_pos row, the table stays in global memory.
-__device__ __forceinline__ DescendMem wide_mem(unsigned char* lds_raw, int T, int sib_rows, int32_t* cur) {
+// ---- workgroup form: any slot count, 256 threads per problem, LDS as wide_carve lays it out for the problem's own slot count --------------
+__device__ __forceinline__ DescendMem wide_mem(unsigned char* lds_raw, Build build, const Shape& sh, int32_t* best_pos, int rank = 0) {
     DescendMem M;
-    M.col1 = M.L.carve(lds_raw, T, T + sib_rows * SIB_MAX);
-    M.sib = M.col1 + T;
-    M.cur = cur;
-    M.table = nullptr;
+    wide_carve(M, lds_raw, build, sh.count(blockIdx.x), sh.max_cand, rank, best_pos + sh.out_row(blockIdx.x));
     return M;
 }
 
-// ---- workgroup form: any slot count, 256 threads per problem ----------------------------------------------------------------------------
-// The columns of cur and the base / len tables live in LDS (WideLds, plus column 1 and the sibling sums), cur itself is the problem's
-// best_pos row, the candidate table stays in global memory.
 __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                            const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                            const int32_t* __restrict__ start_pos, int32_t max_sweeps,
@@ -876,7 +907,7 @@ __global__ __launch_bounds__(WNT) void descend_wide_kernel(Shape sh, const int32
                                                            int32_t* __restrict__ best_pos_out, double* __restrict__ history,
                                                            int32_t* __restrict__ sweeps_out, int32_t* __restrict__ moves_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const DescendMem M = wide_mem(lds_raw, sh.count(blockIdx.x), 1, best_pos_out + sh.out_row(blockIdx.x));
+    const DescendMem M = wide_mem(lds_raw, Build::one_swap, sh, best_pos_out);
     descend_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, best_fitness, start_fitness, best_pos_out,
                                 history, sweeps_out, moves_out);
 }
@@ -887,12 +918,11 @@ __global__ __launch_bounds__(WNT) void descend_pairs_wide_kernel(Shape sh, const
                                                                  const int32_t* __restrict__ start_pos, int32_t max_sweeps,
                                                                  int32_t max_rounds, int32_t max_span, PairOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const DescendMem M = wide_mem(lds_raw, sh.count(blockIdx.x), 3, o.best_pos + sh.out_row(blockIdx.x));
+    const DescendMem M = wide_mem(lds_raw, Build::pairs, sh, o.best_pos);
     descend_pairs_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o);
 }
 
-// Pair-swap descent over shortlists, workgroup form.  LDS: descend_pairs_wide_kernel's, with mer [max_cand] f64 behind the sibling
-// sums and rk [max_cand], list [T][rank] i32 behind the base / len tables (descend_short_lds_bytes).
+// Pair-swap descent over shortlists, workgroup form.
 __global__ __launch_bounds__(WNT) void descend_pairs_shortlist_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                                            const double* __restrict__ cand_g,
                                                                            const double* __restrict__ bounds_g,
@@ -900,57 +930,80 @@ __global__ __launch_bounds__(WNT) void descend_pairs_shortlist_wide_kernel(Shape
                                                                            int32_t max_rounds, int32_t max_span, int32_t rank, PairOut o,
                                                                            ShortOut so) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int T = sh.count(blockIdx.x);
-    DescendMem M;
-    M.col1 = M.L.carve(lds_raw, T, T + 3 * SIB_MAX + sh.max_cand);
-    M.sib = M.col1 + T;
-    M.mer = M.sib + 3 * SIB_MAX;
-    M.cur = o.best_pos + sh.out_row(blockIdx.x);
-    M.table = nullptr;
-    M.rk = M.L.len + T;
-    M.list = M.rk + sh.max_cand;
-    M.rank = rank;
+    const DescendMem M = wide_mem(lds_raw, Build::shortlist, sh, o.best_pos, rank);
     descend_pairs_problem<WNT, false, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_rounds, max_span, o, so);
 }
 
-// ---- tabu walk, lane form: descend_kernel's LDS layout, then expire [max_cand] and best [64] i32 (descend_tabu_lds_bytes) ----------------
+// ---- tabu walk, lane form ----------------------------------------------------------------------------------------------------------------
 // No atomics, no waits on other workgroups; loops bounded by max_steps, max_sweeps, T, list lengths.
 __global__ __launch_bounds__(64) void descend_tabu_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
                                                           const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
                                                           int32_t max_sweeps, int32_t max_steps, int32_t tenure, TabuOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const DescendMem M = lane_mem(lds_raw);
-    TabuMem K;
-    K.expire = reinterpret_cast<int*>(M.table + (size_t)sh.max_cand * 4);
-    K.best = K.expire + sh.max_cand;
-    descend_tabu_problem<64, true>(M, K, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
+    descend_tabu_problem<64, true>(lane_mem(lds_raw, Build::tabu, sh), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
 }
 
-// Tabu walk, workgroup form: descend_wide_kernel's LDS layout with expire [max_cand] and best [T] i32 behind the base / len tables.
+// Tabu walk, workgroup form.
 __global__ __launch_bounds__(WNT) void descend_tabu_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
                                                                 const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                                 const int32_t* __restrict__ start_pos, int32_t max_sweeps,
                                                                 int32_t max_steps, int32_t tenure, TabuOut o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    const int T = sh.count(blockIdx.x);
-    const DescendMem M = wide_mem(lds_raw, T, 1, o.best_pos + sh.out_row(blockIdx.x));
-    TabuMem K;
-    K.expire = M.L.len + T;
-    K.best = K.expire + sh.max_cand;
-    descend_tabu_problem<WNT, false>(M, K, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
+    const DescendMem M = wide_mem(lds_raw, Build::tabu, sh, o.best_pos);
+    descend_tabu_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
 }
 
-// LDS bytes one problem needs (host side).  Lane form: the columns + bounds + base / len / cur + its candidate table.  Workgroup
-// form: four columns, red[8] + bounds[4] + sib[sib_rows][SIB_MAX], cnt[4] + base / len tables.
-static size_t descend_lds_bytes(int n_cand) { return (256 + 4 + (size_t)n_cand * 4) * sizeof(double) + 3 * 64 * sizeof(int); }
-static size_t descend_wide_lds_bytes(int T, int sib_rows = 1) {
-    return ((size_t)4 * T + 12 + (size_t)sib_rows * SIB_MAX) * sizeof(double) + ((size_t)2 * T + 4) * sizeof(int);
+// LDS bytes one problem needs (host side): what the form's carve-up takes from a null base with the launch's maxima.
+static size_t descend_lds_bytes(bool use_wide, Build build, int max_slots, int max_cand, int rank) {
+    DescendMem M;
+    return use_wide ? wide_carve(M, nullptr, build, max_slots, max_cand, rank, nullptr) : lane_carve(M, nullptr, build, max_slots, max_cand, rank);
 }
 
-// The shortlist builds: the same, plus mer [max_cand] f64, rk [max_cand] i32 and list [max_slots][rank] i32.
-static size_t descend_short_lds_bytes(bool use_wide, int max_slots, int max_cand, int rank) {
-    return (use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand)) + (size_t)max_cand * (sizeof(double) + sizeof(int)) +
-           (size_t)max_slots * rank * sizeof(int);
+// The operands every descent entry has, under their names in include/gnnpn_hip.h (wide: 0 where the entry has none).
+struct DescendArgs {
+    int32_t B; const int32_t* prob_ptr; int32_t n_lists, max_slots, max_cand; const int32_t* cand_ptr; const double* cand;
+    const double* bounds; const int32_t* start_pos; int32_t max_sweeps, wide; double* best_rows; void* stream;
+};
+
+// The five descent entries: their argument checks (`who` names the entry in every message; options_ok / operands_given: the entry's
+// own options are >= 0, its own outputs not NULL) and the one launch of `build` — `lane` or `wide`, whose parameters behind
+// max_sweeps are `rest`.  Lane form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots
+// slots within a CU.  The shortlist and tabu builds size buffers of their own by max_cand (and `rank`, the shortlists' row) in both forms.
+template <typename... P, typename... A>
+static int descend_entry(const char* who, Build build, bool lane_only, const DescendArgs& a, int rank, bool options_ok, bool operands_given,
+                         void (*lane)(P...), void (*wide)(P...), const A&... rest) {
+    GNNPN_REQUIRE(a.B >= 0 && a.n_lists >= 0 && a.max_sweeps >= 0 && options_ok && a.max_slots >= 1, "%s: bad argument", who);
+    if (a.B == 0) return GNNPN_OK;
+    GNNPN_REQUIRE(a.prob_ptr && a.cand_ptr && a.cand && a.bounds && a.start_pos && operands_given, "%s: null operand", who);
+    if (lane_only && a.max_slots > 64)
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
+                   "gnnpn_descend_ragged_f64 descends larger problems by single swaps", who, a.max_slots);
+    const bool use_wide = a.wide || a.max_slots > 64, own = build == Build::shortlist || build == Build::tabu;
+    const int max_slots = a.max_slots, max_cand = a.max_cand;
+    if (max_cand < 1 && (own || !use_wide)) {
+        if (build == Build::one_swap) GNNPN_FAIL(GNNPN_E_ARG, "%s: max_cand must be >= 1 for the lane form", who);
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes %s in LDS)", who,
+                   build == Build::pairs ? "the table" : build == Build::shortlist ? "the merit buffer, and in the lane form the table,"
+                                                                                   : "the tabu table, and in the lane form the candidate table,");
+    }
+    const size_t lds = descend_lds_bytes(use_wide, build, max_slots, max_cand, rank);
+    auto too_large = [&]() -> int {
+        const char* hint = use_wide || build == Build::pairs ? "" : "; wide=1 keeps the candidate table in global memory";
+        if (build == Build::shortlist)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
+                       max_slots, max_cand, rank, hint);
+        if (build == Build::tabu)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates) exceed a CU (160 KB)%s", who, lds, max_slots,
+                       max_cand, hint);
+        if (use_wide)
+            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", who, max_slots, lds);
+        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d candidates) exceed a CU%s", who, lds, max_cand, hint);
+    };
+    char entry[80];
+    snprintf(entry, sizeof(entry), "%s_f64%s", who, use_wide ? " (workgroup form)" : "");
+    const Shape sh{a.prob_ptr, 0, max_slots, use_wide ? max_slots : 64, own || !use_wide ? max_cand : 0, a.n_lists, a.best_rows};
+    return search_launch(lds, too_large, use_wide ? wide : lane, a.B, use_wide ? WNT : 64, a.stream, entry, sh, a.cand_ptr, a.cand, a.bounds,
+                         a.start_pos, a.max_sweeps, rest...);
 }
 
 extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
@@ -958,110 +1011,41 @@ extern "C" int gnnpn_descend_ragged_f64(int32_t B, const int32_t* prob_ptr, int3
                                         int32_t max_sweeps, int32_t wide, double* best_fitness, double* start_fitness,
                                         int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps, int32_t* moves,
                                         void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_slots >= 1, "descend_ragged: bad argument");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && history && sweeps &&
-                  moves, "descend_ragged: null operand");
-    const bool use_wide = wide || max_slots > 64;
-    if (!use_wide) GNNPN_REQUIRE(max_cand >= 1, "descend_ragged: max_cand must be >= 1 for the lane form");
-    const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots) : descend_lds_bytes(max_cand);
-    auto too_large = [&]() -> int {
-        if (use_wide)
-            GNNPN_FAIL(GNNPN_E_UNSUP, "descend_ragged: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", max_slots, lds);
-        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_ragged: %zu B of LDS per problem (%d candidates) exceed a CU; wide=1 keeps the candidate "
-                   "table in global memory", lds, max_cand);
-    };
-    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, n_lists, best_rows};
-    return search_launch(lds, too_large, use_wide ? descend_wide_kernel : descend_kernel, B, use_wide ? WNT : 64, stream,
-                         use_wide ? "descend_ragged_f64 (workgroup form)" : "descend_ragged_f64", sh, cand_ptr, cand, bounds, start_pos,
-                         max_sweeps, best_fitness, start_fitness, best_pos, history, sweeps, moves);
+    return descend_entry("descend_ragged", Build::one_swap, false,
+                         {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, 0, true,
+                         best_fitness && start_fitness && best_pos && history && sweeps && moves, descend_kernel, descend_wide_kernel,
+                         best_fitness, start_fitness, best_pos, history, sweeps, moves);
 }
 
-// The tabu builds: the same, plus expire [max_cand] i32 and best [64 | max_slots] i32.
-static size_t descend_tabu_lds_bytes(bool use_wide, int max_slots, int max_cand) {
-    return (use_wide ? descend_wide_lds_bytes(max_slots) : descend_lds_bytes(max_cand)) +
-           ((size_t)max_cand + (use_wide ? max_slots : 64)) * sizeof(int);
-}
-
-// Tabu walk (new: no reference counterpart).  Argument checks as descend_pairs_entry's; max_cand >= 1 in both forms: it sizes expire.
+// Tabu walk (new: no reference counterpart).  max_cand >= 1 in both forms: it sizes expire.
 extern "C" int gnnpn_descend_tabu_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
                                              const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
                                              int32_t max_sweeps, int32_t max_steps, int32_t tenure, int32_t wide, double* best_fitness,
                                              double* start_fitness, int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps,
                                              int32_t* moves, double* walk, int32_t* steps, int32_t* best_step, int32_t* stalled,
                                              void* stream) {
-    GNNPN_REQUIRE(B >= 0 && n_lists >= 0 && max_sweeps >= 0 && max_steps >= 0 && tenure >= 0 && max_slots >= 1,
-                  "descend_tabu_ragged: bad argument");
-    if (B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(prob_ptr && cand_ptr && cand && bounds && start_pos && best_fitness && start_fitness && best_pos && history && sweeps &&
-                  moves && walk && steps && best_step && stalled, "descend_tabu_ragged: null operand");
-    if (max_cand < 1)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_tabu_ragged: max_cand must be >= 1 (it sizes the tabu table, and in the lane form the candidate "
-                   "table, in LDS)");
-    const bool use_wide = wide || max_slots > 64;
-    const size_t lds = descend_tabu_lds_bytes(use_wide, max_slots, max_cand);
-    auto too_large = [&]() -> int {
-        GNNPN_FAIL(GNNPN_E_UNSUP, "descend_tabu_ragged: %zu B of LDS per problem (%d slots, %d candidates) exceed a CU (160 KB)%s", lds,
-                   max_slots, max_cand, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
-    };
-    const Shape sh{prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, n_lists, best_rows};
     const TabuOut o{best_fitness, start_fitness, best_pos, history, sweeps, moves, walk, steps, best_step, stalled};
-    return search_launch(lds, too_large, use_wide ? descend_tabu_wide_kernel : descend_tabu_kernel, B, use_wide ? WNT : 64, stream,
-                         use_wide ? "descend_tabu_ragged_f64 (workgroup form)" : "descend_tabu_ragged_f64", sh, cand_ptr, cand, bounds,
-                         start_pos, max_sweeps, max_steps, tenure, o);
+    return descend_entry("descend_tabu_ragged", Build::tabu, false,
+                         {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, 0,
+                         max_steps >= 0 && tenure >= 0,
+                         best_fitness && start_fitness && best_pos && history && sweeps && moves && walk && steps && best_step && stalled,
+                         descend_tabu_kernel, descend_tabu_wide_kernel, max_steps, tenure, o);
 }
 
-// The arguments of a pair entry: the shortlist entry's parameter list in include/gnnpn_hip.h, name for name and in its order, so an
-// entry passes its own list through as it stands, with 0 / NULL where it has no span, rank, wide or shortlist.
-struct PairArgs {
-    int32_t B; const int32_t* prob_ptr; int32_t n_lists, max_slots, max_cand; const int32_t* cand_ptr; const double* cand;
-    const double* bounds; const int32_t* start_pos; int32_t max_sweeps, max_rounds, max_span, max_rank, wide;
-    double* best_fitness; double* start_fitness; int32_t* best_pos; double* best_rows; double* round_history;
-    int32_t* sweeps; int32_t* moves; int32_t* rounds; int32_t* pair_moves; int32_t* converged; int32_t* shortlist; void* stream;
-};
-
-// The three pair entries: their argument checks (`who` names the entry in every message) and the one launch of pair-swap descent.
-// Lane form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots slots within a CU.
-// max_rank > 0: the shortlist builds, whose merit buffer, rank buffer and lists come on top in both forms; they run with the rank
-// clamped to max_cand (no list is longer than its problem's table).  max_rank = 0: the same launch from every entry, nothing extra.
-static int descend_pairs_entry(const char* who, bool lane_only, const PairArgs& a) {
-    GNNPN_REQUIRE(a.B >= 0 && a.n_lists >= 0 && a.max_sweeps >= 0 && a.max_rounds >= 0 && a.max_span >= 0 && a.max_rank >= 0 &&
-                  a.max_slots >= 1, "%s: bad argument", who);
-    if (a.B == 0) return GNNPN_OK;
-    GNNPN_REQUIRE(a.prob_ptr && a.cand_ptr && a.cand && a.bounds && a.start_pos && a.best_fitness && a.start_fitness && a.best_pos &&
-                  a.round_history && a.sweeps && a.moves && a.rounds && a.pair_moves && a.converged, "%s: null operand", who);
-    if (lane_only && a.max_slots > 64)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
-                   "gnnpn_descend_ragged_f64 descends larger problems by single swaps", who, a.max_slots);
-    const PairOut o{a.best_fitness, a.start_fitness, a.best_pos, a.round_history, a.sweeps, a.moves, a.rounds, a.pair_moves, a.converged};
-    const bool use_wide = a.wide || a.max_slots > 64;
-    const int max_slots = a.max_slots, max_cand = a.max_cand, nt = use_wide ? WNT : 64;
-    char entry[80];
-    snprintf(entry, sizeof(entry), "%s_f64%s", who, use_wide ? " (workgroup form)" : "");
-    if (a.max_rank == 0) {
-        if (!use_wide && max_cand < 1) GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the table in LDS)", who);
-        const size_t lds = use_wide ? descend_wide_lds_bytes(max_slots, 3) : descend_lds_bytes(max_cand);
-        auto too_large = [&]() -> int {
-            if (use_wide)
-                GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots need %zu B of LDS for the four QoS columns (a CU has 160 KB)", who, max_slots, lds);
-            GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d candidates) exceed a CU", who, lds, max_cand);
-        };
-        const Shape sh{a.prob_ptr, 0, max_slots, use_wide ? max_slots : 64, use_wide ? 0 : max_cand, a.n_lists, a.best_rows};
-        return search_launch(lds, too_large, use_wide ? descend_pairs_wide_kernel : descend_pairs_kernel, a.B, nt, a.stream, entry, sh,
-                             a.cand_ptr, a.cand, a.bounds, a.start_pos, a.max_sweeps, a.max_rounds, a.max_span, o);
-    }
-    if (max_cand < 1)
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes the merit buffer, and in the lane form the table, in LDS)", who);
-    const int rank = a.max_rank < max_cand ? a.max_rank : max_cand;
-    const size_t lds = descend_short_lds_bytes(use_wide, max_slots, max_cand, rank);
-    auto too_large = [&]() -> int {
-        GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
-                   max_slots, max_cand, rank, use_wide ? "" : "; wide=1 keeps the candidate table in global memory");
-    };
-    const Shape sh{a.prob_ptr, 0, max_slots, use_wide ? max_slots : 64, max_cand, a.n_lists, a.best_rows};
-    return search_launch(lds, too_large, use_wide ? descend_pairs_shortlist_wide_kernel : descend_pairs_shortlist_kernel, a.B, nt, a.stream,
-                         entry, sh, a.cand_ptr, a.cand, a.bounds, a.start_pos, a.max_sweeps, a.max_rounds, a.max_span, rank, o,
-                         ShortOut{a.shortlist, a.max_rank});
+// The three pair entries, each with 0 / NULL where it has no span, rank, wide (in `a`) or shortlist.  max_rank = 0: the same launch
+// from every entry, nothing extra.  max_rank > 0: the shortlist builds, run with the rank clamped to max_cand (no list is longer than
+// its problem's table).
+static int descend_pairs_entry(const char* who, bool lane_only, const DescendArgs& a, int32_t max_rounds, int32_t max_span, int32_t max_rank,
+                               const PairOut& o, int32_t* shortlist) {
+    const bool options_ok = max_rounds >= 0 && max_span >= 0 && max_rank >= 0;
+    const bool given = o.best_fitness && o.start_fitness && o.best_pos && o.round_history && o.sweeps && o.moves && o.rounds && o.pair_moves &&
+                       o.converged;
+    if (max_rank == 0)
+        return descend_entry(who, Build::pairs, lane_only, a, 0, options_ok, given, descend_pairs_kernel, descend_pairs_wide_kernel, max_rounds,
+                             max_span, o);
+    const int rank = max_rank < a.max_cand ? max_rank : a.max_cand;
+    return descend_entry(who, Build::shortlist, lane_only, a, rank, options_ok, given, descend_pairs_shortlist_kernel,
+                         descend_pairs_shortlist_wide_kernel, max_rounds, max_span, rank, o, ShortOut{shortlist, max_rank});
 }
 
 extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
@@ -1070,8 +1054,8 @@ extern "C" int gnnpn_descend_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr
                                               int32_t* best_pos, double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
                                               int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
     return descend_pairs_entry("descend_pairs_ragged", true,
-        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, 0, 0, 0,
-         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, nullptr, stream});
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, 0, best_rows, stream}, max_rounds, 0, 0,
+        {best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged}, nullptr);
 }
 
 extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
@@ -1081,8 +1065,8 @@ extern "C" int gnnpn_descend_pairs_windowed_ragged_f64(int32_t B, const int32_t*
                                                        double* best_rows, double* round_history, int32_t* sweeps, int32_t* moves,
                                                        int32_t* rounds, int32_t* pair_moves, int32_t* converged, void* stream) {
     return descend_pairs_entry("descend_pairs_windowed_ragged", false,
-        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, 0, wide,
-         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, nullptr, stream});
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, max_rounds, max_span, 0,
+        {best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged}, nullptr);
 }
 
 extern "C" int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots,
@@ -1093,8 +1077,8 @@ extern "C" int gnnpn_descend_pairs_shortlist_ragged_f64(int32_t B, const int32_t
                                                         int32_t* moves, int32_t* rounds, int32_t* pair_moves, int32_t* converged,
                                                         int32_t* shortlist, void* stream) {
     return descend_pairs_entry("descend_pairs_shortlist_ragged", false,
-        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, max_rounds, max_span, max_rank, wide,
-         best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds, pair_moves, converged, shortlist, stream});
+        {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, max_rounds, max_span,
+        max_rank, {best_fitness, start_fitness, best_pos, round_history, sweeps, moves, rounds, pair_moves, converged}, shortlist);
 }
 
 

@@ -193,8 +193,9 @@ struct WideLds {
     int* len;          // [T]
     double* bounds;    // [4]
     // The carve-up of a problem's dynamic LDS, the one statement of the layout the host's *_wide_lds_bytes size: the doubles
-    // (three columns, red, bounds, then `extra` more for the caller, returned), then the ints.
-    __device__ __forceinline__ double* carve(unsigned char* raw, int T, int extra = 0) {
+    // (three columns, red, bounds, then `extra` more for the caller, returned), then the ints.  Host code too: descend.hip sizes
+    // its launches by carving a null base.
+    __host__ __device__ __forceinline__ double* carve(unsigned char* raw, int T, size_t extra = 0) {
         col0 = reinterpret_cast<double*>(raw);
         col2 = col0 + T;
         col3 = col2 + T;

@@ -13,6 +13,7 @@ loadData.py); outputs stay on the device.
 import ctypes
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -140,44 +141,62 @@ def _quality(res, min_cost, dev):
     return res
 
 
-# Pair-swap descent under its three public names, each the SearchTables method of the same name: what a negative argument is told.
-_PAIR_REFUSAL = {"descend_pairs": "the number of rounds must be >= 0, got {}",
-                 "descend_pairs_windowed": "the number of rounds and the span must be >= 0, got {} and {}",
-                 "descend_pairs_shortlist": "the number of rounds, the span and the rank must be >= 0, got {}, {} and {}",
-                 "descend_tabu": "the number of steps and the tenure must be >= 0, got {} and {}"}       # (the tabu walk: no pairs, the same refusal)
+class Stage(NamedTuple):
+    """One search stage over candidate tables, written down once: what every layer above ``ops`` needs to know of it."""
+    method: str                  # the SearchTables method that runs it — and the name of the public function of one start per problem
+    options: tuple               # its option names, in the method's call order behind max_sweeps
+    refusal: str                 # what a negative option is told
+    starts: tuple                # the ``descend_starts*`` function that runs it from every start, and the options that one takes, in order
+    lane_only: bool = False      # it has the lane form only: at most 64 slots per problem
+    row_keys: tuple = ()         # its per-row [B * N] fields that ``_descend_starts`` also keeps per start, [B, N], as ``<key>_all``
+    winner_rows: tuple = ()      # its per-row [B * N, n] fields of which ``_descend_starts`` keeps the winner's row
+    values: tuple = ()           # a bound stage (``bind``): its options' values, ints
+
+    def bind(self, *values, who=None):
+        """This stage with its options' values, refused where one is negative (``who``: the public name that says so, where it is
+        not ``method``)."""
+        if min((int(v) for v in values), default=0) < 0:
+            raise ops.GnnpnError(f"{who or self.method}: " + self.refusal.format(*values))
+        return self._replace(values=tuple(int(v) for v in values))
 
 
-def _pair_options(name, *options, who=None):
-    """(name, max_rounds[, max_span[, max_rank]]) as ints: the pair options of the search stages below, refused where one is negative
-    (``who``: the public name that says so, where it is not ``name``)."""
-    if min(int(v) for v in options) < 0:
-        raise ops.GnnpnError(f"{who or name}: " + _PAIR_REFUSAL[name].format(*options))
-    return (name, *(int(v) for v in options))
+# The five stages: one-swap descent, pair-swap descent under its three public names, the tabu walk.
+STAGES = {s.method: s for s in (
+    Stage("descend", (), "", ("descend_starts",)),
+    Stage("descend_pairs", ("max_rounds",), "the number of rounds must be >= 0, got {}", ("descend_starts_pairs", "pair_rounds"),
+          lane_only=True, row_keys=("rounds", "pair_moves")),
+    Stage("descend_pairs_windowed", ("max_rounds", "max_span"), "the number of rounds and the span must be >= 0, got {} and {}",
+          ("descend_starts_pairs", "pair_rounds"), row_keys=("rounds", "pair_moves")),     # (from every start: the full sweep, no span)
+    Stage("descend_pairs_shortlist", ("max_rounds", "max_span", "max_rank"),
+          "the number of rounds, the span and the rank must be >= 0, got {}, {} and {}",
+          ("descend_starts_pairs_shortlist", "pair_rounds", "pair_span", "pair_rank"), row_keys=("rounds", "pair_moves")),
+    Stage("descend_tabu", ("max_steps", "tenure"), "the number of steps and the tenure must be >= 0, got {} and {}",
+          ("descend_starts_tabu", "max_steps", "tenure"), row_keys=("steps", "best_step"), winner_rows=("walk",)))}
+ONE_SWAP, PAIRS, PAIRS_WINDOWED, PAIRS_SHORTLIST, TABU = STAGES.values()
 
 
-def _search_tables(tabs, max_sweeps, pairs=None):
-    """One-swap descent over the tables, or (``pairs``: _pair_options) the pair-swap descent of that name; plus n_slots."""
-    if pairs and pairs[0] == "descend_pairs" and tabs["max_slots"] > 64:          # the one entry with the lane form only
-        raise ops.GnnpnError(f"descend_pairs: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
+def _search_tables(tabs, max_sweeps, stage=ONE_SWAP):
+    """The (bound) stage over the tables; plus n_slots."""
+    if stage.lane_only and tabs["max_slots"] > 64:
+        raise ops.GnnpnError(f"{stage.method}: a problem of the batch has {tabs['max_slots']} slots; the pair sweep takes at most 64 "
                              "per problem (descend runs one-swap descent at any slot count)")
-    res = getattr(tabs, pairs[0])(max_sweeps, *pairs[1:]) if pairs else tabs.descend(max_sweeps)
+    res = getattr(tabs, stage.method)(max_sweeps, *stage.values)
     res["n_slots"] = tabs["n_slots"]
     return res
 
 
 def _descend_tables(tabs, max_sweeps, pair_rounds=None):
     """One-swap descent over the tables, or (pair_rounds an int, 0 included) ``descend_pairs`` with that many rounds allowed."""
-    return _search_tables(tabs, max_sweeps, None if pair_rounds is None else _pair_options("descend_pairs", pair_rounds))
+    return _search_tables(tabs, max_sweeps, ONE_SWAP if pair_rounds is None else PAIRS.bind(pair_rounds))
 
 
-def _descend_actions(services, batch, out, max_sweeps, pairs, reduct, min_cost, patches):
-    """``descend`` (pairs None) and the three ``descend_pairs*`` (pairs: _pair_options' arguments): the refusal of a negative
-    argument, the tables of ``out["actions"]``, their descent, the quality."""
-    pairs = pairs and _pair_options(*pairs)
+def _descend_actions(services, batch, out, max_sweeps, stage, reduct, min_cost, patches):
+    """``descend``, the three ``descend_pairs*`` and ``descend_tabu``: the tables of ``out["actions"]``, the (bound) stage over them,
+    the quality."""
     actions = out["actions"]
     tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                               actions, reduct=reduct, patches=patches)
-    return _quality(_search_tables(tabs, max_sweeps, pairs), min_cost, actions.device)
+    return _quality(_search_tables(tabs, max_sweeps, stage), min_cost, actions.device)
 
 
 @torch.no_grad()
@@ -188,7 +207,7 @@ def descend(services, batch, out, max_sweeps=16, reduct=0, min_cost=None, patche
     problems in one launch, deterministic: no seeds).  A problem the host path raises on raises GnnpnError naming it.
     ``ML2PNPipeline.descend`` is this, as a method.  Returns ops.descend_ragged's dict (best_fitness, start_fitness, best_pos,
     best_rows, history, sweeps, moves) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness)."""
-    return _descend_actions(services, batch, out, max_sweeps, None, reduct, min_cost, patches)
+    return _descend_actions(services, batch, out, max_sweeps, ONE_SWAP, reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -201,7 +220,7 @@ def descend_pairs(services, batch, out, max_sweeps=16, max_rounds=4, reduct=0, m
     ops.descend_pairs_ragged's dict (best_fitness, start_fitness, best_pos, best_rows, round_history, sweeps, moves, rounds,
     pair_moves, converged) plus n_slots [B] i32 (and quality [B] f64 = min_cost / best_fitness).  ``max_rounds`` = 0: ``descend``'s
     result in every shared field."""
-    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs", max_rounds), reduct, min_cost, patches)
+    return _descend_actions(services, batch, out, max_sweeps, PAIRS.bind(max_rounds), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -211,7 +230,7 @@ def descend_pairs_windowed(services, batch, out, max_sweeps=16, max_rounds=4, ma
     makes a pair sweep affordable at hundreds of slots (converged then means: no single swap and no pair within the span lowers the
     result).  Problems of more than 64 slots run in the workgroup form (all of the batch, then).  A negative span or a negative
     number of rounds raises GnnpnError.  ``ML2PNPipeline.descend_pairs_windowed`` is this, as a method."""
-    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs_windowed", max_rounds, max_span), reduct, min_cost, patches)
+    return _descend_actions(services, batch, out, max_sweeps, PAIRS_WINDOWED.bind(max_rounds, max_span), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -222,8 +241,7 @@ def descend_pairs_shortlist(services, batch, out, max_sweeps=16, max_rounds=4, m
     lowest merit, so a slot pair costs at most m * m evaluations (converged then means: no single swap, and no pair within the span
     and the final composition's shortlists, lowers the result).  Any slot count.  A negative span, rank or number of rounds raises
     GnnpnError.  ``ML2PNPipeline.descend_pairs_shortlist`` is this, as a method."""
-    return _descend_actions(services, batch, out, max_sweeps, ("descend_pairs_shortlist", max_rounds, max_span, max_rank), reduct, min_cost,
-                            patches)
+    return _descend_actions(services, batch, out, max_sweeps, PAIRS_SHORTLIST.bind(max_rounds, max_span, max_rank), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -236,7 +254,7 @@ def descend_tabu(services, batch, out, max_sweeps=16, max_steps=32, tenure=ops.D
     tenure raises GnnpnError.  ``ML2PNPipeline.descend_tabu`` is this, as a method.  Returns ops.descend_tabu_ragged's dict
     (``descend``'s keys, history per step, walk, steps, best_step, stalled) plus n_slots [B] i32 (and quality [B] f64).
     ``max_steps`` = 0: ``descend``'s result in every shared field."""
-    return _descend_actions(services, batch, out, max_sweeps, ("descend_tabu", max_steps, tenure), reduct, min_cost, patches)
+    return _descend_actions(services, batch, out, max_sweeps, TABU.bind(max_steps, tenure), reduct, min_cost, patches)
 
 
 @torch.no_grad()
@@ -248,7 +266,7 @@ def descend_starts_tabu(services, batch, starts, max_sweeps=16, max_steps=32, te
     best_step_all are [B, N] i32.  ``max_steps`` = 0 is ``descend_starts``' result in every shared field.  A negative number of
     steps or tenure raises GnnpnError.  ``ML2PNPipeline.descend_starts_tabu`` is this, as a method."""
     return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
-                           _pair_options("descend_tabu", max_steps, tenure, who="descend_starts_tabu"))
+                           TABU.bind(max_steps, tenure, who="descend_starts_tabu"))
 
 
 @torch.no_grad()
@@ -263,7 +281,7 @@ def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=No
     method.  Returns ``descend``'s keys for the winners plus start_index [B] i32, actions [B, T', 8] (the winner's start rows:
     ``refine(services, batch, res, ..., descend=k)`` rebuilds its tables and repeats its descent before ES-WOA), fitness_all and
     start_fitness_all [B, N] f64, sweeps_all and moves_all [B, N] i32 (and quality [B] f64 = min_cost / best_fitness)."""
-    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, None)
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, ONE_SWAP)
 
 
 @torch.no_grad()
@@ -275,7 +293,7 @@ def descend_starts_pairs(services, batch, starts, max_sweeps=16, pair_rounds=4, 
     ``pair_rounds`` = 0 is ``descend_starts``: the same launches, the same result.  ``descend_starts`` itself keeps its
     signature, which is why this is a function of its own.  ``ML2PNPipeline.descend_starts_pairs`` is this, as a method."""
     return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
-                           _pair_options("descend_pairs", pair_rounds) if int(pair_rounds) else None)
+                           PAIRS.bind(pair_rounds) if int(pair_rounds) else ONE_SWAP)
 
 
 @torch.no_grad()
@@ -288,12 +306,12 @@ def descend_starts_pairs_shortlist(services, batch, starts, max_sweeps=16, pair_
     the rows' one-swap descent, reported in the pair-swap format).  A negative span, rank or number of rounds raises GnnpnError.
     ``ML2PNPipeline.descend_starts_pairs_shortlist`` is this, as a method."""
     return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
-                           _pair_options("descend_pairs_shortlist", pair_rounds, pair_span, pair_rank, who="descend_starts_pairs_shortlist"))
+                           PAIRS_SHORTLIST.bind(pair_rounds, pair_span, pair_rank, who="descend_starts_pairs_shortlist"))
 
 
-def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, pairs):
-    """The three ``descend_starts*``: the tables of every start, their descent (``pairs``: _pair_options, or None for the one-swap
-    descent and its result keys), the selection, the per-start fields, the quality."""
+def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, stage):
+    """The four ``descend_starts*``: the tables of every start, the (bound) stage over them, the selection, the per-start fields
+    (the stage's own among them), the quality."""
     all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
     if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
         raise ops.GnnpnError(f"descend_starts: starts [B, N, T, 8|9] expected, got {tuple(getattr(all_rows, 'shape', ()))}")
@@ -301,17 +319,14 @@ def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patch
     B, N = all_rows.shape[:2]
     tabs = ops.woa_candidates_replicas(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
                                        all_rows, reduct=reduct, patches=patches)
-    per_row = _search_tables(tabs, max_sweeps, pairs)
+    per_row = _search_tables(tabs, max_sweeps, stage)
     res = ops.descend_select(per_row, all_rows, tabs["n_slots"])        # (the rounds' merits and counters too, where there are any)
     res.update(fitness_all=per_row["best_fitness"].view(B, N), start_fitness_all=per_row["start_fitness"].view(B, N),
                sweeps_all=per_row["sweeps"].view(B, N), moves_all=per_row["moves"].view(B, N))
-    if pairs is not None and pairs[0] == "descend_tabu":
-        win = res["start_index"].long()[:, None, None]
-        walk = per_row["walk"].reshape(B, N, -1)
-        res.update(steps_all=per_row["steps"].view(B, N), best_step_all=per_row["best_step"].view(B, N),
-                   walk=walk.gather(1, win.expand(B, 1, walk.shape[2]))[:, 0])
-    elif pairs is not None:
-        res.update(rounds_all=per_row["rounds"].view(B, N), pair_moves_all=per_row["pair_moves"].view(B, N))
+    res.update({k + "_all": per_row[k].view(B, N) for k in stage.row_keys})
+    for k in stage.winner_rows:
+        rows = per_row[k].reshape(B, N, -1)
+        res[k] = rows.gather(1, res["start_index"].long()[:, None, None].expand(B, 1, rows.shape[2]))[:, 0]
     return _quality(res, min_cost, all_rows.device)
 
 

@@ -133,6 +133,20 @@ def _load_ml_checkpoint(path):
     return obj
 
 
+def _valued(flags, name, bare=None):
+    """The text of the valued flag ``name`` among ``flags``: what follows ``name=``, ``bare`` for the flag alone (a flag without a default
+    passes "", which is no number), None where the flag is absent.  The first spelling on the command line counts."""
+    for a in flags:
+        if a == name or a.startswith(name + "="):
+            return a.split("=", 1)[1] if "=" in a else bare
+    return None
+
+
+def _count(text):
+    """A flag's text as an int >= 0; -1 where it is none (below every option's least value), None where the flag is absent."""
+    return None if text is None else int(text) if text.lstrip("+").isdigit() else -1
+
+
 def main(argv):
     if len(argv) < 3:
         print("Please check the parameters!")
@@ -199,48 +213,39 @@ def main(argv):
     from gnnpn_sc_amd import ML2PN
     if "--infer" in flags:
         import json
-        samples = next((a.split("=", 1)[1] for a in flags if a.startswith("--samples=")), None)
-        sweeps = next((a.split("=", 1)[1] if "=" in a else "16" for a in flags if a == "--descend" or a.startswith("--descend=")), None)
-        if "--all-starts" in flags and (samples is None or int(samples) < 2 or sweeps is None):
-            print("--all-starts: needs --samples=N (N > 1) and --descend[=SWEEPS]")
-            return 1
-        rounds = next((a.split("=", 1)[1] if "=" in a else "4" for a in flags if a == "--pairs" or a.startswith("--pairs=")), None)
-        if rounds is not None and (sweeps is None or int(rounds) < 1):
-            print("--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round")
-            return 1
-        if "--services" in flags and sweeps is None and "--woa" not in flags:
-            print("--services: needs --descend[=SWEEPS] or --woa (the services of a searched composition)")
-            return 1
-        span = next((a.split("=", 1)[1] for a in flags if a.startswith("--span=")), "" if "--span" in flags else None)
-        top = next((a.split("=", 1)[1] for a in flags if a.startswith("--top=")), "" if "--top" in flags else None)
-        if top is not None:
-            if rounds is None or not top.lstrip("+").isdigit():
-                print("--top=M: needs --pairs[=ROUNDS] and M >= 0 (0: every candidate)")
+        woa_flag, services, all_starts = "--woa" in flags, "--services" in flags, "--all-starts" in flags
+        samples = _valued(flags, "--samples") or None
+        sweeps = _valued(flags, "--descend", "16")
+        # the search options, by ML2PN's names for them; what each needs is ML2PN.stage_ok's to say, of the stage that takes it last
+        given = {k: _count(_valued(flags, flag, bare)) for k, flag, bare in (
+            ("pair_rounds", "--pairs", "4"), ("pair_span", "--span", ""), ("pair_rank", "--top", ""), ("tabu_steps", "--tabu", "32"),
+            ("tenure", "--tenure", ""))}
+        rounds, span, top, tabu, tenure = given.values()
+        ok = ML2PN.stage_ok
+        for refused, why in (                                       # in the order they are reported: the first one is
+                (all_starts and (samples is None or int(samples) < 2 or sweeps is None),
+                 "--all-starts: needs --samples=N (N > 1) and --descend[=SWEEPS]"),
+                (rounds is not None and not ok("descend_pairs", sweeps, rounds),
+                 "--pairs[=ROUNDS]: needs --descend[=SWEEPS] and at least one round"),
+                (services and sweeps is None and not woa_flag,
+                 "--services: needs --descend[=SWEEPS] or --woa (the services of a searched composition)"),
+                (top is not None and not ok("descend_pairs_shortlist", sweeps, rounds, 0, top),
+                 "--top=M: needs --pairs[=ROUNDS] and M >= 0 (0: every candidate)"),
+                (top is not None and woa_flag, "--top=M: not with --woa (the ES-WOA start takes the full pair sweep of at most 64 slots)"),
+                (span is not None and not ok("descend_pairs_windowed", sweeps, rounds, span),
+                 "--span=N: needs --pairs[=ROUNDS] and N >= 0 (0: every slot pair)"),
+                (span is not None and ((all_starts and top is None) or woa_flag),
+                 "--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at most 64 slots)"),
+                (tabu is not None and not ok("descend_tabu", sweeps, tabu, 0),
+                 "--tabu[=STEPS]: needs --descend[=SWEEPS] and STEPS >= 0 (0: the one-swap descent alone)"),
+                (tabu is not None and (rounds is not None or woa_flag or services),
+                 "--tabu[=STEPS]: not with --pairs, --woa or --services (the walk takes single swaps, and the ES-WOA start and the services "
+                 "artefact take the descent's result)"),
+                (tenure is not None and not ok("descend_tabu", sweeps, tabu, tenure),
+                 "--tenure=N: needs --tabu[=STEPS] and N >= 0 (0: a slot may go straight back)")):
+            if refused:
+                print(why)
                 return 1
-            if "--woa" in flags:
-                print("--top=M: not with --woa (the ES-WOA start takes the full pair sweep of at most 64 slots)")
-                return 1
-        if span is not None:
-            if rounds is None or not span.lstrip("+").isdigit():
-                print("--span=N: needs --pairs[=ROUNDS] and N >= 0 (0: every slot pair)")
-                return 1
-            if ("--all-starts" in flags and top is None) or "--woa" in flags:
-                print("--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at "
-                      "most 64 slots)")
-                return 1
-        tabu = next((a.split("=", 1)[1] if "=" in a else "32" for a in flags if a == "--tabu" or a.startswith("--tabu=")), None)
-        tenure = next((a.split("=", 1)[1] for a in flags if a.startswith("--tenure=")), "" if "--tenure" in flags else None)
-        if tabu is not None:
-            if sweeps is None or not tabu.lstrip("+").isdigit():
-                print("--tabu[=STEPS]: needs --descend[=SWEEPS] and STEPS >= 0 (0: the one-swap descent alone)")
-                return 1
-            if rounds is not None or "--woa" in flags or "--services" in flags:
-                print("--tabu[=STEPS]: not with --pairs, --woa or --services (the walk takes single swaps, and the ES-WOA start and the "
-                      "services artefact take the descent's result)")
-                return 1
-        if tenure is not None and (tabu is None or not tenure.lstrip("+").isdigit()):
-            print("--tenure=N: needs --tabu[=STEPS] and N >= 0 (0: a slot may go straight back)")
-            return 1
         with open(f"./data/{ds}/serviceFeature.data") as f:
             sf = json.load(f)
         n_services = sum(len(v) for v in sf.values())
@@ -248,36 +253,25 @@ def main(argv):
         args = argv[3:]
         seed = int(args[args.index("--seed") + 1]) if "--seed" in args else None      # the ES-WOA streams' and the best-of-N draws'
         woa = None
-        if "--woa" in flags:                                        # + ES-WOA refinement on the device ([<ds>-WOA])
+        if woa_flag:                                                # + ES-WOA refinement on the device ([<ds>-WOA])
             w = cfg[f"{ds}-WOA"]
             woa = {"popSize": int(w["popSize"]), "MAX_Iter": int(w["MAX_Iter"]),
                    "reduct": float(w["reduct"]) if ds == "Normal" else int(w["reduct"]), "seed": seed}
-        best = {}
+        best = {k: v for k, v in given.items() if v is not None}    # the search options given (their combinations are refused above)
         if samples is not None:                                     # best-of-N decoding of the High level
-            best = {"samples": int(samples), "sample_seed": seed}
+            best.update(samples=int(samples), sample_seed=seed)
         if sweeps is not None:                                      # one-swap descent of the test quarter's actions
             if int(sweeps) < 1:
                 print("--descend=SWEEPS: at least one sweep")
                 return 1
             best["descend"] = int(sweeps)
-        if "--all-starts" in flags:                                 # descent from every best-of-N replica, the lowest optimum kept
+        if all_starts:                                              # descent from every best-of-N replica, the lowest optimum kept
             best["all_starts"] = True
-        if rounds is not None:                                      # pair-swap descent in place of the one-swap descent
-            best["pair_rounds"] = int(rounds)
-        if span is not None:                                        # ... at any slot count, over slots at most N apart
-            best["pair_span"] = int(span)
-        if tabu is not None:                                        # a tabu walk from the one-swap optimum (refused above beside --pairs, --woa)
-            ML2PN.infer_tabu(ds, net, low, high, K, epoch, tabu_steps=int(tabu), tenure=None if tenure is None else int(tenure), **best)
-        elif "--services" in flags:                                 # the same run, plus ML+2PN+services.txt: which services it found
-            if top is not None:
-                best["pair_rank"] = int(top)
-            ML2PN.infer_services(ds, net, low, high, K, epoch, woa=woa, **best)
-        elif top is not None:                                       # ... over the M best candidates of each slot (refused beside --woa)
-            ML2PN.infer_pairs_shortlist(ds, net, low, high, K, epoch, pair_rank=int(top), **best)
-        elif "pair_span" in best:                                   # (refused above beside --woa and --all-starts)
-            ML2PN.infer_pairs_windowed(ds, net, low, high, K, epoch, **best)
-        else:
-            ML2PN.infer(ds, net, low, high, K, epoch, woa=woa, **best)
+        # the stage's own infer_*; with --services infer_services: the same run, plus ML+2PN+services.txt: which services it found
+        run = ML2PN.infer_services if services else getattr(ML2PN, ML2PN.RUNS[ML2PN.stage_given(rounds, span, top, tabu)][2])
+        if run in (ML2PN.infer, ML2PN.infer_services):              # the two with ES-WOA behind the stage (--woa is refused above beside the others)
+            best["woa"] = woa
+        run(ds, net, low, high, K, epoch, **best)
         n_cat = len(sf)
     ML2PN.check(ds, n_cat, epoch)
     return 0
