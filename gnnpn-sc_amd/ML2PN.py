@@ -113,6 +113,19 @@ def infer_tabu(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_
     return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts, stage)
 
 
+def infer_tabu_pairs(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", samples=1, sample_seed=None,
+                     descend=16, all_starts=False, tabu_steps=32, tenure=None, pair_rank=None, pair_span=0):
+    """``infer_tabu`` whose step may take a pair swap of the ``pair_rank`` best candidates of two slots at most ``pair_span`` apart
+    (>= 0; a rank of None: ops.DEFAULT_PAIR_RANK, of 0: whole lists; a span of 0: every slot pair; pipeline.descend_tabu_pairs):
+    ``ML+2PN+tabu+pairs.txt`` in ``infer_tabu``'s format plus the per-problem ``pair_steps`` and the settings ``top`` and ``span``.
+    With ``all_starts`` (and samples > 1) from every replica (pipeline.descend_starts_tabu_pairs):
+    ``ML+2PN+multistart+tabu+pairs.txt``.  Without ``woa``.  A function of its own, as ``infer_tabu`` is."""
+    from . import ops
+    stage = _stage("infer_tabu_pairs", "descend_tabu_pairs", descend, tabu_steps, ops.DEFAULT_TENURE if tenure is None else tenure,
+                   ops.DEFAULT_PAIR_RANK if pair_rank is None else pair_rank, pair_span)
+    return _infer(dataset, net, low, high, n_per, epoch, device, batch_size, precision, None, samples, sample_seed, descend, all_starts, stage)
+
+
 def infer_services(dataset, net, low, high, n_per, epoch=-1, device="cuda:0", batch_size=128, precision="f32", woa=None, samples=1,
                    sample_seed=None, descend=None, all_starts=False, pair_rounds=None, pair_span=None, pair_rank=None):
     """``infer`` (with ``pair_span`` / ``pair_rank``: ``infer_pairs_windowed`` / ``infer_pairs_shortlist``) whose last search stage
@@ -142,23 +155,35 @@ RUNS = {
                      ("tabu_steps", "tenure"))}
 
 
-def stage_given(pair_rounds=None, pair_span=None, pair_rank=None, tabu_steps=None):
-    """The stage (its name in pipeline.STAGES) that the options given — not None — ask for: the one that takes the last of them."""
-    return ("descend_tabu" if tabu_steps is not None else "descend_pairs_shortlist" if pair_rank is not None else
+# The stages of pipeline.MORE_STAGES, in RUNS' format: a table of its own beside RUNS, as MORE_STAGES is beside STAGES.
+MORE_RUNS = {
+    "descend_tabu_pairs": ((0, 0, 0, 0), "pair_moves needs descend, a number of steps >= 0, a tenure >= 0, a rank >= 0 and a span >= 0",
+                           "infer_tabu_pairs", "tabu+pairs", "stalled", ("tabu_steps", "tenure", "top", "span"))}
+
+
+def run_named(name):
+    """The row of that stage: RUNS' first, then MORE_RUNS'."""
+    return RUNS[name] if name in RUNS else MORE_RUNS[name]
+
+
+def stage_given(pair_rounds=None, pair_span=None, pair_rank=None, tabu_steps=None, pair_moves=None):
+    """The stage (its name in pipeline.STAGES or MORE_STAGES) that the options given — not None — ask for: the one that takes the last
+    of them.  ``pair_moves``: the rank of the tabu walk's pair moves."""
+    return ("descend_tabu_pairs" if pair_moves is not None else "descend_tabu" if tabu_steps is not None else "descend_pairs_shortlist" if pair_rank is not None else
             "descend_pairs_windowed" if pair_span is not None else "descend_pairs" if pair_rounds is not None else "descend")
 
 
 def stage_ok(name, descend, *values):
     """The precondition of a stage with options: ``descend`` is given, and so is every option, none below its least value."""
-    return not values or (descend is not None and all(v is not None and v >= least for v, least in zip(values, RUNS[name][0])))
+    return not values or (descend is not None and all(v is not None and v >= least for v, least in zip(values, run_named(name)[0])))
 
 
 def _stage(who, name, descend, *values):
     """The stage ``name`` bound to its options' values (pipeline.Stage.bind), or ``who``'s ValueError where ``stage_ok`` says no."""
     if not stage_ok(name, descend, *values):
-        raise ValueError(f"ML2PN.{who}: {RUNS[name][1]}")
+        raise ValueError(f"ML2PN.{who}: {run_named(name)[1]}")
     from . import pipeline as pl
-    return pl.STAGES[name].bind(*values)
+    return pl.stage_named(name).bind(*values)
 
 
 def _stage_asked(who, descend, pair_rounds, pair_span=None, pair_rank=None):
@@ -172,7 +197,7 @@ def search_plan(stage, multi):
     """How the test quarter goes through a (bound) stage, from every start (``multi``) or from the actions: the pipeline function, its
     keyword arguments beside max_sweeps, reduct and min_cost, the artefact, the per-problem fields of the result it lists and the
     settings beside them (no fields: the artefact has no ``extra``).  A pure function: no device is touched."""
-    _, _, _, part, flag, written = RUNS[stage.method]
+    _, _, _, part, flag, written = run_named(stage.method)
     function, *names = stage.starts if multi else (stage.method, *stage.options)
     parts = [p for p in ("multistart" if multi else "", part) if p] or ["descent"]
     return (function, dict(zip(names, stage.values)), "ML+2PN+" + "+".join(parts) + ".txt", stage.row_keys + (flag,) if flag else (),

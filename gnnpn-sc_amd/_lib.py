@@ -105,6 +105,8 @@ _SIGNATURES = {
                                                          c_int32, c_int32] + [_P] * 12),
     "gnnpn_descend_tabu_ragged_f64": (c_int, [c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32] +
                                       [_P] * 12),
+    "gnnpn_descend_tabu_pairs_ragged_f64": (c_int, [c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32,
+                                                    c_int32, c_int32] + [_P] * 13),
     "gnnpn_woa_candidates_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "gnnpn_woa_candidates_count": (c_int, [c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_double,
                                            _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P]),

@@ -28,6 +28,13 @@
 // step — whether or not it lowers the merit, bars the position the slot left for `tenure` steps unless the swap beats the best merit
 // seen, and remembers the best composition; the one-swap sweeps polish it where the walk was cut there (tests/tabu_reference.py).
 // No draws: a pure function of the tables.  The six descent builds compile none of it.
+//
+// The tabu walk over pair moves (descend_tabu_pairs_kernel, descend_tabu_pairs_wide_kernel) is that walk whose step may also take a
+// pair: the step's slot loop forms the shortlists of the current composition from the same single-swap merits that the singles'
+// argmin reads, a pair pass over the shortlists follows — the evaluation of one (i, j, a, b) is the pair sweeps' (pair_path,
+// pair_rest, pair_merit), stated once — and ONE argmin over (merit, single before pair, key) ends the step; a pair is tabu where
+// either of its positions is, and both slots bar the positions they leave (tests/tabu_pairs_reference.py).  It crosses in one step
+// the wall that costs the tabu walk two, and goes on where the pair sweeps stop.  The eight other builds compile none of the pass.
 #include "woa_eval.h"
 
 #include <climits>
@@ -105,7 +112,8 @@ constexpr int SIB_MAX = 32;        // levels of np.sum's recursion: a block halv
 // Where a problem's state lives: the columns of cur (L.col0, col1, L.col2, L.col3), the base / len tables and the bounds in LDS;
 // cur, in LDS or the problem's best_pos row; the candidate table's LDS copy (lane form); red / cnt / sib (workgroup form).  The
 // shortlist builds add mer / rk (one list's single-swap merits and their ranks) and list (every slot's shortlist), the tabu builds
-// expire and best, all in LDS.  A build fills what it uses (lane_carve, wide_carve) and reads nothing else.
+// expire and best, the pair-move walk's builds all five, all in LDS.  A build fills what it uses (lane_carve, wide_carve) and reads
+// nothing else.
 struct DescendMem {
     WideLds L;
     double* col1;      // [T] column 1 (np.min)
@@ -120,21 +128,24 @@ struct DescendMem {
     int* best;         // [T] ... the best composition the walk has seen
 };
 
-// The four builds of each form, by what they search with: it decides the sibling rows and what comes on top of the search state.
-enum class Build { one_swap, pairs, shortlist, tabu };
+// The five builds of each form, by what they search with: it decides the sibling rows and what comes on top of the search state.
+enum class Build { one_swap, pairs, shortlist, tabu, tabu_pairs };
+__host__ __device__ __forceinline__ bool has_shortlists(Build b) { return b == Build::shortlist || b == Build::tabu_pairs; }
+__host__ __device__ __forceinline__ bool has_tabu_table(Build b) { return b == Build::tabu || b == Build::tabu_pairs; }
 
-// The ints on top of a form's tables: rk [max_cand] and list [slots][rank] (shortlist), expire [max_cand] and best [slots] (tabu).
+// The ints on top of a form's tables: rk [max_cand] and list [slots][rank] (shortlists), then expire [max_cand] and best [slots]
+// (tabu table); the pair-move walk has both.
 __host__ __device__ __forceinline__ int* carve_ints(DescendMem& M, int* at, Build build, int slots, int max_cand, int rank) {
-    if (build == Build::shortlist) {
+    if (has_shortlists(build)) {
         M.rk = at;
         M.list = M.rk + max_cand;
         M.rank = rank;
-        return M.list + (size_t)slots * rank;
+        at = M.list + (size_t)slots * rank;
     }
-    if (build == Build::tabu) {
+    if (has_tabu_table(build)) {
         M.expire = at;
         M.best = M.expire + max_cand;
-        return M.best + slots;
+        at = M.best + slots;
     }
     return at;
 }
@@ -142,7 +153,8 @@ __host__ __device__ __forceinline__ int* carve_ints(DescendMem& M, int* at, Buil
 // The LDS layout of a problem, stated once per form: the kernels carve `raw` with it, and the host asks for the bytes it returns
 // on a null base with the launch's maxima (descend_lds_bytes), so the two cannot part.
 // Lane form: the four columns of cur [4][64] (figure_of_merit's layout), bounds [4], base / len / cur [64] each, the candidate table
-// [max_cand][4]; behind it mer [max_cand] f64, rk and list [max_slots][rank] (shortlist), or expire and best [64] (tabu).
+// [max_cand][4]; behind it mer [max_cand] f64, rk and list [max_slots][rank] (shortlist), or expire and best [64] (tabu), or all of
+// them with best [max_slots] (the pair-move walk).
 __host__ __device__ __forceinline__ size_t lane_carve(DescendMem& M, unsigned char* raw, Build build, int max_slots, int max_cand, int rank) {
     double* col = reinterpret_cast<double*>(raw);
     int* tab = reinterpret_cast<int*>(col + 260);
@@ -152,7 +164,7 @@ __host__ __device__ __forceinline__ size_t lane_carve(DescendMem& M, unsigned ch
     M.cur = tab + 128;
     M.table = reinterpret_cast<double*>(tab + 192);
     double* top = M.table + (size_t)max_cand * 4;
-    if (build == Build::shortlist) {
+    if (has_shortlists(build)) {
         M.mer = top;
         top += max_cand;
     }
@@ -162,13 +174,13 @@ __host__ __device__ __forceinline__ size_t lane_carve(DescendMem& M, unsigned ch
 
 // Workgroup form, T slots (the problem's own in a kernel, max_slots on the host): WideLds with column 1 [T], the sibling sums
 // [1 | 3][SIB_MAX] (one row for the one-swap sweeps, three where there is a pair sweep) and, shortlist, mer [max_cand] among its
-// doubles; behind its base / len tables rk and list [T][rank] (shortlist), or expire and best [T] (tabu).  cur is the problem's
-// best_pos row, the table stays in global memory.
+// doubles; behind its base / len tables rk and list [T][rank] (shortlist), or expire and best [T] (tabu), or all four (the pair-move
+// walk, which also has the three sibling rows and mer).  cur is the problem's best_pos row, the table stays in global memory.
 __host__ __device__ __forceinline__ size_t wide_carve(DescendMem& M, unsigned char* raw, Build build, int T, int max_cand, int rank, int32_t* cur) {
-    const int sibs = (build == Build::pairs || build == Build::shortlist ? 3 : 1) * SIB_MAX;
-    M.col1 = M.L.carve(raw, T, (size_t)T + sibs + (build == Build::shortlist ? max_cand : 0));
+    const int sibs = (build == Build::pairs || has_shortlists(build) ? 3 : 1) * SIB_MAX;
+    M.col1 = M.L.carve(raw, T, (size_t)T + sibs + (has_shortlists(build) ? max_cand : 0));
     M.sib = M.col1 + T;
-    if (build == Build::shortlist) M.mer = M.sib + sibs;
+    if (has_shortlists(build)) M.mer = M.sib + sibs;
     M.cur = cur;
     M.table = nullptr;
     int* end = carve_ints(M, M.L.len + T, build, T, max_cand, rank);
@@ -418,11 +430,31 @@ __device__ __forceinline__ bool ranks_before(double f2, int c2, double f, int c)
     return n2 == n ? c2 < c : n;
 }
 
+// A slot's shortlist from the merits of its list in M.mer[0 .. lj - 1] (written, and a barrier passed): every candidate's rank by counting
+// the candidates before it (lj reads of M.mer, every thread the same address) into M.rk; a kept candidate's place = the kept ones at
+// lower positions.  row[0 .. keep - 1] = the kept positions, ascending.  lj, keep and the barrier are workgroup-uniform.
+template <int NT>
+__device__ __forceinline__ void keep_lowest(const DescendMem& M, int* row, int lj, int keep) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < lj; c += NT) {
+        const double f = M.mer[c];
+        int r = 0;
+        for (int c2 = 0; c2 < lj; ++c2) r += ranks_before(M.mer[c2], c2, f, c);
+        M.rk[c] = r;
+    }
+    __syncthreads();
+    for (int c = tid; c < lj; c += NT) {
+        if (M.rk[c] >= keep) continue;
+        int at = 0;
+        for (int c2 = 0; c2 < c; ++c2) at += M.rk[c2] < keep;
+        row[at] = c;
+    }
+}
+
 // The shortlists of one pair sweep, from the state in LDS by the NT threads of the problem's workgroup: per slot j the min(rank,
 // len_j) candidates whose single swap into the CURRENT composition has the lowest merit, positions ascending, into M.list[j][..]
 // (-1 behind them).  Per slot: the merits of the list (one_swap_merit, thread = one candidate, chunks beyond the workgroup) into
-// M.mer; every candidate's rank by counting the candidates before it (len_j reads of M.mer, every thread the same address); a kept
-// candidate's place = the kept ones at lower positions.  A list no longer than `rank` is kept whole and nothing is evaluated.
+// M.mer, then keep_lowest.  A list no longer than `rank` is kept whole and nothing is evaluated.
 // Nothing moves here.  Bounded by T and list lengths; j, keep and every barrier are workgroup-uniform.
 template <int NT>
 __device__ __forceinline__ void form_shortlists(const DescendMem& M, const DescendState& S) {
@@ -441,19 +473,7 @@ __device__ __forceinline__ void form_shortlists(const DescendMem& M, const Desce
             const double old0 = L.col0[j];
             for (int c = tid; c < lj; c += NT) M.mer[c] = one_swap_merit<NT>(M, S.cr, cand + (size_t)(bj + c) * 4, T, j, sp, old0, pre2, pre3);
             __syncthreads();
-            for (int c = tid; c < lj; c += NT) {
-                const double f = M.mer[c];
-                int r = 0;
-                for (int c2 = 0; c2 < lj; ++c2) r += ranks_before(M.mer[c2], c2, f, c);
-                M.rk[c] = r;
-            }
-            __syncthreads();
-            for (int c = tid; c < lj; c += NT) {
-                if (M.rk[c] >= keep) continue;
-                int at = 0;
-                for (int c2 = 0; c2 < c; ++c2) at += M.rk[c2] < keep;
-                row[at] = c;
-            }
+            keep_lowest<NT>(M, row, lj, keep);
         }
         for (int k = keep + tid; k < rank; k += NT) row[k] = -1;
         __syncthreads();                                              // the row stands; mer / rk / sib are free for slot j + 1
@@ -467,19 +487,125 @@ __device__ __forceinline__ void form_shortlists(const DescendMem& M, const Desce
 template <int NT>
 using pair_key_t = std::conditional_t<(NT > 64), long long, int>;
 
+// The evaluation of one pair (i, j, a, b), stated once for the pair sweeps and the pair-move walk: pair_path (what np.sum needs of the
+// slot pair), pair_rest (what np.min and the count of real services keep of the other slots) and pair_merit (one thread's merit).
+
+// np.sum's blocks of the slot pair i < j.  Lane form: one leaf, nothing to form.  Workgroup form, above 128 slots: the block that
+// holds both slots (off, ln) and its n_up untouched siblings up to the root in M.sib[0 ..]; `two`: the paths part, each slot has
+// its own leaf (off_i, ln_i / off_j, ln_j) and n_i / n_j siblings below the parting node in M.sib[SIB_MAX ..] / M.sib[2 SIB_MAX ..].
+// The sibling sums are formed by pw_sum, the waves taking them in turn, and a barrier follows.  Workgroup-uniform.
+struct PairPath {
+    int off, ln, n_up, off_i, ln_i, n_i, off_j, ln_j, n_j;
+    bool two;
+};
+template <int NT>
+__device__ __forceinline__ PairPath pair_path(const DescendMem& M, int T, int i, int j) {
+    PairPath pp{0, T, 0, 0, 0, 0, 0, 0, 0, false};
+    if constexpr (NT > 64) {
+        const WideLds& L = M.L;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        // One walk in three stretches (part 0: the common path from the root, 1: slot i's below the parting node, 2: slot
+        // j's), so that pw_sum stands once; the waves take the siblings in turn.  Thread-uniform, no barrier inside.
+        int part = 0, o = 0, l = T, d = 0, turn = 0, right_o = 0, right_l = 0;
+        for (int step = 0; step < 3 * SIB_MAX + 4; ++step) {
+            if (l <= 128 || d >= SIB_MAX) {                            // a leaf block ends the stretch
+                if (part == 0) {
+                    pp.off = o; pp.ln = l; pp.n_up = d;
+                    break;
+                }
+                if (part == 2) {
+                    pp.off_j = o; pp.ln_j = l; pp.n_j = d;
+                    break;
+                }
+                pp.off_i = o; pp.ln_i = l; pp.n_i = d;
+                part = 2; o = right_o; l = right_l; d = 0;
+                continue;
+            }
+            int n2 = l / 2;
+            n2 -= n2 % 8;
+            if (part == 0 && i < o + n2 && j >= o + n2) {              // i left, j right: the paths part here
+                pp.two = true;
+                pp.n_up = d;
+                right_o = o + n2; right_l = l - n2;
+                part = 1; l = n2; d = 0;
+                continue;
+            }
+            int so, sl;
+            if ((part == 2 ? j : i) < o + n2) {                        // (common path: both slots are on slot i's side)
+                so = o + n2; sl = l - n2; l = n2;
+            } else {
+                so = o; sl = n2; o += n2; l -= n2;
+            }
+            if (wave == (turn & (NT / 64 - 1))) {
+                const double v = pw_sum(L.col0 + so, sl, lane);
+                if (lane == 0) M.sib[part * SIB_MAX + d] = v;
+            }
+            ++turn;
+            ++d;
+        }
+        __syncthreads();                                               // sib is written
+    }
+    return pp;
+}
+
+// np.min of column 1 and the number of real services without slots i and j.
+struct PairRest {
+    double min;
+    int real;
+};
+__device__ __forceinline__ PairRest pair_rest(const DescendMem& M, const Carried& cr, int i, int j) {
+    return PairRest{cr.min_without(i, j), cr.n_real - (M.L.col0[i] > 0.0) - (M.L.col0[j] > 0.0)};
+}
+
+// The merit of the current composition with slots i < j replaced by rows ra and rb, by ONE thread.  pre2 / pre3: np.cumprod up to
+// slot i - 1; the thread continues both chains with row a, cur[i+1 .. j-1], row b, cur[j+1 .. T-1], one __dmul_rn each (numpy's
+// order), and forms np.sum with the two elements replaced: in one leaf both at once; in two leaves each leaf with its own, the
+// untouched siblings of each path up to the parting node, left + right; then the common path up to the root.
+template <int NT>
+__device__ __forceinline__ double pair_merit(const DescendMem& M, const PairRest& rest, const double* ra, const double* rb, int T, int i, int j,
+                                             const PairPath& pp, double pre2, double pre3) {
+    const WideLds& L = M.L;
+    const double a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
+    double p2 = i == 0 ? ra[2] : __dmul_rn(pre2, ra[2]), p3 = i == 0 ? ra[3] : __dmul_rn(pre3, ra[3]);
+    for (int m = i + 1; m < j; ++m) {
+        p2 = __dmul_rn(p2, L.col2[m]);
+        p3 = __dmul_rn(p3, L.col3[m]);
+    }
+    p2 = __dmul_rn(p2, rb[2]);
+    p3 = __dmul_rn(p3, rb[3]);
+    for (int m = j + 1; m < T; ++m) {
+        p2 = __dmul_rn(p2, L.col2[m]);
+        p3 = __dmul_rn(p3, L.col3[m]);
+    }
+    double sum;
+    if constexpr (NT > 64) {
+        if (pp.two) {
+            double left = pw_leaf_swapped(L.col0 + pp.off_i, pp.ln_i, i - pp.off_i, a0);
+            for (int d = pp.n_i - 1; d >= 0; --d) left = __dadd_rn(left, M.sib[SIB_MAX + d]);
+            double right = pw_leaf_swapped(L.col0 + pp.off_j, pp.ln_j, j - pp.off_j, b0);
+            for (int d = pp.n_j - 1; d >= 0; --d) right = __dadd_rn(right, M.sib[2 * SIB_MAX + d]);
+            sum = __dadd_rn(left, right);
+        } else {
+            sum = pw_leaf_swapped(L.col0 + pp.off, pp.ln, i - pp.off, a0, j - pp.off, b0);
+        }
+        for (int d = pp.n_up - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
+    } else {
+        sum = pw_leaf_swapped(L.col0, T, i, a0, j, b0);
+    }
+    const int n_real = rest.real + (a0 > 0.0) + (b0 > 0.0);
+    return merit_of(sum, n_real, fmin(fmin(rest.min, a1), b1), p2, p3, L.bounds);
+}
+
 // One pair sweep from the state in LDS by the NT threads of the problem's workgroup: for every slot pair i < j in order (max_span = s
 // > 0: only j <= i + s), threads stride over k = a * len_j + b — the composition with slots i and j replaced by candidates a and b of
 // their lists, current members included — lowest k first, each keeping its best under strict <; the argmin over the workgroup is by
-// (value, k); the pair is taken if it is strictly below the current merit.  A thread continues the carried prefix pre2 / pre3
-// (np.cumprod up to slot i - 1) with row a, cur[i+1 .. j-1], row b, cur[j+1 .. T-1], one __dmul_rn each: numpy's order.  Returns the
-// number of pairs taken.  Bounded by T and list lengths; (i, j) and every barrier are workgroup-uniform, the k loop has no barrier.
+// (value, k); the pair is taken if it is strictly below the current merit.  A thread evaluates its products by pair_merit with the
+// carried prefix pre2 / pre3 (np.cumprod up to slot i - 1).  Returns the number of pairs taken.  Bounded by T and list lengths;
+// (i, j) and every barrier are workgroup-uniform, the k loop has no barrier.
 //
-// np.sum above 128 slots (workgroup form only) replaces two elements of numpy's recursion tree.  Both in one leaf block: that leaf
-// with both replaced, then the untouched siblings up to the root (M.sib[0 ..], as in the one-swap sweep).  In two leaves: the tree
-// node where their paths part (the lowest common ancestor) has slot i in its left child and slot j in its right; a thread sums each
-// leaf with its own element in it, adds the untouched siblings of each path up to that child (M.sib[SIB_MAX ..] for i,
-// M.sib[2 SIB_MAX ..] for j), adds left + right, and goes on up the common path — the recursion's own additions (a + b rounds as
-// b + a).  The sibling sums are formed per (i, j) by pw_sum, the waves taking them in turn.
+// np.sum above 128 slots (workgroup form only) replaces two elements of numpy's recursion tree (pair_path, pair_merit): where the
+// slots lie in two leaves, the tree node where their paths part (the lowest common ancestor) has slot i in its left child and slot
+// j in its right, and the additions are the recursion's own (a + b rounds as b + a).
 //
 // SHORT: the sweep runs over the shortlists M.list (form_shortlists, formed by the caller before the sweep and left as they are
 // through it): a and b are the ia-th and ib-th kept position of their lists, k = ia * |S_j| + ib; everything else is the same code.
@@ -497,92 +623,17 @@ __device__ __forceinline__ int pair_sweep(const DescendMem& M, DescendState& S, 
         const int* si = SHORT ? M.list + (size_t)i * M.rank : nullptr;
         const int j_end = max_span > 0 && max_span < T - 1 - i ? i + max_span + 1 : T;
         for (int j = i + 1; j < j_end; ++j) {
-            int off = 0, ln = T, n_up = 0;                             // the block that holds both slots, its siblings up to the root
-            int off_i = 0, ln_i = 0, n_i = 0, off_j = 0, ln_j = 0, n_j = 0;      // two leaves: each slot's leaf and its path's length
-            bool two = false;
-            if constexpr (WAVES) {
-                // One walk in three stretches (part 0: the common path from the root, 1: slot i's below the parting node, 2: slot
-                // j's), so that pw_sum stands once; the waves take the siblings in turn.  Thread-uniform, no barrier inside.
-                int part = 0, o = 0, l = T, d = 0, turn = 0, right_o = 0, right_l = 0;
-                for (int step = 0; step < 3 * SIB_MAX + 4; ++step) {
-                    if (l <= 128 || d >= SIB_MAX) {                    // a leaf block ends the stretch
-                        if (part == 0) {
-                            off = o; ln = l; n_up = d;
-                            break;
-                        }
-                        if (part == 2) {
-                            off_j = o; ln_j = l; n_j = d;
-                            break;
-                        }
-                        off_i = o; ln_i = l; n_i = d;
-                        part = 2; o = right_o; l = right_l; d = 0;
-                        continue;
-                    }
-                    int n2 = l / 2;
-                    n2 -= n2 % 8;
-                    if (part == 0 && i < o + n2 && j >= o + n2) {      // i left, j right: the paths part here
-                        two = true;
-                        n_up = d;
-                        right_o = o + n2; right_l = l - n2;
-                        part = 1; l = n2; d = 0;
-                        continue;
-                    }
-                    int so, sl;
-                    if ((part == 2 ? j : i) < o + n2) {                // (common path: both slots are on slot i's side)
-                        so = o + n2; sl = l - n2; l = n2;
-                    } else {
-                        so = o; sl = n2; o += n2; l -= n2;
-                    }
-                    if (wave == (turn & (NT / 64 - 1))) {
-                        const double v = pw_sum(L.col0 + so, sl, lane);
-                        if (lane == 0) M.sib[part * SIB_MAX + d] = v;
-                    }
-                    ++turn;
-                    ++d;
-                }
-                __syncthreads();                                       // sib is written, red of the pair before is read
-            }
+            const PairPath pp = pair_path<NT>(M, T, i, j);             // (workgroup form: red of the pair before is read behind it)
             const int bj = L.base[j], lj = SHORT && M.rank < L.len[j] ? M.rank : L.len[j];
             const int* sj = SHORT ? M.list + (size_t)j * M.rank : nullptr;
             const Key n = (Key)li * lj;
-            const double rest_min = S.cr.min_without(i, j);
-            const int rest_real = S.cr.n_real - (L.col0[i] > 0.0) - (L.col0[j] > 0.0);
+            const PairRest rest = pair_rest(M, S.cr, i, j);
             double bf = INFINITY;
             Key bk = std::numeric_limits<Key>::max();
             for (Key k = tid; k < n; k += NT) {                        // products beyond the workgroup: chunks, lowest k first
                 const int ia = (int)(k / lj), ib = (int)(k - (Key)ia * lj);
                 const int a = SHORT ? si[ia] : ia, b = SHORT ? sj[ib] : ib;
-                const double* ra = cand + (size_t)(bi + a) * 4;
-                const double* rb = cand + (size_t)(bj + b) * 4;
-                const double a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
-                double p2 = i == 0 ? ra[2] : __dmul_rn(pre2, ra[2]), p3 = i == 0 ? ra[3] : __dmul_rn(pre3, ra[3]);
-                for (int m = i + 1; m < j; ++m) {
-                    p2 = __dmul_rn(p2, L.col2[m]);
-                    p3 = __dmul_rn(p3, L.col3[m]);
-                }
-                p2 = __dmul_rn(p2, rb[2]);
-                p3 = __dmul_rn(p3, rb[3]);
-                for (int m = j + 1; m < T; ++m) {
-                    p2 = __dmul_rn(p2, L.col2[m]);
-                    p3 = __dmul_rn(p3, L.col3[m]);
-                }
-                double sum;
-                if constexpr (WAVES) {
-                    if (two) {
-                        double left = pw_leaf_swapped(L.col0 + off_i, ln_i, i - off_i, a0);
-                        for (int d = n_i - 1; d >= 0; --d) left = __dadd_rn(left, M.sib[SIB_MAX + d]);
-                        double right = pw_leaf_swapped(L.col0 + off_j, ln_j, j - off_j, b0);
-                        for (int d = n_j - 1; d >= 0; --d) right = __dadd_rn(right, M.sib[2 * SIB_MAX + d]);
-                        sum = __dadd_rn(left, right);
-                    } else {
-                        sum = pw_leaf_swapped(L.col0 + off, ln, i - off, a0, j - off, b0);
-                    }
-                    for (int d = n_up - 1; d >= 0; --d) sum = __dadd_rn(sum, M.sib[d]);
-                } else {
-                    sum = pw_leaf_swapped(L.col0, T, i, a0, j, b0);
-                }
-                const int n_real = rest_real + (a0 > 0.0) + (b0 > 0.0);
-                const double f = merit_of(sum, n_real, fmin(fmin(rest_min, a1), b1), p2, p3, L.bounds);
+                const double f = pair_merit<NT>(M, rest, cand + (size_t)(bi + a) * 4, cand + (size_t)(bj + b) * 4, T, i, j, pp, pre2, pre3);
                 if (f < bf) {
                     bf = f;
                     bk = k;
@@ -698,54 +749,142 @@ __device__ __forceinline__ void descend_pairs_problem(const DescendMem& M, const
     }
 }
 
-// ---- tabu walk: leave the one-swap optimum by the best single swap, improving or not ----------------------------------------------------
+// ---- tabu walk: leave the one-swap optimum by the best single swap — or (pair-move walk) single or pair swap — improving or not --------------
 struct TabuOut {
     double* best_fitness; double* start_fitness; int32_t* best_pos; double* history; int32_t* sweeps; int32_t* moves;
     double* walk; int32_t* steps; int32_t* best_step; int32_t* stalled;
+    int32_t* pair_steps;       // the pair-move walk only
 };
+
+// A step's key.  The tabu walk: base[j] + c of the single swap, an int; INT_MAX: no admissible move.  The pair-move walk: 64 bits —
+// a single's base[j] + c as it is, a pair (i, j, ia, ib) as PAIR_MOVE | (i * T + j) << 32 | ia * |S_j| + ib, so every single comes
+// before every pair and the pairs in the order of (i, j, a, b): the shortlists are ascending.  The fields cannot overflow: a form's
+// LDS holds T doubles per column and max_cand merits, so i * T + j < 2^30 and ia * |S_j| + ib <= max_cand^2 < 2^31.
+template <bool PAIRS>
+using tabu_key_t = std::conditional_t<PAIRS, long long, int>;
+constexpr long long PAIR_MOVE = 1ll << 62;
 
 // One step's evaluation, form_shortlists' slot loop: for every slot j in order, thread = one candidate c != cur[j] of its list (chunks
 // beyond the workgroup, lowest position first), the single-swap merit f by slot_path / one_swap_merit with pre2 / pre3 carried across
 // the slots and S.cr constant.  (j, c) is admissible where expire[base[j] + c] < t, or f < best_f (aspiration).  A thread keeps its
-// best admissible (f, base[j] + c) under strict < — its keys only grow, so the lowest stays among equals, and a NaN never enters —
-// and ONE (value, key) argmin over the workgroup follows the last slot.  key = INT_MAX: no admissible move.  Nothing moves here.
-// Bounded by T and list lengths; j and every barrier are workgroup-uniform.
-template <int NT>
-__device__ __forceinline__ void tabu_step(const DescendMem& M, const DescendState& S, const int* expire, int t, double best_f, double& f_out,
-                                          int& key_out) {
+// best admissible (f, key) under strict < — its keys only grow, so the lowest stays among equals, and a NaN never enters — and ONE
+// (value, key) argmin over the workgroup ends the step.  key = the type's maximum: no admissible move.  Nothing moves here.
+// Bounded by T, list lengths and the rank; j, (i, j) of the workgroup form and every barrier are workgroup-uniform.
+//
+// PAIRS (the pair-move walk): the same slot loop also forms the shortlists of the current composition — a list longer than the rank
+// leaves its merits, cur[j]'s among them, in M.mer for keep_lowest — and the pair pass follows: every i < j (max_span = s > 0: only
+// j <= i + s), every (ia, ib) of S_i x S_j with a != cur[i] and b != cur[j], f by pair_merit; the pair is admissible where neither
+// position is tabu, or f < best_f.  Lane form: np.sum is one leaf and nothing is shared per slot pair, so the lanes stride over ALL
+// (i, j, ia, ib) of the step — a lane walks the slot pairs with its offset k into the current one and carries its own prefix —
+// and a pair's few products do not leave most lanes idle.  Workgroup form: the sibling sums are per (i, j) (pair_path), the threads
+// stride over a pair's products and a barrier frees the sums for the next pair.
+template <int NT, bool PAIRS>
+__device__ __forceinline__ void tabu_step(const DescendMem& M, const DescendState& S, const int* expire, int t, double best_f, int32_t max_span,
+                                          double& f_out, tabu_key_t<PAIRS>& key_out) {
+    using Key = tabu_key_t<PAIRS>;
     const WideLds& L = M.L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, T = S.T;
     const double* cand = S.cand;
     double pre2 = 1.0, pre3 = 1.0;                                    // np.cumprod of columns 2 and 3 up to slot j - 1
     double bf = INFINITY;
-    int bk = INT_MAX;
+    Key bk = std::numeric_limits<Key>::max();
     for (int j = 0; j < T; ++j) {
         const SlotPath sp = slot_path<NT>(M, T, j);
         const int bj = L.base[j], lj = L.len[j], cj = M.cur[j];
         const double old0 = L.col0[j];
+        const bool ranked = PAIRS && M.rank < lj;                     // the list is longer than its shortlist: every merit is wanted
         for (int c = tid; c < lj; c += NT) {
-            if (c == cj) continue;
+            if (c == cj && !ranked) continue;
             const double f = one_swap_merit<NT>(M, S.cr, cand + (size_t)(bj + c) * 4, T, j, sp, old0, pre2, pre3);
-            if ((expire[bj + c] < t || f < best_f) && f < bf) {
+            if constexpr (PAIRS)
+                if (ranked) M.mer[c] = f;
+            if (c != cj && (expire[bj + c] < t || f < best_f) && f < bf) {
                 bf = f;
                 bk = bj + c;
             }
         }
-        if constexpr (NT > 64)
+        if constexpr (PAIRS) {
+            int* row = M.list + (size_t)j * M.rank;
+            const int keep = ranked ? M.rank : lj;
+            if (ranked) {
+                __syncthreads();
+                keep_lowest<NT>(M, row, lj, keep);
+            } else {
+                for (int c = tid; c < lj; c += NT) row[c] = c;
+            }
+            for (int k = keep + tid; k < M.rank; k += NT) row[k] = -1;
+            __syncthreads();                                          // the row stands; mer / rk / sib are free for slot j + 1
+        } else if constexpr (NT > 64) {
             if (sp.depth > 0) __syncthreads();                        // sib is free for slot j + 1
+        }
         pre2 = j == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[j]);
         pre3 = j == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[j]);
     }
+    if constexpr (PAIRS) {
+        const int rank = M.rank;
+        // product k of the slot pair (i, j), |S_j| = lj: evaluated unless it leaves a slot where it is, kept if admissible and better
+        auto try_pair = [&](int i, int j, int lj, long long k, const PairPath& pp, const PairRest& rest, double p2, double p3) {
+            const int ia = (int)(k / lj), ib = (int)(k - (long long)ia * lj);
+            const int a = M.list[(size_t)i * rank + ia], b = M.list[(size_t)j * rank + ib];
+            if (a == M.cur[i] || b == M.cur[j]) return;
+            const int ka = L.base[i] + a, kb = L.base[j] + b;
+            const double f = pair_merit<NT>(M, rest, cand + (size_t)ka * 4, cand + (size_t)kb * 4, T, i, j, pp, p2, p3);
+            if (((expire[ka] < t && expire[kb] < t) || f < best_f) && f < bf) {
+                bf = f;
+                bk = PAIR_MOVE | (long long)(i * T + j) << 32 | k;
+            }
+        };
+        auto kept = [&](int s) { return rank < L.len[s] ? rank : L.len[s]; };      // |S_s|
+        pre2 = pre3 = 1.0;                                            // np.cumprod up to slot i - 1
+        if constexpr (NT > 64) {
+            for (int i = 0; i < T; ++i) {
+                const int li = kept(i);
+                const int j_end = max_span > 0 && max_span < T - 1 - i ? i + max_span + 1 : T;
+                for (int j = i + 1; j < j_end; ++j) {
+                    const PairPath pp = pair_path<NT>(M, T, i, j);
+                    const PairRest rest = pair_rest(M, S.cr, i, j);
+                    const int lj = kept(j);
+                    const long long n = (long long)li * lj;
+                    for (long long k = tid; k < n; k += NT) try_pair(i, j, lj, k, pp, rest, pre2, pre3);
+                    __syncthreads();                                  // sib is free for the next pair
+                }
+                pre2 = i == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[i]);
+                pre3 = i == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[i]);
+            }
+        } else {
+            // Every turn either passes a slot pair whose products lie before this lane's next one or evaluates one product: bounded by
+            // the number of slot pairs plus the lane's share of the products.  No barrier and no shuffle inside: the lanes part here.
+            const PairPath pp = pair_path<NT>(M, T, 0, 1);            // one leaf: the same for every pair
+            int i = 0, j = 1;
+            long long k = tid;                                        // this lane's next product, counted from the first one of (i, j)
+            while (i < T - 1) {
+                const int lj = kept(j);
+                const long long n = (long long)kept(i) * lj;
+                if (k < n) {
+                    try_pair(i, j, lj, k, pp, pair_rest(M, S.cr, i, j), pre2, pre3);
+                    k += NT;
+                    continue;
+                }
+                k -= n;
+                if (++j < (max_span > 0 && max_span < T - 1 - i ? i + max_span + 1 : T)) continue;
+                pre2 = i == 0 ? L.col2[0] : __dmul_rn(pre2, L.col2[i]);
+                pre3 = i == 0 ? L.col3[0] : __dmul_rn(pre3, L.col3[i]);
+                ++i;
+                j = i + 1;
+            }
+        }
+    }
     wave_argmin(bf, bk, lane);
     if constexpr (NT > 64) {
+        Key* red_k = PAIRS ? reinterpret_cast<Key*>(L.red + 4) : reinterpret_cast<Key*>(L.cnt);      // 64-bit keys: red[4 .. 7], as pair_sweep
         if (lane == 0) {
             L.red[wave] = bf;
-            L.cnt[wave] = bk;
+            red_k[wave] = bk;
         }
         __syncthreads();
         bf = L.red[0];
-        bk = L.cnt[0];
-        for (int w = 1; w < NT / 64; ++w) take_better(bf, bk, L.red[w], L.cnt[w]);
+        bk = red_k[0];
+        for (int w = 1; w < NT / 64; ++w) take_better(bf, bk, L.red[w], red_k[w]);
     }
     f_out = bf;
     key_out = bk;
@@ -758,11 +897,14 @@ __device__ __forceinline__ void tabu_step(const DescendMem& M, const DescendStat
 // step taken is best_step, and it did not stall) the one-swap sweeps run once more from there: best need not be a one-swap optimum.
 // history[t - 1] = the best merit after step t (past the last step the last such value, before the polish; max_steps = 0: phase
 // 0's merit), walk[t - 1] = the current merit after step t, NaN past the last step.
-template <int NT, bool TABLE_IN_LDS>
+//
+// PAIRS: the pair-move walk (tests/tabu_pairs_reference.py) — the same walk whose step may take a pair of the slots' shortlists
+// (tabu_step); both slots of a pair bar the positions they leave, and pair_steps counts the steps that took one.
+template <int NT, bool TABLE_IN_LDS, bool PAIRS = false>
 __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const Shape& sh, const int32_t* __restrict__ cand_ptr,
                                                      const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
                                                      const int32_t* __restrict__ start_pos, int32_t max_sweeps, int32_t max_steps,
-                                                     int32_t tenure, const TabuOut& o) {
+                                                     int32_t tenure, const TabuOut& o, int32_t max_span = 0) {
     const WideLds& L = M.L;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int ld = max_steps > 1 ? max_steps : 1;                  // history and walk have at least one entry per problem
@@ -776,6 +918,7 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
             o.steps[p] = -1;
             o.best_step[p] = 0;
             o.stalled[p] = 0;
+            if constexpr (PAIRS) o.pair_steps[p] = 0;
         }
         return;
     }
@@ -784,29 +927,45 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
     const int n_cand = L.base[T - 1] + L.len[T - 1];               // the lists are contiguous (descend_load checked them)
     for (int i = tid; i < n_cand; i += NT) M.expire[i] = 0;
     __syncthreads();
-    int sweeps = 0, moves = 0, steps = 0, best_step = 0, stalled = 0;
+    int sweeps = 0, moves = 0, steps = 0, best_step = 0, stalled = 0, pair_steps = 0;
     bool settled = false;
     one_swap_sweeps<NT>(M, S, max_sweeps, nullptr, sweeps, moves, settled);
     double best_f = S.fit;
     for (int j = tid; j < T; j += NT) M.best[j] = M.cur[j];
     for (int t = 1; t <= max_steps; ++t) {
         double f;
-        int key;
-        tabu_step<NT>(M, S, M.expire, t, best_f, f, key);
-        if (key == INT_MAX) {                                         // workgroup-uniform
+        tabu_key_t<PAIRS> key;
+        tabu_step<NT, PAIRS>(M, S, M.expire, t, best_f, max_span, f, key);
+        if (key == std::numeric_limits<tabu_key_t<PAIRS>>::max()) {   // workgroup-uniform
             stalled = 1;
             break;
         }
-        for (int j = tid; j < T; j += NT) {                            // the one thread whose slot owns the key moves
-            const int c = key - L.base[j];
-            if (c < 0 || c >= L.len[j]) continue;
-            const double* r = cand + (size_t)key * 4;
+        auto move = [&](int j, int c) {                                // slot j goes to position c and bars the one it leaves
+            const double* r = cand + (size_t)(L.base[j] + c) * 4;
             M.expire[L.base[j] + M.cur[j]] = tenure > INT_MAX - t ? INT_MAX : t + tenure;
             M.cur[j] = c;
             L.col0[j] = r[0];
             M.col1[j] = r[1];
             L.col2[j] = r[2];
             L.col3[j] = r[3];
+        };
+        bool pair = false;
+        if constexpr (PAIRS) pair = key >= PAIR_MOVE;
+        if (pair) {                                                   // workgroup-uniform; the shortlists stand as the step formed them
+            if constexpr (PAIRS) {
+                if (tid == 0) {
+                    const int ij = (int)((key ^ PAIR_MOVE) >> 32), i = ij / T, j = ij - i * T, k = (int)(key & 0x7fffffff);
+                    const int lj = M.rank < L.len[j] ? M.rank : L.len[j], ia = k / lj, ib = k - ia * lj;
+                    move(i, M.list[(size_t)i * M.rank + ia]);
+                    move(j, M.list[(size_t)j * M.rank + ib]);
+                }
+                ++pair_steps;
+            }
+        } else {
+            for (int j = tid; j < T; j += NT) {                        // the one thread whose slot owns the key moves
+                const int c = (int)key - L.base[j];
+                if (c >= 0 && c < L.len[j]) move(j, c);
+            }
         }
         S.fit = f;
         steps = t;
@@ -850,6 +1009,7 @@ __device__ __forceinline__ void descend_tabu_problem(const DescendMem& M, const 
         o.steps[p] = steps;
         o.best_step[p] = best_step;
         o.stalled[p] = stalled;
+        if constexpr (PAIRS) o.pair_steps[p] = pair_steps;
     }
 }
 }  // namespace
@@ -953,6 +1113,28 @@ __global__ __launch_bounds__(WNT) void descend_tabu_wide_kernel(Shape sh, const 
     descend_tabu_problem<WNT, false>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o);
 }
 
+// ---- pair-move tabu walk, lane form: one wavefront per problem (<= 64 slots) -----------------------------------------------------------------
+// No atomics, no waits on other workgroups; loops bounded by max_steps, max_sweeps, T, list lengths, the rank.
+__global__ __launch_bounds__(64) void descend_tabu_pairs_kernel(Shape sh, const int32_t* __restrict__ cand_ptr, const double* __restrict__ cand_g,
+                                                                const double* __restrict__ bounds_g, const int32_t* __restrict__ start_pos,
+                                                                int32_t max_sweeps, int32_t max_steps, int32_t tenure, int32_t max_span,
+                                                                int32_t rank, TabuOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    descend_tabu_problem<64, true, true>(lane_mem(lds_raw, Build::tabu_pairs, sh, rank), sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps,
+                                         max_steps, tenure, o, max_span);
+}
+
+// Pair-move tabu walk, workgroup form.
+__global__ __launch_bounds__(WNT) void descend_tabu_pairs_wide_kernel(Shape sh, const int32_t* __restrict__ cand_ptr,
+                                                                      const double* __restrict__ cand_g, const double* __restrict__ bounds_g,
+                                                                      const int32_t* __restrict__ start_pos, int32_t max_sweeps,
+                                                                      int32_t max_steps, int32_t tenure, int32_t max_span, int32_t rank,
+                                                                      TabuOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const DescendMem M = wide_mem(lds_raw, Build::tabu_pairs, sh, o.best_pos, rank);
+    descend_tabu_problem<WNT, false, true>(M, sh, cand_ptr, cand_g, bounds_g, start_pos, max_sweeps, max_steps, tenure, o, max_span);
+}
+
 // LDS bytes one problem needs (host side): what the form's carve-up takes from a null base with the launch's maxima.
 static size_t descend_lds_bytes(bool use_wide, Build build, int max_slots, int max_cand, int rank) {
     DescendMem M;
@@ -965,10 +1147,11 @@ struct DescendArgs {
     const double* bounds; const int32_t* start_pos; int32_t max_sweeps, wide; double* best_rows; void* stream;
 };
 
-// The five descent entries: their argument checks (`who` names the entry in every message; options_ok / operands_given: the entry's
+// The six descent entries: their argument checks (`who` names the entry in every message; options_ok / operands_given: the entry's
 // own options are >= 0, its own outputs not NULL) and the one launch of `build` — `lane` or `wide`, whose parameters behind
 // max_sweeps are `rest`.  Lane form: the table in LDS, so max_cand >= 1 and within a CU; workgroup form: the columns of max_slots
-// slots within a CU.  The shortlist and tabu builds size buffers of their own by max_cand (and `rank`, the shortlists' row) in both forms.
+// slots within a CU.  The shortlist, tabu and pair-move builds size buffers of their own by max_cand (and `rank`, the shortlists' row) in
+// both forms.
 template <typename... P, typename... A>
 static int descend_entry(const char* who, Build build, bool lane_only, const DescendArgs& a, int rank, bool options_ok, bool operands_given,
                          void (*lane)(P...), void (*wide)(P...), const A&... rest) {
@@ -978,18 +1161,20 @@ static int descend_entry(const char* who, Build build, bool lane_only, const Des
     if (lane_only && a.max_slots > 64)
         GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %d slots: the pair sweep has the lane form only (at most 64 slots per problem); "
                    "gnnpn_descend_ragged_f64 descends larger problems by single swaps", who, a.max_slots);
-    const bool use_wide = a.wide || a.max_slots > 64, own = build == Build::shortlist || build == Build::tabu;
+    const bool use_wide = a.wide || a.max_slots > 64, own = has_shortlists(build) || has_tabu_table(build);
     const int max_slots = a.max_slots, max_cand = a.max_cand;
     if (max_cand < 1 && (own || !use_wide)) {
         if (build == Build::one_swap) GNNPN_FAIL(GNNPN_E_ARG, "%s: max_cand must be >= 1 for the lane form", who);
         GNNPN_FAIL(GNNPN_E_UNSUP, "%s: max_cand must be >= 1 (it sizes %s in LDS)", who,
-                   build == Build::pairs ? "the table" : build == Build::shortlist ? "the merit buffer, and in the lane form the table,"
-                                                                                   : "the tabu table, and in the lane form the candidate table,");
+                   build == Build::pairs       ? "the table"
+                   : build == Build::shortlist ? "the merit buffer, and in the lane form the table,"
+                   : build == Build::tabu      ? "the tabu table, and in the lane form the candidate table,"
+                                               : "the tabu table and the merit buffer, and in the lane form the candidate table,");
     }
     const size_t lds = descend_lds_bytes(use_wide, build, max_slots, max_cand, rank);
     auto too_large = [&]() -> int {
         const char* hint = use_wide || build == Build::pairs ? "" : "; wide=1 keeps the candidate table in global memory";
-        if (build == Build::shortlist)
+        if (has_shortlists(build))
             GNNPN_FAIL(GNNPN_E_UNSUP, "%s: %zu B of LDS per problem (%d slots, %d candidates, shortlists of %d) exceed a CU (160 KB)%s", who, lds,
                        max_slots, max_cand, rank, hint);
         if (build == Build::tabu)
@@ -1024,12 +1209,32 @@ extern "C" int gnnpn_descend_tabu_ragged_f64(int32_t B, const int32_t* prob_ptr,
                                              double* start_fitness, int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps,
                                              int32_t* moves, double* walk, int32_t* steps, int32_t* best_step, int32_t* stalled,
                                              void* stream) {
-    const TabuOut o{best_fitness, start_fitness, best_pos, history, sweeps, moves, walk, steps, best_step, stalled};
+    const TabuOut o{best_fitness, start_fitness, best_pos, history, sweeps, moves, walk, steps, best_step, stalled, nullptr};
     return descend_entry("descend_tabu_ragged", Build::tabu, false,
                          {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, 0,
                          max_steps >= 0 && tenure >= 0,
                          best_fitness && start_fitness && best_pos && history && sweeps && moves && walk && steps && best_step && stalled,
                          descend_tabu_kernel, descend_tabu_wide_kernel, max_steps, tenure, o);
+}
+
+// Tabu walk over pair moves (new: no reference counterpart): gnnpn_descend_tabu_ragged_f64 whose step takes the best admissible single
+// swap or pair swap of the slots' shortlists.  max_rank = 0, or above max_cand: whole lists (run with the rank max_cand: no list is
+// longer than its problem's table).  max_cand >= 1 in both forms: it sizes expire and the merit buffer.
+extern "C" int gnnpn_descend_tabu_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                                   const int32_t* cand_ptr, const double* cand, const double* bounds,
+                                                   const int32_t* start_pos, int32_t max_sweeps, int32_t max_steps, int32_t tenure,
+                                                   int32_t max_span, int32_t max_rank, int32_t wide, double* best_fitness,
+                                                   double* start_fitness, int32_t* best_pos, double* best_rows, double* history,
+                                                   int32_t* sweeps, int32_t* moves, double* walk, int32_t* steps, int32_t* best_step,
+                                                   int32_t* stalled, int32_t* pair_steps, void* stream) {
+    const TabuOut o{best_fitness, start_fitness, best_pos, history, sweeps, moves, walk, steps, best_step, stalled, pair_steps};
+    const int rank = max_rank > 0 && max_rank < max_cand ? max_rank : max_cand;
+    return descend_entry("descend_tabu_pairs_ragged", Build::tabu_pairs, false,
+                         {B, prob_ptr, n_lists, max_slots, max_cand, cand_ptr, cand, bounds, start_pos, max_sweeps, wide, best_rows, stream}, rank,
+                         max_steps >= 0 && tenure >= 0 && max_span >= 0 && max_rank >= 0,
+                         best_fitness && start_fitness && best_pos && history && sweeps && moves && walk && steps && best_step && stalled &&
+                             pair_steps,
+                         descend_tabu_pairs_kernel, descend_tabu_pairs_wide_kernel, max_steps, tenure, max_span, rank, o);
 }
 
 // The three pair entries, each with 0 / NULL where it has no span, rank, wide (in `a`) or shortlist.  max_rank = 0: the same launch

@@ -1123,6 +1123,11 @@ def woa_status_error(status, first, replicas=None):
 # merit over §4.8's two configurations, the smaller one on a tie (profiles/r13_tabu_bench.json holds the sweep).
 DEFAULT_TENURE = 16
 
+# The pair-move walk's default rank (the length of the shortlists its pair moves come from).  The rule: the value of
+# tools/bench_tabu_pairs.py's sweep over {1, 2, 4, 8} at max_steps = 32, tenure 16, with the lowest mean merit over §4.8's two
+# configurations, the smaller one on a tie.  The sweep has not been run: 4 is the rule's fallback, unmeasured.
+DEFAULT_PAIR_RANK = 4
+
 
 class SearchTables(dict):
     """The candidate tables of a batch as woa_candidates / woa_candidates_replicas return them: a dict of their keys whose
@@ -1147,6 +1152,10 @@ class SearchTables(dict):
 
     def descend_tabu(self, max_sweeps=16, max_steps=32, tenure=None, wide=None):
         return self._to(descend_tabu_ragged, max_sweeps, max_steps, DEFAULT_TENURE if tenure is None else tenure, wide=wide)
+
+    def descend_tabu_pairs(self, max_sweeps=16, max_steps=32, tenure=None, max_rank=None, max_span=0, wide=None):
+        return self._to(descend_tabu_pairs_ragged, max_sweeps, max_steps, DEFAULT_TENURE if tenure is None else tenure,
+                        DEFAULT_PAIR_RANK if max_rank is None else max_rank, max_span, wide=wide)
 
     def eswoa(self, pop, max_iter, seeds, start_pos=None, wide=None):
         """eswoa_ragged from ``start_pos`` (None: the tables' own)."""
@@ -1497,6 +1506,30 @@ def descend_tabu_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=
     out = _descend_launch("gnnpn_descend_tabu_ragged_f64", "descend_tabu_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps,
                           (int(max_steps), int(tenure), int(bool(wide))), max_slots, max_cand, ld,
                           (("walk", lambda B, dev: torch.empty(B, ld, dtype=F64, device=dev)), ("steps", ()), ("best_step", ()), ("stalled", ())))
+    out["history"] = out["history"][:, :int(max_steps)]
+    out["walk"] = out["walk"][:, :int(max_steps)]
+    return out
+
+
+def descend_tabu_pairs_ragged(prob_ptr, cand_ptr, cand, bounds, start_pos, max_sweeps=16, max_steps=32, tenure=DEFAULT_TENURE,
+                              max_rank=DEFAULT_PAIR_RANK, max_span=0, max_slots=None, max_cand=None, wide=None):
+    """Tabu walk over pair moves, a ragged batch in ONE launch (gnnpn_descend_tabu_pairs_ragged_f64): descend_tabu_ragged's walk whose
+    step takes the best admissible single swap OR pair swap — a pair exchanges two slots (``max_span`` = s > 0: at most s apart) for
+    candidates of their shortlists, the ``max_rank`` candidates of each slot whose single swap into the current composition has the
+    lowest merit, formed anew every step (0: whole lists) — so a product-bound wall that costs the tabu walk two steps, one of them
+    worsening, is crossed in one, and unlike the pair sweeps the walk goes on past a pair optimum.  A pair is tabu where either of
+    its positions is; both slots bar the positions they leave.  Among equal merits a single comes before a pair.  The rank is
+    clamped to the longest list (one small copy to the host), as descend_pairs_shortlist_ragged clamps it.  Deterministic: no draws.
+    Operands and ``wide`` as descend_tabu_ragged.  Returns its dict plus pair_steps [B] i32, the steps that took a pair.  max_steps =
+    0 is descend_ragged's result in every shared field; a problem that is not searched has steps -1."""
+    if isinstance(cand_ptr, torch.Tensor) and cand_ptr.is_cuda and cand_ptr.numel() > 1 and int(max_rank) >= 0:
+        longest = max(int((cand_ptr[1:] - cand_ptr[:-1]).max().item()), 1)
+        max_rank = min(int(max_rank), longest) if int(max_rank) > 0 else longest
+    ld = max(int(max_steps), 1)
+    out = _descend_launch("gnnpn_descend_tabu_pairs_ragged_f64", "descend_tabu_pairs_ragged", prob_ptr, cand_ptr, cand, bounds, start_pos,
+                          max_sweeps, (int(max_steps), int(tenure), int(max_span), int(max_rank), int(bool(wide))), max_slots, max_cand, ld,
+                          (("walk", lambda B, dev: torch.empty(B, ld, dtype=F64, device=dev)), ("steps", ()), ("best_step", ()), ("stalled", ()),
+                           ("pair_steps", ())))
     out["history"] = out["history"][:, :int(max_steps)]
     out["walk"] = out["walk"][:, :int(max_steps)]
     return out

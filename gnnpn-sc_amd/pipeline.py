@@ -174,6 +174,20 @@ STAGES = {s.method: s for s in (
           ("descend_starts_tabu", "max_steps", "tenure"), row_keys=("steps", "best_step"), winner_rows=("walk",)))}
 ONE_SWAP, PAIRS, PAIRS_WINDOWED, PAIRS_SHORTLIST, TABU = STAGES.values()
 
+# The stages added since: the tabu walk over pair moves.  A table of its own beside STAGES, whose five rows the host tests pin by name;
+# ``stage_named`` reads both.
+MORE_STAGES = {s.method: s for s in (
+    Stage("descend_tabu_pairs", ("max_steps", "tenure", "max_rank", "max_span"),
+          "the number of steps, the tenure, the rank and the span must be >= 0, got {}, {}, {} and {}",
+          ("descend_starts_tabu_pairs", "max_steps", "tenure", "max_rank", "max_span"), row_keys=("steps", "best_step", "pair_steps"),
+          winner_rows=("walk",)),)}
+(TABU_PAIRS,) = MORE_STAGES.values()
+
+
+def stage_named(name):
+    """The stage of that method name: STAGES' first, then MORE_STAGES'."""
+    return STAGES[name] if name in STAGES else MORE_STAGES[name]
+
 
 def _search_tables(tabs, max_sweeps, stage=ONE_SWAP):
     """The (bound) stage over the tables; plus n_slots."""
@@ -191,7 +205,7 @@ def _descend_tables(tabs, max_sweeps, pair_rounds=None):
 
 
 def _descend_actions(services, batch, out, max_sweeps, stage, reduct, min_cost, patches):
-    """``descend``, the three ``descend_pairs*`` and ``descend_tabu``: the tables of ``out["actions"]``, the (bound) stage over them,
+    """``descend``, the three ``descend_pairs*``, ``descend_tabu`` and ``descend_tabu_pairs``: the tables of ``out["actions"]``, the (bound) stage over them,
     the quality."""
     actions = out["actions"]
     tabs = ops.woa_candidates(services.cat_ptr, services.qos, batch.x, batch.seg_ptr, batch.local_bounds, batch.global_bounds,
@@ -270,6 +284,31 @@ def descend_starts_tabu(services, batch, starts, max_sweeps=16, max_steps=32, te
 
 
 @torch.no_grad()
+def descend_tabu_pairs(services, batch, out, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, max_rank=ops.DEFAULT_PAIR_RANK, max_span=0,
+                       reduct=0, min_cost=None, patches=()):
+    """Tabu walk over pair moves of ``out["actions"]`` on the device (gnnpn_descend_tabu_pairs_ragged_f64; all problems in one launch,
+    deterministic: no seeds): ``descend_tabu`` whose step takes the best admissible single swap or pair swap — a pair exchanges two
+    slots (``max_span`` = s > 0: at most s apart) for candidates of their shortlists, the ``max_rank`` best single swaps of each
+    slot, formed anew every step (0: whole lists).  It crosses in one step a product-bound wall that costs the tabu walk two, and
+    goes on past the pair optimum at which the pair sweeps stop.  Any slot count.  A negative number of steps, tenure, rank or span
+    raises GnnpnError.  ``ML2PNPipeline.descend_tabu_pairs`` is this, as a method.  Returns ops.descend_tabu_pairs_ragged's dict
+    (``descend_tabu``'s keys plus pair_steps) plus n_slots [B] i32 (and quality [B] f64).  ``max_steps`` = 0: ``descend``'s result
+    in every shared field."""
+    return _descend_actions(services, batch, out, max_sweeps, TABU_PAIRS.bind(max_steps, tenure, max_rank, max_span), reduct, min_cost, patches)
+
+
+@torch.no_grad()
+def descend_starts_tabu_pairs(services, batch, starts, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, max_rank=ops.DEFAULT_PAIR_RANK,
+                              max_span=0, reduct=0, min_cost=None, patches=()):
+    """``descend_starts`` whose B * N rows go through the tabu walk over pair moves (gnnpn_descend_tabu_pairs_ragged_f64 in place of
+    the descent launch); the same selection (gnnpn_descend_select_f64, unchanged) picks the winner: ``descend_starts_tabu``'s result
+    plus pair_steps [B] i32 (the winner's) and pair_steps_all [B, N] i32.  A negative number of steps, tenure, rank or span raises
+    GnnpnError.  ``ML2PNPipeline.descend_starts_tabu_pairs`` is this, as a method."""
+    return _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches,
+                           TABU_PAIRS.bind(max_steps, tenure, max_rank, max_span, who="descend_starts_tabu_pairs"))
+
+
+@torch.no_grad()
 def descend_starts(services, batch, starts, max_sweeps=16, reduct=0, min_cost=None, patches=()):
     """Multi-start descent: ``descend`` from N start compositions per problem, the lowest local optimum kept.  ``starts``: a
     [B, N, T', 8|9] tensor (float32 or float64) or a mapping with ``actions_all`` (what ``best_of(..., return_all=True)`` returns);
@@ -310,7 +349,7 @@ def descend_starts_pairs_shortlist(services, batch, starts, max_sweeps=16, pair_
 
 
 def _descend_starts(services, batch, starts, max_sweeps, reduct, min_cost, patches, stage):
-    """The four ``descend_starts*``: the tables of every start, the (bound) stage over them, the selection, the per-start fields
+    """The ``descend_starts*``: the tables of every start, the (bound) stage over them, the selection, the per-start fields
     (the stage's own among them), the quality."""
     all_rows = starts["actions_all"] if hasattr(starts, "keys") else starts
     if not isinstance(all_rows, torch.Tensor) or all_rows.dim() != 4 or all_rows.shape[3] not in (8, 9):
@@ -599,6 +638,18 @@ class ML2PNPipeline:
         call: ``run`` / ``capture`` are unchanged."""
         return descend_tabu(services, batch, out, max_sweeps=max_sweeps, max_steps=max_steps, tenure=tenure, reduct=reduct,
                             min_cost=min_cost, patches=patches)
+
+    def descend_tabu_pairs(self, services, batch, out, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, max_rank=ops.DEFAULT_PAIR_RANK,
+                           max_span=0, reduct=0, min_cost=None, patches=()):
+        """Tabu walk over pair moves of ``out["actions"]``: module-level ``descend_tabu_pairs`` (it needs no network).  An extra call."""
+        return descend_tabu_pairs(services, batch, out, max_sweeps=max_sweeps, max_steps=max_steps, tenure=tenure, max_rank=max_rank,
+                                  max_span=max_span, reduct=reduct, min_cost=min_cost, patches=patches)
+
+    def descend_starts_tabu_pairs(self, services, batch, starts, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE,
+                                  max_rank=ops.DEFAULT_PAIR_RANK, max_span=0, reduct=0, min_cost=None, patches=()):
+        """Multi-start tabu walk over pair moves: module-level ``descend_starts_tabu_pairs`` (it needs no network).  An extra call."""
+        return descend_starts_tabu_pairs(services, batch, starts, max_sweeps=max_sweeps, max_steps=max_steps, tenure=tenure, max_rank=max_rank,
+                                         max_span=max_span, reduct=reduct, min_cost=min_cost, patches=patches)
 
     def descend_starts_tabu(self, services, batch, starts, max_sweeps=16, max_steps=32, tenure=ops.DEFAULT_TENURE, reduct=0, min_cost=None,
                             patches=()):

@@ -940,6 +940,38 @@ int gnnpn_descend_tabu_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_
                                   double* start_fitness, int32_t* best_pos, double* best_rows, double* history, int32_t* sweeps,
                                   int32_t* moves, double* walk, int32_t* steps, int32_t* best_step, int32_t* stalled, void* stream);
 
+/* Tabu walk over pair moves (csrc/descend.hip).  New: no reference counterpart.  gnnpn_descend_tabu_ragged_f64 whose step may take a
+ * single swap or a pair swap: the pair sweeps go downhill only and stop at the first pair optimum, the tabu walk pays two steps, one
+ * of them worsening, for every product-bound wall a pair crosses in one; this walk has both properties.  Operands as that entry,
+ * with max_span and max_rank between tenure and wide and pair_steps [B] int32 behind stalled; the same two forms (wide != 0 or
+ * max_slots > 64: one workgroup per problem).  Per problem:
+ *   Phase 0, Polish, history, walk, steps, best_step, stalled   as gnnpn_descend_tabu_ragged_f64.
+ *   Step t        singles: that entry's — every slot j in order, every position c != cur[j] of its WHOLE list; tabu iff
+ *                 expire[j][c] >= t.  Then the shortlists of the current composition, as gnnpn_descend_pairs_shortlist_ragged_f64
+ *                 forms them (per slot the min(max_rank, len) candidates whose single swap has the lowest merit, positions
+ *                 ascending, a NaN last; max_rank = 0 or at least the list's length: the whole list), anew every step and from the
+ *                 same single-swap merits; a shortlist may hold cur[j].  Pairs: every i < j in lexicographic order (max_span = s >
+ *                 0: only j <= i + s), every a of S_i and b of S_j with a != cur[i] and b != cur[j]; tabu iff expire[i][a] >= t or
+ *                 expire[j][b] >= t.  A move is admissible iff it is not tabu or its merit is below the best so far (strict).  The
+ *                 admissible move with the smallest merit under plain < is taken, whether or not it is below the current merit: a
+ *                 NaN never, a single before a pair among equals, singles by the lowest (j, c), pairs by the lowest (i, j, a, b).
+ *                 Every slot that moves bars the position it leaves through step t + tenure (saturating).  No admissible move:
+ *                 stalled = 1, the walk ends, step t is not counted.
+ *   pair_steps    the steps that took a pair.
+ * max_steps = 0 is gnnpn_descend_ragged_f64's run in every shared field; the result is never above that entry's.  A problem that is
+ * not searched leaves gnnpn_descend_tabu_ragged_f64's record plus pair_steps 0.  max_cand is read in BOTH forms: the tabu table, the
+ * merits of one list (8 B per candidate), their ranks and the shortlists (4 B x slots x the rank, the rank clamped to max_cand) live
+ * in LDS beside the form's own state.  No atomics, no waits on other workgroups, every loop bounded by max_steps, max_sweeps, T, a
+ * list length or the rank.  GNNPN_E_ARG: a negative scalar, max_slots < 1, a null operand (best_rows may be NULL).  GNNPN_E_UNSUP,
+ * nothing launched: max_cand < 1; LDS beyond a CU (the message names slots, candidates, the rank and bytes, and wide=1 where the
+ * workgroup form would take less).  B = 0 returns GNNPN_OK at once. */
+int gnnpn_descend_tabu_pairs_ragged_f64(int32_t B, const int32_t* prob_ptr, int32_t n_lists, int32_t max_slots, int32_t max_cand,
+                                        const int32_t* cand_ptr, const double* cand, const double* bounds, const int32_t* start_pos,
+                                        int32_t max_sweeps, int32_t max_steps, int32_t tenure, int32_t max_span, int32_t max_rank,
+                                        int32_t wide, double* best_fitness, double* start_fitness, int32_t* best_pos, double* best_rows,
+                                        double* history, int32_t* sweeps, int32_t* moves, double* walk, int32_t* steps, int32_t* best_step,
+                                        int32_t* stalled, int32_t* pair_steps, void* stream);
+
 /* Multi-start descent, the selection (csrc/descend.hip).  New: no reference counterpart, as the descent itself — the reference
  * refines one composition per problem.  After ONE gnnpn_descend_ragged_f64 launch over B * R rows (row b * R + r = replica r of
  * problem b, problem-major as in gnnpn_pointer_decode_replicas_f32) it keeps, per problem, the replica with the smallest

@@ -50,6 +50,12 @@
                                          # ML+2PN+multistart+tabu.txt), the descent format plus steps / best_step / stalled.
                                          # Deterministic.  Not with --pairs, --woa or --services
 
+    python main.py QWS ML+2PN -1 --infer --descend[=SWEEPS] --tabu[=STEPS] [--tenure=N] --pair-moves[=RANK] [--pair-span=N] [--samples=N --all-starts]
+                                         # ... whose step may also exchange two slots at once (at most N apart; N = 0: any two) for
+                                         # candidates among the RANK best single swaps of each (the measured default unless given; 0:
+                                         # whole lists): ./solutions/WOA/<ds>/ML+2PN+tabu+pairs.txt (with --all-starts
+                                         # ML+2PN+multistart+tabu+pairs.txt), the tabu format plus pair_steps, top and span
+
     python main.py QWS WOA [epoch]       # ES-WOA fine-tuning of the ML+2PN solution on the GPU (reference main.py:86-104,
                                          # mode ML2PNWOATest of [<ds>-WOA]); --seed N makes the run reproducible
 
@@ -221,6 +227,9 @@ def main(argv):
             ("pair_rounds", "--pairs", "4"), ("pair_span", "--span", ""), ("pair_rank", "--top", ""), ("tabu_steps", "--tabu", "32"),
             ("tenure", "--tenure", ""))}
         rounds, span, top, tabu, tenure = given.values()
+        # the pair moves of the tabu walk: the flag alone asks for the default rank (None below; 0 stands in for it where it is checked)
+        moves_text, pair_span = _valued(flags, "--pair-moves", "default"), _count(_valued(flags, "--pair-span", ""))
+        moves = None if moves_text in (None, "default") else _count(moves_text)
         ok = ML2PN.stage_ok
         for refused, why in (                                       # in the order they are reported: the first one is
                 (all_starts and (samples is None or int(samples) < 2 or sweeps is None),
@@ -238,11 +247,18 @@ def main(argv):
                  "--span=N: not with --all-starts or --woa (multi-start descent and the ES-WOA start take the full pair sweep of at most 64 slots)"),
                 (tabu is not None and not ok("descend_tabu", sweeps, tabu, 0),
                  "--tabu[=STEPS]: needs --descend[=SWEEPS] and STEPS >= 0 (0: the one-swap descent alone)"),
+                ((moves_text is not None or pair_span is not None) and (woa_flag or services),
+                 "--pair-moves[=RANK], --pair-span=N: not with --woa or --services (the ES-WOA start and the services artefact take the "
+                 "descent's result)"),
                 (tabu is not None and (rounds is not None or woa_flag or services),
                  "--tabu[=STEPS]: not with --pairs, --woa or --services (the walk takes single swaps, and the ES-WOA start and the services "
                  "artefact take the descent's result)"),
                 (tenure is not None and not ok("descend_tabu", sweeps, tabu, tenure),
-                 "--tenure=N: needs --tabu[=STEPS] and N >= 0 (0: a slot may go straight back)")):
+                 "--tenure=N: needs --tabu[=STEPS] and N >= 0 (0: a slot may go straight back)"),
+                (moves_text is not None and not ok("descend_tabu_pairs", sweeps, tabu, 0, moves or 0, 0),
+                 "--pair-moves[=RANK]: needs --tabu[=STEPS] and RANK >= 0 (0: whole lists)"),
+                (pair_span is not None and (moves_text is None or not ok("descend_tabu_pairs", sweeps, tabu, 0, moves or 0, pair_span)),
+                 "--pair-span=N: needs --pair-moves[=RANK] and N >= 0 (0: every slot pair)")):
             if refused:
                 print(why)
                 return 1
@@ -268,7 +284,10 @@ def main(argv):
         if all_starts:                                              # descent from every best-of-N replica, the lowest optimum kept
             best["all_starts"] = True
         # the stage's own infer_*; with --services infer_services: the same run, plus ML+2PN+services.txt: which services it found
-        run = ML2PN.infer_services if services else getattr(ML2PN, ML2PN.RUNS[ML2PN.stage_given(rounds, span, top, tabu)][2])
+        if moves_text is not None:                                  # the tabu walk's pair moves, under infer_tabu_pairs' names for them
+            best.update(pair_rank=moves, pair_span=pair_span or 0)
+        run = ML2PN.infer_services if services else getattr(
+            ML2PN, ML2PN.run_named(ML2PN.stage_given(rounds, span, top, tabu, moves_text))[2])
         if run in (ML2PN.infer, ML2PN.infer_services):              # the two with ES-WOA behind the stage (--woa is refused above beside the others)
             best["woa"] = woa
         run(ds, net, low, high, K, epoch, **best)

@@ -13,7 +13,7 @@ GPU test file, each file named ``<test file stem>.<n>.kernel_stats.csv`` (n: one
 them go through the same normalisation (plus a ``.kd`` suffix dropped).  A traced name whose family is one of the library's
 but which is no build of the inventory is an error: the normalisation, or the record, is out of date.
 
-The record is tests/golden/agreement_kernel_record_tabu.json: per build ``reached_by`` (written here) and ``checked_by`` (one pytest
+The record is tests/golden/agreement_kernel_record_tabu_pairs.json: per build ``reached_by`` (written here) and ``checked_by`` (one pytest
 node id whose test compares this build's own output with a CPU reference) or ``waived`` (a reason; only for kernels that hand
 no numerical result to a caller).  tests/test_kernel_inventory_host.py keeps the record and the library in step; it reads the
 record at RECORD below.  (Committed golden files are never edited, so a pull request that adds a kernel build continues the record in
@@ -30,8 +30,9 @@ agreement_kernel_record_attn_decode.json as it stood before score_select_kernel,
 stood before pick_prob_kernel, the ten pointer_decode_lean_kernel builds and the two pointer_decode_coop_kernel builds got checking
 tests of their own (checked_by moved from test_two_level_greedy_golden and test_pointer_decode_cooperative_build to
 tests/test_gpu_decode_replay.py, no new build), agreement_kernel_record_decode_replay.json as it stood before the tabu walk
-(descend_tabu_kernel, descend_tabu_wide_kernel); the current record repeats every row of its predecessors, with reached_by grown by
-the new GPU test file where there is one; nothing reads the ten older files.)
+(descend_tabu_kernel, descend_tabu_wide_kernel), agreement_kernel_record_tabu.json as it stood before the walk over pair moves
+(descend_tabu_pairs_kernel, descend_tabu_pairs_wide_kernel); the current record repeats every row of its predecessors, with
+reached_by grown by the new GPU test file where there is one; nothing reads the eleven older files.)
 """
 import argparse
 import csv
@@ -44,7 +45,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "gnnpn-sc_amd", "libgnnpn_hip.so")
-RECORD = os.path.join(ROOT, "tests", "golden", "agreement_kernel_record_tabu.json")
+RECORD = os.path.join(ROOT, "tests", "golden", "agreement_kernel_record_tabu_pairs.json")
 NO_RESULT_KERNELS = ("lds_interferer_kernel", "gate_wait_kernel", "coop_zero_kernel")   # hand no numerical result to a caller
 MAX_WAIVED = 4
 
